@@ -7,17 +7,23 @@ A "step" is one pass of the hot path over one resident batch, exactly the per-ba
 the reference's fit loop (deepctr/models/basemodel.py:245-262): forward -> BCE(sum) -> L2 term ->
 backward -> Adam step.  Inputs are in HBM before the timed region starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  The timed K steps run the way `fit` runs them: replayed from the HIP graph
-the model captured on its third step (single process; eager launches when row-parallel).  `roofline`
-describes the dominant hand-written kernel by summed device time, measured live right after the timed
-region over up to 10 of the same steps issued eagerly with HIP events around every launch on the launch
-stream (events cannot be recorded inside a graph replay; `profiles/` holds the rocprofv3 summary of the
-same command); `other_arithmetic` repeats the K steps with the other CIN arithmetic; `cpu_baseline` is
-the CPU oracle (a port of the reference's op sequence) timed on this host's cores on a bounded sample.
+the model captured on its third step (single process; eager launches when row-parallel).  A plain run
+sets up, warms up, times the K steps and prints the headline figures; `--dump-outputs DIR` then writes
+what the last timed step computed (see dump_outputs) as DIR/<name>.npy.
+
+`--full` adds the side measurements, each of which takes runs of its own (`--no-alt`, `--no-extras` and
+`--no-cpu-baseline` leave parts of them out): `roofline` and `kernels` describe the dominant hand-written
+kernel by summed device time, measured live right after the timed region over up to 10 of the same steps
+issued eagerly with HIP events around every launch on the launch stream (events cannot be recorded inside
+a graph replay; `profiles/` holds the rocprofv3 summary of the same command); `other_arithmetic` repeats
+the K steps with the other CIN arithmetic; the extras time a long region, `fit` / `predict`, uniform ids,
+the mid vocabulary, the SFG model, the lazy-Adam opt-in and the dense Adam sweep; `cpu_baseline` is the
+CPU oracle (a port of the reference's op sequence) timed on this host's cores on a bounded sample.
 """
 import argparse
 import json
@@ -116,8 +122,33 @@ def build_model(cfg, vocab, device, lazy_rows=False):
 
 def train_step(model, xb, yb, dp):
     """The body of the reference's batch loop (basemodel.py:245-262) as the model's own fit runs it,
-    without the two .item() host syncs (losses stay on the device)."""
-    return model.train_on_batch(xb, yb)[1]
+    without the two .item() host syncs: (y_pred, data loss, total loss), all on the device."""
+    return model.train_on_batch(xb, yb)
+
+
+DUMP_ROWS = 1024
+
+
+def dump_outputs(dirname, model, outs):
+    """What the last timed step computed, as DIR/<name>.npy in float32: the arrays train_on_batch returned
+    (y_pred, data_loss, total_loss) and the parameters the step left behind (param.<name>), every element of a
+    parameter with at most DUMP_ROWS rows and a fixed, seeded sample of DUMP_ROWS rows of a larger one (the
+    embedding tables).  The timed region flushed the deferred table update, so every row is up to date."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = dict(zip(("y_pred", "data_loss", "total_loss"), outs))
+    rng = np.random.default_rng(0)
+    for name, p in model.named_parameters():
+        p = p.detach()
+        if p.dim() > 0 and p.shape[0] > DUMP_ROWS:
+            rows = np.sort(rng.choice(p.shape[0], DUMP_ROWS, replace=False))
+            p = p[torch.from_numpy(rows).to(p.device)]
+        arrays["param." + name] = p
+    total = 0
+    for name, v in arrays.items():
+        a = v.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    log("wrote %d arrays (%.1f MB) to %s" % (len(arrays), total / 2**20, dirname))
 
 
 def usable_cores():
@@ -205,6 +236,72 @@ def pmc_traffic(bracket, workload, math_mode):
                 traffic_source="profiles/r03_pmc_traffic.md (rocprofv3 --pmc over bench.py, eager launches)")
 
 
+def kernel_figures(prof, prof_steps, math_mode, workload, optim):
+    """(roofline, kernels) of the --full line from the event-bracketed launches of `prof_steps` eager steps."""
+    # Every step issues the same launch sequence, so launch k of a name is the same kernel on the same shape in
+    # every profiled step: take the MEDIAN over the steps of each such launch (a host hiccup between the start
+    # event and the launch -- allocator, GC -- would otherwise be billed to the kernel), then add them up.
+    by_name = {}
+    for name, work, e0, e1 in prof:
+        by_name.setdefault(name, []).append((e0.elapsed_time(e1) * 1e-3, work))
+    per_kernel = {}
+    for name, ev in by_name.items():
+        per_step = len(ev) // prof_steps if len(ev) % prof_steps == 0 and len(ev) >= prof_steps else 0
+        if per_step:
+            secs = sum(float(np.median([ev[s * per_step + k][0] for s in range(prof_steps)])) for k in range(per_step))
+            work = sum(ev[k][1] for k in range(per_step))
+            per_kernel[name] = [secs * prof_steps, work * prof_steps, len(ev)]
+        else:
+            per_kernel[name] = [sum(t for t, _ in ev), sum(w for _, w in ev), len(ev)]
+    # the DOMINANT bracketed kernel by summed device time, whatever it is (CIN contraction, attention block, gather,
+    # scatter, optimizer), against the roofline that bounds it
+    cands = {k: v for k, v in per_kernel.items() if v[1] > 0 and not k.endswith("passes")}
+    roof = None
+    if cands:
+        name, (secs, work, n) = max(cands.items(), key=lambda kv: kv[1][0])
+        if name.endswith("[bytes]"):
+            achieved, peak = work / secs / 1e9, HBM_PEAK_GBS
+            roof = dict(kernel=name.replace("[bytes]", ""), bound="hbm", achieved=round(achieved, 1), peak=peak, unit="GB/s",
+                        frac=round(achieved / peak, 4), traffic=None, launches=n, avg_ms=round(secs / n * 1e3, 4),
+                        note="algorithmic bytes per launch (SURVEY.md 8d) / measured launch time")
+        elif name.startswith("vocab_ce"):
+            achieved, peak = work / secs / 1e12, CIN_MATH[1][1]
+            roof = dict(kernel=name, bound="mfma", achieved=round(achieved, 2), peak=round(peak, 1), unit="TFLOP/s",
+                        frac=round(achieved / peak, 4), traffic=None, launches=n, avg_ms=round(secs / n * 1e3, 4),
+                        note="fp32-equivalent FLOPs of the reference's product (2 * positive rows * K * vocabulary rows of all "
+                             "heads per launch; the backward kernels recompute the logits on top of their own product, which "
+                             "is not counted); f16x3 on the matrix pipe, " + CIN_MATH[1][2])
+        elif name.startswith("cin_attn_pool"):
+            achieved, peak = work / secs / 1e12, ATTN_PEAK_TFLOPS
+            roof = dict(kernel=name, bound="mfma", achieved=round(achieved, 2), peak=round(peak, 1), unit="TFLOP/s",
+                        frac=round(achieved / peak, 4), traffic=None, launches=n, avg_ms=round(secs / n * 1e3, 4), note=ATTN_NOTE)
+        else:
+            achieved = work / secs / 1e12
+            peak = CIN_MATH[math_mode][1]
+            roof = dict(kernel=name, bound="mfma", achieved=round(achieved, 2), peak=round(peak, 1),
+                        unit="TFLOP/s", frac=round(achieved / peak, 4), traffic=None,
+                        launches=n, avg_ms=round(secs / n * 1e3, 4),
+                        note="fp32-equivalent FLOPs of the reference's contraction (2*H*Hp*m*N per launch); level 0 "
+                             "(x_prev is x0) contracts over the pairs i <= j with folded weights and issues about half (50-54 %) "
+                             "of the MFMAs counted here for it; " + CIN_MATH[math_mode][2])
+            roof.update(pmc_traffic(name, workload, math_mode))
+    kernels = {}
+    calls_per_step = {k: v[2] / prof_steps for k, v in per_kernel.items()}
+    for k, v in sorted(per_kernel.items()):
+        rate = v[1] / v[0] if v[0] > 0 else 0.0
+        kernels[k.replace("[bytes]", "")] = dict(
+            ms_per_step=round(v[0] / max(v[2], 1) * calls_per_step[k] * 1e3, 4),
+            **({"GBps": round(rate / 1e9, 1), "frac_hbm": round(rate / 1e9 / HBM_PEAK_GBS, 4)}
+               if k.endswith("[bytes]") else ({} if (k.endswith("passes") or v[1] <= 0) else {"TFLOPs": round(rate / 1e12, 2)})))
+    if getattr(optim, "_def", None) is not None and "adam_step" in kernels:
+        # deferred table update: no sweep to price in GB/s -- these are the step's own optimizer kernels (dense weights,
+        # small-table mark scan, big tables by the batch's rows); the catch-up before the gather and the periodic flush
+        # are part of the line's ms_per_step
+        kernels["adam_step"] = {"ms_per_step": kernels["adam_step"]["ms_per_step"],
+                                "note": "deferred table update: per-step optimizer kernels only (see `optimizer`)"}
+    return roof, kernels
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -214,11 +311,16 @@ def main():
     ap.add_argument("--vocab-preset", default=None, choices=["criteo-card", "mid", "small"],
                     help="SURVEY 8d vocabulary preset (default: criteo-card for the 26-field workloads, mid otherwise)")
     ap.add_argument("--vocab", type=int, default=0, help="uniform rows per embedding table (overrides the preset)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the mid-vocabulary and lazy-Adam side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: per-kernel times and roofline, the other CIN arithmetic, the "
+                         "extras and the CPU baseline (the --no-* switches leave parts of them out)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the mid-vocabulary and lazy-Adam side measurements")
     ap.add_argument("--cpu-rows", type=int, default=1024)
     ap.add_argument("--cpu-steps", type=int, default=3)
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the second timed region with the other CIN arithmetic")
+    ap.add_argument("--no-alt", action="store_true", help="--full: skip the second timed region with the other CIN arithmetic")
     ap.add_argument("--option", action="append", default=[], help="libxdfm tuning knob key=value")
     ap.add_argument("--cin-math", type=int, default=None, choices=[0, 1, 2],
                     help="CIN arithmetic: 0 fp32 MFMA, 1 f16x3 (default), 2 bf16 (default for --workload avazu_c5)")
@@ -314,7 +416,7 @@ def main():
             ops.PROFILE = [] if kernel_events else None     # (name, work, start_event, end_event) per heavy launch
             t0 = time.perf_counter()
             for s in range(steps):
-                loss = train_step(self.model, *self.batches[s % self.n_res], dp)
+                self.outs = train_step(self.model, *self.batches[s % self.n_res], dp)
             if flush is not None:
                 flush()                                      # ... and pays everything its K steps deferred before the clock stops
             t_host = time.perf_counter() - t0
@@ -328,7 +430,7 @@ def main():
                 t = torch.tensor([dt], device=device if args.backend == "nccl" else "cpu", dtype=torch.float64)
                 dist.all_reduce(t, op=dist.ReduceOp.MAX)
                 dt = float(t.item())
-            if not np.isfinite(float(loss.item())):
+            if not np.isfinite(float(self.outs[1].item())):
                 raise RuntimeError("non-finite loss in the benchmark loop")
             return dt, t_host, prof
 
@@ -342,10 +444,12 @@ def main():
         dt / args.steps * 1e3, t_host / args.steps * 1e3,
         "HIP graph replay, %d nodes" % max(e.nodes for e in run.gstep.entries.values()) if replayed else "eager launches"))
     dt_local, host_local = run.dt_local, t_host
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.model, run.outs)
     # per-kernel device times for the roofline: the same steps from eager launches, HIP events around each launch
-    _, _, prof = run.timed(min(args.steps, 10), 2, kernel_events=True)
+    prof = run.timed(min(args.steps, 10), 2, kernel_events=True)[2] if args.full else None
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank's own view of the timed region, so that a scaling run explains itself: its wall time before the final
         # barrier, its host time to enqueue a step (the second half of the row-parallel step is launched eagerly), and the
         # device time of ITS scatter (K2 runs over the rows of all ranks on every rank) and gather launches
@@ -361,7 +465,7 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     alt = None
-    if world == 1 and not args.no_alt:
+    if args.full and world == 1 and not args.no_alt:
         # the same K steps with the other arithmetic of the CIN contraction, for reference in the same line
         other = 1 - math_mode if math_mode in (0, 1) else 1          # beside bf16: the f16x3 (fp32-grade) measurement
         _lib.set_option("cin_math", other)
@@ -371,7 +475,7 @@ def main():
                    ms_per_step=round(adt / args.steps * 1e3, 4), arithmetic=CIN_MATH[other][2])
         log("other arithmetic (%s): %.3f ms/step" % (CIN_MATH[other][0], adt / args.steps * 1e3))
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # (0a) one LONG timed region of the same replayed step (400 steps, the periodic flushes of the deferred update inside
         # it and one at its end): the figure a 20-step region can only sample
         ldt, _, _ = run.timed(400, 0)
@@ -423,7 +527,7 @@ def main():
         log("uniform ids: %.3f ms/step" % (udt / args.steps * 1e3))
         del uni
         torch.cuda.empty_cache()
-    if world == 1 and not args.no_extras and args.vocab <= 0 and preset == "criteo-card":
+    if args.full and world == 1 and not args.no_extras and args.vocab <= 0 and preset == "criteo-card":
         # (1) the same step at the mid vocabulary (1e5 rows per field: round 1's headline): what the step costs when the
         # dense-Adam table sweep is small;  (2) the criteo-card step with the OPT-IN row-sparse ("lazy") Adam, which is
         # NOT the reference's arithmetic (untouched rows keep their moments): what the sweep costs the reference's way
@@ -472,68 +576,6 @@ def main():
         torch.cuda.empty_cache()
 
     if rank == 0:
-        # Every step issues the same launch sequence, so launch k of a name is the same kernel on the same shape in
-        # every profiled step: take the MEDIAN over the steps of each such launch (a host hiccup between the start
-        # event and the launch -- allocator, GC -- would otherwise be billed to the kernel), then add them up.
-        prof_steps = min(args.steps, 10)
-        by_name = {}
-        for name, work, e0, e1 in prof:
-            by_name.setdefault(name, []).append((e0.elapsed_time(e1) * 1e-3, work))
-        per_kernel = {}
-        for name, ev in by_name.items():
-            per_step = len(ev) // prof_steps if len(ev) % prof_steps == 0 and len(ev) >= prof_steps else 0
-            if per_step:
-                secs = sum(float(np.median([ev[s * per_step + k][0] for s in range(prof_steps)])) for k in range(per_step))
-                work = sum(ev[k][1] for k in range(per_step))
-                per_kernel[name] = [secs * prof_steps, work * prof_steps, len(ev)]
-            else:
-                per_kernel[name] = [sum(t for t, _ in ev), sum(w for _, w in ev), len(ev)]
-        # the DOMINANT bracketed kernel by summed device time, whatever it is (CIN contraction, attention block, gather,
-        # scatter, optimizer), against the roofline that bounds it
-        cands = {k: v for k, v in per_kernel.items() if v[1] > 0 and not k.endswith("passes")}
-        roof = None
-        if cands:
-            name, (secs, work, n) = max(cands.items(), key=lambda kv: kv[1][0])
-            if name.endswith("[bytes]"):
-                achieved, peak = work / secs / 1e9, HBM_PEAK_GBS
-                roof = dict(kernel=name.replace("[bytes]", ""), bound="hbm", achieved=round(achieved, 1), peak=peak, unit="GB/s",
-                            frac=round(achieved / peak, 4), traffic=None, launches=n, avg_ms=round(secs / n * 1e3, 4),
-                            note="algorithmic bytes per launch (SURVEY.md 8d) / measured launch time")
-            elif name.startswith("vocab_ce"):
-                achieved, peak = work / secs / 1e12, CIN_MATH[1][1]
-                roof = dict(kernel=name, bound="mfma", achieved=round(achieved, 2), peak=round(peak, 1), unit="TFLOP/s",
-                            frac=round(achieved / peak, 4), traffic=None, launches=n, avg_ms=round(secs / n * 1e3, 4),
-                            note="fp32-equivalent FLOPs of the reference's product (2 * positive rows * K * vocabulary rows of all "
-                                 "heads per launch; the backward kernels recompute the logits on top of their own product, which "
-                                 "is not counted); f16x3 on the matrix pipe, " + CIN_MATH[1][2])
-            elif name.startswith("cin_attn_pool"):
-                achieved, peak = work / secs / 1e12, ATTN_PEAK_TFLOPS
-                roof = dict(kernel=name, bound="mfma", achieved=round(achieved, 2), peak=round(peak, 1), unit="TFLOP/s",
-                            frac=round(achieved / peak, 4), traffic=None, launches=n, avg_ms=round(secs / n * 1e3, 4), note=ATTN_NOTE)
-            else:
-                achieved = work / secs / 1e12
-                peak = CIN_MATH[math_mode][1]
-                roof = dict(kernel=name, bound="mfma", achieved=round(achieved, 2), peak=round(peak, 1),
-                            unit="TFLOP/s", frac=round(achieved / peak, 4), traffic=None,
-                            launches=n, avg_ms=round(secs / n * 1e3, 4),
-                            note="fp32-equivalent FLOPs of the reference's contraction (2*H*Hp*m*N per launch); level 0 "
-                                 "(x_prev is x0) contracts over the pairs i <= j with folded weights and issues about half (50-54 %) "
-                                 "of the MFMAs counted here for it; " + CIN_MATH[math_mode][2])
-                roof.update(pmc_traffic(name, args.workload, math_mode))
-        kernels = {}
-        calls_per_step = {k: v[2] / prof_steps for k, v in per_kernel.items()}
-        for k, v in sorted(per_kernel.items()):
-            rate = v[1] / v[0] if v[0] > 0 else 0.0
-            kernels[k.replace("[bytes]", "")] = dict(
-                ms_per_step=round(v[0] / max(v[2], 1) * calls_per_step[k] * 1e3, 4),
-                **({"GBps": round(rate / 1e9, 1), "frac_hbm": round(rate / 1e9 / HBM_PEAK_GBS, 4)}
-                   if k.endswith("[bytes]") else ({} if (k.endswith("passes") or v[1] <= 0) else {"TFLOPs": round(rate / 1e12, 2)})))
-        if getattr(run.model.optim, "_def", None) is not None and "adam_step" in kernels:
-            # deferred table update: no sweep to price in GB/s -- these are the step's own optimizer kernels (dense weights,
-            # small-table mark scan, big tables by the batch's rows); the catch-up before the gather and the periodic flush
-            # are part of the line's ms_per_step
-            kernels["adam_step"] = {"ms_per_step": kernels["adam_step"]["ms_per_step"],
-                                    "note": "deferred table update: per-step optimizer kernels only (see `optimizer`)"}
         m_, nd_, D_ = cfg["n_sparse"], cfg["n_dense"], cfg["emb_dim"]
         gather_bytes = 4 * (m_ + nd_) + m_ * (4 * D_ + 4) + 4 * m_ * D_ + 4 * (m_ * D_ + nd_) + 4
         n_params = sum(p.numel() for p in run.model.parameters())
@@ -548,7 +590,7 @@ def main():
             "dtype_detail": ("fp32 inputs, weights, accumulators, outputs and optimizer state in both CIN arithmetics; "
                              + CIN_MATH[math_mode][2] + (". Error against fp64 <= that of the fp32-MFMA kernels "
                              "(tests/test_gpu_parity.py::test_cin_f16x3_is_as_accurate_as_fp32_mfma); the strict fp32-MFMA "
-                             "measurement of the same K steps is `other_arithmetic`" if math_mode == 1 else "")),
+                             "measurement of the same K steps is `other_arithmetic` (--full)" if math_mode == 1 else "")),
             "config": {"workload": "%s: %d sparse + %d dense, emb_dim %d, cin %s, dnn %s, vocabulary %s (%.1f M rows, %.0f M "
                                    "parameters), per-GPU batch %d, dense Adam + L2 as the reference, fp32" % (
                                        args.workload, cfg["n_sparse"], cfg["n_dense"], cfg["emb_dim"],
@@ -563,12 +605,12 @@ def main():
             "optimizer": ("Adam, the reference's dense update of every table row in every step, computed DEFERRED: rows are brought "
                           "up to date before a batch gathers them, when a gradient arrives, and every %d steps for all rows "
                           "(bit-identical parameters and moments, tests/test_gpu_host.py); every update the timed K steps owe is "
-                          "paid inside the timed region (flush before the clock stops); `dense_adam_sweep` = the same step with "
+                          "paid inside the timed region (flush before the clock stops); `dense_adam_sweep` (--full) = the same step with "
                           "the per-step HBM sweep" % run.model.optim.flush_every)
             if getattr(run.model.optim, "_def", None) is not None else "Adam, dense sweep over every parameter in every step",
-            "roofline": roof,
-            "kernels": kernels,
         }
+        if prof is not None:
+            out["roofline"], out["kernels"] = kernel_figures(prof, min(args.steps, 10), math_mode, args.workload, run.model.optim)
         out.update(extras)
         if ranks_seen is not None:
             out["ranks_seen"] = ranks_seen
@@ -577,7 +619,7 @@ def main():
             out["per_rank"] = per_rank
         if alt is not None:
             out["other_arithmetic"] = alt
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             if "mid_vocab" in extras:
                 del run                              # the CPU oracle needs the host memory and cores, not the GPU model
             out["cpu_baseline"] = cpu_baseline(cfg, vocab, args.cpu_rows, args.cpu_steps)

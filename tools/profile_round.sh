@@ -8,7 +8,7 @@ R=${1:-r03}
 OUT=gpurun_out/$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="--steps 30 --warmup 5 --no-cpu-baseline --no-alt --no-extras"
+B="--steps 30 --warmup 5 --full --no-cpu-baseline --no-alt --no-extras"
 run_kt() {  # name, bench args
   local name=$1; shift
   timeout -k 10 240 rocprofv3 --kernel-trace --stats -d $OUT/kt_$name -o kt -f csv -- python3 bench.py $B "$@" > $OUT/kt_$name.json 2> $OUT/kt_$name.err || { echo "kt $name failed"; return 1; }
@@ -20,12 +20,12 @@ timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_G
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY -d $OUT/pmc_s -o pmc -f csv -- python3 tools/pmc_cin.py > $OUT/pmc_s.log 2>&1 && python3 tools/pmc_summary.py $OUT/pmc_s cin_ > $OUT/${R}_pmc_cin_waves.txt || exit 1
 echo "== HBM traffic counters over bench.py itself (eager launches)"
 export XDFM_HIP_GRAPH=0
-PB="--steps 3 --warmup 1 --no-cpu-baseline --no-alt --no-extras --vocab-preset mid"
+PB="--steps 3 --warmup 1 --full --no-cpu-baseline --no-alt --no-extras --vocab-preset mid"
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_f -o pmc -f csv -- python3 bench.py $PB > $OUT/pmc_f.log 2>&1 || { echo "FETCH_SIZE pass over bench.py failed / timed out"; exit 1; }
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_w -o pmc -f csv -- python3 bench.py $PB > $OUT/pmc_w.log 2>&1 || { echo "WRITE_SIZE pass over bench.py failed / timed out"; exit 1; }
 python3 tools/pmc_traffic.py $OUT/pmc_f $OUT/pmc_w $OUT/${R}_pmc_bench_traffic.json > $OUT/${R}_pmc_bench_traffic.txt
 echo "== the attention kernels (config 3), the gather / scatter at larger batches, the SFG heads' kernels"
-PB3="--steps 3 --warmup 1 --no-cpu-baseline --no-alt --no-extras --vocab-preset mid --workload criteo_c3_attn"
+PB3="--steps 3 --warmup 1 --full --no-cpu-baseline --no-alt --no-extras --vocab-preset mid --workload criteo_c3_attn"
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_f3 -o pmc -f csv -- python3 bench.py $PB3 > $OUT/pmc_f3.log 2>&1 || { echo "FETCH_SIZE pass (c3) failed"; exit 1; }
 timeout -k 10 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_w3 -o pmc -f csv -- python3 bench.py $PB3 > $OUT/pmc_w3.log 2>&1 || { echo "WRITE_SIZE pass (c3) failed"; exit 1; }
 python3 tools/pmc_traffic.py $OUT/pmc_f3 $OUT/pmc_w3 - > $OUT/${R}_pmc_c3_traffic.txt
