@@ -163,6 +163,9 @@ ATTN_CASES = [
     ("attn_v1_d16",     "v1", 4, 26, 16, (16, 8),    4,     True,  True,  1),
     ("attn_v2_l1",      "v2", 3,  4,  8, (8, 6),     4,     True,  True,  1),
     ("attn_v2_l2",      "v2", 3,  4,  8, (8, 6),     2,     True,  True,  2),
+    ("attn_v1_h1_d16",  "v1", 3,  4, 16, (8, 6),     1,     True,  True,  1),   # one head: the odd-head branches
+    ("attn_v1_d32",     "v1", 3,  4, 32, (8, 6),     4,     True,  True,  1),   # the default 4 heads at D = 32
+    ("attn_v1_s520",    "v1", 2,  2,  8, (1024, 8),  4,     True,  True,  1),   # S = 520: the 1024-thread kernels
 ]
 
 
