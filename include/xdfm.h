@@ -89,7 +89,11 @@ int xdfm_device_count(void);                /* <0: HIP error code negated */
  * dOut planes, run on one XCD (one L2) instead of in launch order; same results, 4.7x fewer bytes fetched at config 2. */
 /* read-only probes (xdfm_get_option): "last_fwd_kernel", "last_bwx_kernel", "last_bww_kernel" = arithmetic of the kernel
  * the last xdfm_cin_level_fwd / _bwd_x / _bwd_w call launched (0 f32mfma, 1 f16x3, 2 bf16; -1 before the first call):
- * a shape without a kernel in the selected mode runs mode 0, and the tests assert which one ran. */
+ * a shape without a kernel in the selected mode runs mode 0, and the tests assert which one ran.
+ * "last_fwd_inst", "last_bwx_inst", "last_bww_inst" = the template instance of that launch, T * 1000 + NW * 100 + NT * 10 + S:
+ * T = row tiles per wave of the forward (MT 2 / 4 / 8), h-blocks per tile of dX (HBT 2 / 4 / 8 / 16), 4 for dW; NW = waves per
+ * workgroup (4 / 8); NT = MFMA terms per product (3 f16x3, 1 bf16); S = 1 for the folded level-0 kernel.  0 when the call ran
+ * the mode-0 kernel, -1 before the first call.  Example: 8831 = forward, MT 8, 8 waves, f16x3, folded level 0. */
 int xdfm_set_option(const char* key, int value);
 int xdfm_get_option(const char* key);
 /* Ticket board: `board` = a DEVICE array of `slots` >= 1040 unsigned ints, zeroed once by the caller and kept alive, registered

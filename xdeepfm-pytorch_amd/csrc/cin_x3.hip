@@ -727,7 +727,9 @@ static int launch_bwx3(const X3DoutSrc& dOut, const float* xp, const float* x0, 
     const size_t lds8 = (size_t)X3_BWX_RING * FR * 1024 + (size_t)2 * NWMAX * m * 32 * sizeof(float);
     const size_t lds4 = (size_t)X3_BWX_RING * FR * 1024 + (size_t)8 * m * 32 * sizeof(float);
     if (lds4 > 160 * 1024) return xdfm_fail(XDFM_ERR_INVALID, "cin_level_bwd_x: m=%d needs %zu B of LDS", m, lds4);
-    if (NWMAX == 8 && xdfm_opt(OPT_X3_WAVES) != 4 && N >= 256 * 64 && lds8 <= 160 * 1024)
+    const bool wide = NWMAX == 8 && xdfm_opt(OPT_X3_WAVES) != 4 && N >= 256 * 64 && lds8 <= 160 * 1024;
+    xdfm_opt_note(OPT_LAST_BWX_INST, x3_inst_code(HBT, wide ? NWMAX : 4, NT, false));
+    if (wide)
         hipLaunchKernelGGL((cin_bwd_x3_kernel<HBT, NWMAX, NT>), dim3(ceil_div(N, 32 * NWMAX)), dim3(64 * NWMAX), lds8, st, dOut, xp,
                            x0, pack, H, Hp, m, N, g.IB, dxp, dx0, flags);
     else

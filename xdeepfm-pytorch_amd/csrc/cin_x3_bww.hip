@@ -894,12 +894,14 @@ int x3_level_bwd_w(const float* dOut, const float* xp, const float* x0, int H, i
     const size_t lds = (size_t)2 * (32 * 4 + NW * (32 + 8)) * 128;
     const int xcd = xdfm_opt(OPT_BWW_XCD) != 0 ? 1 : 0;
     const long hstride = prepared ? w.HS : 0;          // per-split headers, or the one header of the stand-alone passes
-#define BWW_LAUNCH(NWV, NTV) \
+#define BWW_LAUNCH(NWV, NTV) do { \
+    xdfm_opt_note(OPT_LAST_BWW_INST, x3_inst_code(4, NWV, NTV, false)); \
     hipLaunchKernelGGL((cin_bwd_w_x3_kernel<4, NWV, NTV>), dim3(g.gx, g.nsplit), dim3(64 * NWV), lds, st, planes, w.NP * 4, xp, \
-                       x0, hdr, hstride, Hp, m, N, g.IB, g.JP, g.TPH, g.n_per_split, g.Hpad, g.IPAD, slabs, g.slab, xcd)
-#define BWW_LAUNCH_SYM(NWV, NTV) \
+                       x0, hdr, hstride, Hp, m, N, g.IB, g.JP, g.TPH, g.n_per_split, g.Hpad, g.IPAD, slabs, g.slab, xcd); } while (0)
+#define BWW_LAUNCH_SYM(NWV, NTV) do { \
+    xdfm_opt_note(OPT_LAST_BWW_INST, x3_inst_code(4, NWV, NTV, true)); \
     hipLaunchKernelGGL((cin_bwd_w_x3_kernel<4, NWV, NTV, true>), dim3(g.gx, g.nsplit), dim3(64 * NWV), lds, st, planes, w.NP * 4, xp, \
-                       x0, hdr, hstride, Hp, m, N, g.IB, g.JP, g.TPH, g.n_per_split, g.Hpad, g.IPAD, slabs, g.slab, xcd)
+                       x0, hdr, hstride, Hp, m, N, g.IB, g.JP, g.TPH, g.n_per_split, g.Hpad, g.IPAD, slabs, g.slab, xcd); } while (0)
     if (sym) {
         if (NW == 8) { if (nt == 3) BWW_LAUNCH_SYM(8, 3); else BWW_LAUNCH_SYM(8, 1); }
         else { if (nt == 3) BWW_LAUNCH_SYM(4, 3); else BWW_LAUNCH_SYM(4, 1); }

@@ -253,7 +253,9 @@ static int launch_bwx3_sym(const X3DoutSrc& dOut, const float* x0, const float* 
     static_assert(FR % 4 == 0, "a ring stage is dealt to 4 or 8 waves");
     const size_t lds8 = (size_t)X3_BWX_RING * FR * 1024 + (size_t)2 * NWMAX * M * 32 * sizeof(float);
     const size_t lds4 = (size_t)X3_BWX_RING * FR * 1024 + (size_t)8 * M * 32 * sizeof(float);
-    if (NWMAX == 8 && xdfm_opt(OPT_X3_WAVES) != 4 && N >= 256 * 64)
+    const bool wide = NWMAX == 8 && xdfm_opt(OPT_X3_WAVES) != 4 && N >= 256 * 64;
+    xdfm_opt_note(OPT_LAST_BWX_INST, x3_inst_code(HBT, wide ? NWMAX : 4, NT, true));
+    if (wide)
         hipLaunchKernelGGL((cin_bwd_x3_sym_kernel<HBT, NWMAX, NT, M>), dim3(ceil_div(N, 32 * NWMAX)), dim3(64 * NWMAX), lds8, st,
                            dOut, x0, pack, H, N, dxp, dx0, flags);
     else

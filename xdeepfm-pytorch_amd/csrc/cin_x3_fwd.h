@@ -75,7 +75,8 @@ __device__ __forceinline__ void x3_load_dout(float (&raw)[8 * HBT], const X3Dout
     // sign bits of this wave's 32 columns: the chunk's words are contiguous over the rows -- lane L takes rows 4L .. 4L+3
     uint4 wv = make_uint4(~0u, ~0u, ~0u, ~0u);
     if (S.mask) {
-        const long chunk = n0 >> 5;
+        // a wave wholly past the last column (its values are zeroed) reads the last chunk: the mask has ceil(N / 32) of them
+        const long chunk = (n0 < N ? n0 : N - 1) >> 5;
         int r4 = 4 * lane;
         r4 = r4 + 4 <= (int)S.mask_ld - S.h0 ? r4 : 0;                       // rows past the level: any words (their values are zeroed)
         wv = *reinterpret_cast<const uint4*>(S.mask + chunk * S.mask_ld + S.h0 + r4);
@@ -562,10 +563,12 @@ static int launch_x3(const float* xp, const float* x0, const float* pack, const 
                 X3_EXP_CASE(1) X3_EXP_CASE(2) X3_EXP_CASE(3) X3_EXP_CASE(4) X3_EXP_CASE(5) X3_EXP_CASE(6) X3_EXP_CASE(7)
 #undef X3_EXP_CASE
             }
+            xdfm_opt_note(OPT_LAST_FWD_INST, x3_inst_code(MT, NWMAX, NT, SYM));
             hipLaunchKernelGGL((cin_fwd_x3_kernel<MT, M, NWMAX, X3_RING, NT, 0, SYM>), grid, block, ldsx, st, xp, x0, pack, bias, H, Hp, N, g, act, out, epi);
             return xdfm_check_launch("cin_level_fwd (f16x3 / bf16)");
         }
     }
+    xdfm_opt_note(OPT_LAST_FWD_INST, x3_inst_code(MT, 4, NT, SYM));
     const size_t lds4 = RING + 32 * MT * sizeof(float) + (size_t)2 * 8 * 128 * sizeof(float);
     hipLaunchKernelGGL((cin_fwd_x3_kernel<MT, M, 4, X3_RING, NT, 0, SYM>), dim3(ceil_div(N, 128), g.MB), dim3(256), lds4, st, xp, x0, pack,
                        bias, H, Hp, N, g, act, out, epi);

@@ -32,8 +32,13 @@ enum {
     OPT_LAST_SYM,        // read-only probe: bit 0 / 1 / 2 = the last f16x3 / bf16 forward / dX / dW launch ran the folded level-0 kernel
     OPT_X3_SYM,          // 1 (default) = level 0 (x_prev is x0) contracts over the pairs i <= j with folded weights; 0 = full (i, j) grid
     OPT_BWW_XCD,         // 1 (default) = the f16x3 / bf16 dW kernel keeps the workgroups of an n-split on one XCD; 0 = launch order
+    OPT_LAST_FWD_INST,   // read-only probes: template instance of the last f16x3 / bf16 forward / dX / dW launch (x3_inst_code),
+    OPT_LAST_BWX_INST,   //   0 when the call ran the fp32-MFMA kernel, -1 before the first call
+    OPT_LAST_BWW_INST,
     OPT_COUNT
 };
+// value of the instance probes: row tiles (forward MT, dX HBT, dW MT) * 1000 + waves * 100 + MFMA terms * 10 + folded level 0
+static inline int x3_inst_code(int T, int NW, int NT, bool SYM) { return T * 1000 + NW * 100 + NT * 10 + (SYM ? 1 : 0); }
 
 // Ticket board (api.hip, xdfm_set_ticket_board): a small zeroed device array the host registers once per device.  A kernel
 // that leaves per-block partials takes a ticket when a block is done; the block that draws the last one sums the
