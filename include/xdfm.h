@@ -38,6 +38,8 @@
  * xdfm_cin_level_bwd_w_prepared (dOut, its fp16 planes and the dW kernel's scales in one pass); xdfm_set_ticket_board;
  * xdfm_cin_attn_pool_bwd_det (K5's parameter gradients without float atomics); xdfm_cin_level_fwd_ex (direct-connect sums
  * and ReLU sign bits from the forward's epilogue; the direct-connect half of a level is never stored).
+ * ABI 8 additions (no existing struct or signature changed): xdfm_opt_tensor, xdfm_opt_step_ws_elems, xdfm_sgd_step,
+ * xdfm_adagrad_step (K7s / K7g: the streaming sweep for the trainer's two other optimizers).
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -415,6 +417,34 @@ int xdfm_adam_step(const xdfm_adam_tensor* tensors, int T, double lr, double bet
  * instead of being captured again for every value. */
 int xdfm_adam_step_lr(const xdfm_adam_tensor* tensors, int T, double lr, const double* lr_dev, double beta1, double beta2,
                       double eps, float* l2_ws, float* l2_value, void* stream);
+
+/* ------------------------------------------------------------------ SGD and Adagrad (K7s, K7g)
+ * replaces: torch.optim.SGD(lr=0.01).step() and torch.optim.Adagrad().step() (deepctr/models/basemodel.py:447-461,
+ * the trainer's --optimizer sgd|adagrad) with K7's streaming sweep: 8 bytes per parameter (SGD: p read + written) or
+ * 16 (Adagrad: p and the accumulator `state`), in fp32 and in ATen's order:
+ *   g' = fma(2 l2, p, g);   SGD: p = fma(-lr, g', p);   Adagrad: s = s + g' g', p = fma(-lr, g' / (sqrt(s) + eps), p)
+ * (momentum 0, lr_decay 0, no weight decay; IEEE sqrt and division).  Descriptors, `lr` / `lr_dev`, `l2`, `l2_ws`
+ * (xdfm_opt_step_ws_elems(T) floats) and `l2_value` (sum_t l2_t * sum(w_t^2) of the weights BEFORE the update) are
+ * K7's; so is `grad_marks` (see xdfm_adam_tensor: unmarked chunks are zeros and not read, marked ones are read,
+ * re-zeroed and unmarked, the numel % 4 tail is always read and zeroed; needs 16-byte aligned param / grad / state),
+ * with one exact shortcut: an unmarked chunk of a tensor with l2 == 0 has g' == 0, which changes neither p nor s, so it
+ * is skipped without reading them -- such a tensor costs one mark byte per 16 bytes of gradient.  With l2 > 0 an
+ * unmarked chunk is a real update and is computed as a marked one with g = 0: marks on / off give the same bits.
+ * Tensors whose pointers are not 16-byte aligned take a scalar path.  Errors (NULL `tensors`, T <= 0, Adagrad without
+ * `state`, eps <= 0) are reported before any device work. */
+typedef struct {
+    float* param;
+    float* grad;
+    float* state;                   /* Adagrad: the accumulator ("sum"); SGD: NULL */
+    long numel;
+    float l2;
+    unsigned char* grad_marks;      /* NULL: grad is read in full and left alone */
+} xdfm_opt_tensor;
+size_t xdfm_opt_step_ws_elems(int T);
+int xdfm_sgd_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, float* l2_ws, float* l2_value,
+                  void* stream);
+int xdfm_adagrad_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps, float* l2_ws,
+                      float* l2_value, void* stream);
 
 /* ------------------------------------------------------------------ deferred Adam for the tables (K7d)
  * Same arithmetic, same results, bit for bit, as the dense sweep above -- but the sweep's 24 bytes per table parameter

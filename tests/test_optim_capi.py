@@ -1,0 +1,103 @@
+"""CPU: the SGD / Adagrad entry points (K7s / K7g) are declared, bound and exported, validate their arguments before any
+device work, and the host classes keep the stock classes' layout and the reference's defaults (no compute)."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+from conftest import ROOT
+
+NEW = ("xdfm_opt_step_ws_elems", "xdfm_sgd_step", "xdfm_adagrad_step")
+
+
+def test_new_symbols_are_declared_bound_and_exported():
+    from xdfm_amd import _lib
+    lib = _lib.load()
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xdfm.h")).read(), flags=re.S)
+    for name in NEW:
+        assert re.search(r"\b%s\s*\(" % name, header), "include/xdfm.h lacks %s" % name
+        assert name in _lib.SIGNATURES and hasattr(lib, name)
+    assert "xdfm_opt_tensor" in header
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8          # additions only
+    # the descriptor as the header lays it out: three pointers, a long, a float (padded), a pointer
+    assert ctypes.sizeof(_lib.OptTensor) == 48
+    assert [f[0] for f in _lib.OptTensor._fields_] == ["param", "grad", "state", "numel", "l2", "grad_marks"]
+    assert lib.xdfm_opt_step_ws_elems(0) == 0 and lib.xdfm_opt_step_ws_elems(3) >= 3
+
+
+def test_bad_arguments_are_refused_before_any_device_work():
+    from xdfm_amd import _lib
+    lib = _lib.load()
+    one = (_lib.OptTensor * 1)()
+    arr = ctypes.cast(one, ctypes.c_void_p)
+
+    def refused(rc, text):
+        msg = lib.xdfm_last_error()
+        assert rc == 1 and text in msg, (rc, msg)
+        with pytest.raises(ValueError):
+            _lib.check(rc, "opt_step")
+
+    refused(lib.xdfm_sgd_step(None, 1, 0.01, None, None, None, None), b"null pointer")
+    refused(lib.xdfm_adagrad_step(None, 1, 0.01, None, 1e-10, None, None, None), b"null pointer")
+    refused(lib.xdfm_sgd_step(arr, 0, 0.01, None, None, None, None), b"bad tensor count")
+    refused(lib.xdfm_adagrad_step(arr, -2, 0.01, None, 1e-10, None, None, None), b"bad tensor count")
+    refused(lib.xdfm_adagrad_step(arr, 1, 0.01, None, 0.0, None, None, None), b"bad hyper-parameters")      # eps <= 0
+    refused(lib.xdfm_sgd_step(arr, 1, 0.01, None, None, None, None), b"null pointer")                       # param / grad NULL
+    # Adagrad without the accumulator: host addresses stand in for device ones, nothing is dereferenced
+    buf = (ctypes.c_float * 8)()
+    one[0].param = one[0].grad = ctypes.addressof(buf)
+    one[0].numel = 8
+    refused(lib.xdfm_adagrad_step(arr, 1, 0.01, None, 1e-10, None, None, None), b"no state")
+    refused(lib.xdfm_sgd_step(arr, 1, 0.01, None, None, ctypes.c_void_p(ctypes.addressof(buf)), None), b"l2_value needs l2_ws")
+
+
+def test_table_optimizers_keep_the_stock_layout_and_the_reference_defaults():
+    from xdfm_amd.optim import TableAdagrad, TableAdam, TableSGD
+    ps = [torch.nn.Parameter(torch.randn(5, 3)), torch.nn.Parameter(torch.randn(4))]
+    sgd, ada = TableSGD(ps), TableAdagrad(ps)
+    assert isinstance(sgd, torch.optim.SGD) and isinstance(ada, torch.optim.Adagrad)
+    assert issubclass(TableSGD, torch.optim.SGD) and issubclass(TableAdagrad, torch.optim.Adagrad)
+    g = sgd.param_groups[0]
+    assert g["lr"] == 0.01 and g["momentum"] == 0 and g["weight_decay"] == 0 and not g["nesterov"]
+    g = ada.param_groups[0]
+    assert g["lr"] == 0.01 and g["eps"] == 1e-10 and g["lr_decay"] == 0 and g["initial_accumulator_value"] == 0
+    for opt in (sgd, ada, TableAdam(ps)):
+        assert opt.table_step and opt.generation == 0 and opt.l2_value is None and opt.owns(ps)
+        assert not opt.owns([torch.nn.Parameter(torch.zeros(1))])
+    assert sorted(ada.state[ps[0]].keys()) == ["step", "sum"] and not ada.state[ps[0]]["step"].is_cuda
+    # CPU parameters: the stock update (with an armed L2 term applied by hand), bit for bit
+    qs = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    for mine, stock in ((TableSGD(ps), torch.optim.SGD(qs, lr=0.01)), (TableAdagrad(ps), torch.optim.Adagrad(qs))):
+        for step in range(3):
+            for p, q in zip(ps, qs):
+                p.grad = torch.full_like(p, 0.5 + step)
+                q.grad = p.grad.clone()
+            if step == 1:
+                mine.arm_l2(ps[:1], [0.25])
+                want = 0.25 * float(qs[0].detach().square().sum())
+                qs[0].grad.add_(qs[0].detach(), alpha=0.5)
+            mine.step()
+            stock.step()
+            assert (mine.l2_value is None) == (step != 1)
+            if step == 1:
+                assert abs(float(mine.l2_value) - want) <= 1e-6 * want
+        for p, q in zip(ps, qs):
+            assert torch.equal(p, q)
+        gen = mine.generation
+        stock.load_state_dict(mine.state_dict())             # interchangeable state
+        mine.load_state_dict(stock.state_dict())
+        assert mine.generation > gen                         # captured graphs that baked the old state are stale
+    assert float(ada.state[ps[0]]["step"]) == 0.0 and float(mine.state[ps[0]]["step"]) == 3.0
+
+
+def test_cpu_model_compiles_the_stock_classes():
+    from deepctr.inputs import DenseFeat, SparseFeat
+    from deepctr.models import xDeepFM
+    cols = [SparseFeat("C1", 7, 4), SparseFeat("C2", 5, 4), DenseFeat("I1", 1)]
+    model = xDeepFM(cols, cols, dnn_hidden_units=(8,), cin_layer_size=(6, 4), device="cpu")
+    for name, cls, lr in (("sgd", torch.optim.SGD, 0.01), ("adagrad", torch.optim.Adagrad, 0.01)):
+        model.compile(name, "binary_crossentropy")
+        assert type(model.optim) is cls and model.optim.param_groups[0]["lr"] == lr
+        assert not model._optim_capturable and model._l2_fusion() is None

@@ -76,6 +76,9 @@ SIGNATURES = {
     "xdfm_adam_apply_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, c_double, c_double, P, P, P]),
     "xdfm_adam_flush": (c_int, [P, c_int, P, c_double, c_double, c_double, P, P]),
     "xdfm_adam_selftest": (c_int, [c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_double, c_double, c_double, c_double, P, P]),
+    "xdfm_opt_step_ws_elems": (c_size_t, [c_int]),
+    "xdfm_sgd_step": (c_int, [P, c_int, c_double, P, P, P, P]),
+    "xdfm_adagrad_step": (c_int, [P, c_int, c_double, P, c_double, P, P, P]),
     "xdfm_vocab_lse_update": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_softmax_grad": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_ce_x3_supported": (c_int, [c_int]),
@@ -104,6 +107,12 @@ class AdamTensor(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
                 ("step", c_void_p), ("numel", c_long), ("l2", ctypes.c_float), ("grad_marks", c_void_p), ("flags", c_int),
                 ("last", c_void_p)]
+
+
+class OptTensor(ctypes.Structure):
+    """xdfm_opt_tensor of include/xdfm.h (SGD / Adagrad; `state` is Adagrad's accumulator)"""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("state", c_void_p), ("numel", c_long), ("l2", ctypes.c_float),
+                ("grad_marks", c_void_p)]
 
 
 class AdamClock(ctypes.Structure):

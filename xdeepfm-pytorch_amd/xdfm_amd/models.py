@@ -311,10 +311,10 @@ class BaseModel(nn.Module):
 
     def _l2_fusion(self):
         """(tensors, strengths) of the whole L2 term when the optimizer applies it itself while it streams the
-        weights (xdfm_amd.optim.TableAdam, K7), else None.  Only the model's own train step uses this."""
-        from .optim import TableAdam
+        weights (xdfm_amd.optim.TableAdam / TableSGD / TableAdagrad: K7, K7s, K7g), else None.  Only the model's own
+        train step uses this."""
         opt = getattr(self, "optim", None)
-        if not isinstance(opt, TableAdam):
+        if not getattr(opt, "table_step", False):
             return None
         tensors, coeffs = [], []
         for weight_list, l1, l2 in self.regularization_weight:
@@ -414,8 +414,7 @@ class BaseModel(nn.Module):
         model's OWN train step only (`_own_step`): there nothing touches a gradient between the scatter and K7.  A
         user-driven loop (model(x); loss.backward(); edit .grad; optim.step()) gets ordinary dense gradients, because
         K7 would not see what such code adds outside the marked chunks."""
-        from .optim import TableAdam
-        plan.arena_on = bool(self.__dict__.get("_own_step")) and isinstance(getattr(self, "optim", None), TableAdam)
+        plan.arena_on = bool(self.__dict__.get("_own_step")) and bool(getattr(getattr(self, "optim", None), "table_step", False))
         if plan.arena_on and plan not in self.optim.grad_sources:
             self.optim.grad_sources.append(plan)
 
@@ -550,8 +549,9 @@ class BaseModel(nn.Module):
         self._optim_capturable = False
         self._flush_optim()                # a previous optimizer may still owe table rows their latest steps
         self.optim = self._get_optim(optimizer)
-        from .optim import TableAdam
-        if isinstance(self.optim, TableAdam):          # also when handed in as an object, e.g. TableAdam(..., lazy_rows=True)
+        # the table optimizers (optim.TableAdam / TableSGD / TableAdagrad), also when handed in as an object, e.g.
+        # TableAdam(..., lazy_rows=True); an object of a stock torch class keeps the stock path
+        if getattr(self.optim, "table_step", False):
             self._optim_capturable = all(p.is_cuda for g in self.optim.param_groups for p in g["params"])
         self.loss_func = self._get_loss_func(loss)
         self.metrics = self._get_metrics(metrics)
@@ -569,8 +569,17 @@ class BaseModel(nn.Module):
                 from .optim import TableAdam
                 return TableAdam(params)
             return torch.optim.Adam(params)
-        table = {"sgd": lambda p: torch.optim.SGD(p, lr=0.01), "adam": adam,
-                 "adagrad": torch.optim.Adagrad, "rmsprop": torch.optim.RMSprop}
+        def native(table_cls, stock):
+            # SGD / Adagrad through K7s / K7g on a GPU (xdfm_amd.optim); on the CPU the stock class, as the reference
+            def make(params):
+                params = list(params)
+                if len(params) > 0 and all(p.is_cuda for p in params):
+                    from . import optim
+                    return getattr(optim, table_cls)(params)
+                return stock(params)
+            return make
+        table = {"sgd": native("TableSGD", lambda p: torch.optim.SGD(p, lr=0.01)), "adam": adam,
+                 "adagrad": native("TableAdagrad", torch.optim.Adagrad), "rmsprop": torch.optim.RMSprop}
         if optimizer not in table:
             raise NotImplementedError
         return table[optimizer](self.parameters())

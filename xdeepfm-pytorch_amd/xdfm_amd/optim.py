@@ -12,7 +12,11 @@ while it streams the weights and returns the term's value (`l2_value`), which re
 passes over the parameters (basemodel.py:412-428) from the step.
 
 Gradients that are views of a kept gradient buffer (`ops.GradArena`, registered through `grad_sources`) are read by
-their chunk marks: K7 skips the untouched rows of the dense table gradients and re-zeroes the touched ones."""
+their chunk marks: K7 skips the untouched rows of the dense table gradients and re-zeroes the touched ones.
+
+`TableSGD` and `TableAdagrad` (K7s / K7g, `xdfm_sgd_step` / `xdfm_adagrad_step`) give the trainer's two other optimizers
+(`--optimizer sgd|adagrad`, basemodel.py:447-461) the same sweep, armed L2 term, marked gradients and device-resident
+learning rate; their state layout is that of torch.optim.SGD / torch.optim.Adagrad."""
 import ctypes
 import os
 
@@ -26,6 +30,8 @@ ROWS_MIN_NUMEL = 1 << 20  # tables at least this large get the step's update by 
 
 
 class TableAdam(torch.optim.Adam):
+    table_step = True            # the model's train step may arm the L2 term and hand over marked gradients (models.py)
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, lazy_rows=False, deferred=None, flush_every=64):
         super().__init__(params, lr=lr, betas=betas, eps=eps, fused=True, capturable=True)
         # Deferred (exact) update of the tables, include/xdfm.h "K7d": same bits as the dense sweep, but a row is brought
@@ -461,3 +467,245 @@ class TableAdam(torch.optim.Adam):
             if val is not None:
                 self.l2_value = val if self.l2_value is None else self.l2_value + val
         return None
+
+
+class _TableStep(object):
+    """What `TableSGD` and `TableAdagrad` share, and what the model's train step duck-types on (`table_step`): `arm_l2`,
+    `owns`, `l2_value`, `grad_sources`, `sync_lr`, `generation`, `note_replay`.  A mixin in front of the stock class;
+    TableAdam keeps its own copies (its deferred update threads through all of them)."""
+    table_step = True
+    _KERNEL = None               # "sgd" / "adagrad"
+
+    def _table_init(self):
+        self._armed = None          # id(parameter) -> L2 strength, for the next step only
+        self._desc = {}             # group index -> (key, ctypes array of xdfm_opt_tensor)
+        self.l2_value = None        # [1] device tensor: value of the armed L2 term at the last step
+        self.grad_sources = []      # objects with .arenas() -> [ops.GradArena]: gradients the kernel may read by their marks
+        self._lr_dev = {}           # group index -> [host value, [1] float64 device tensor the kernel reads the rate from]
+        self._replay_steps = None   # host step counters a captured step advances (its Python does not run on replay)
+        self.generation = 0         # bumped whenever state tensors may have been replaced (part of the graph key)
+
+    # The kernels take the learning rate from device memory, so a captured train step follows `param_groups[i]["lr"]`
+    # edits without a new capture; the scalar is rewritten OUTSIDE any capture (GraphedStep calls this before a replay).
+    def sync_lr(self):
+        for gi, group in enumerate(self.param_groups):
+            lr = group["lr"]
+            if not isinstance(lr, float) or not group["params"]:
+                continue
+            hit = self._lr_dev.get(gi)
+            dev = group["params"][0].device
+            if hit is None or hit[1].device != dev:
+                if dev.type != "cuda" or torch.cuda.is_current_stream_capturing():
+                    continue
+                hit = self._lr_dev[gi] = [None, torch.empty(1, dtype=torch.float64, device=dev)]
+            if hit[0] != lr:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("xdfm %s: learning rate changed inside a HIP-graph capture" % type(self).__name__)
+                hit[1].fill_(lr)
+                hit[0] = lr
+
+    def _invalidate(self):
+        """State tensors may have been replaced: forget the cached descriptors and make every captured graph that baked
+        their addresses stale (graphstep._signature hashes `generation`)."""
+        self._desc = {}
+        self._lr_dev = {}
+        self._replay_steps = None
+        self.generation += 1
+
+    def load_state_dict(self, state_dict):
+        out = super().load_state_dict(state_dict)
+        self._invalidate()
+        return out
+
+    def add_param_group(self, param_group):
+        out = super().add_param_group(param_group)
+        if hasattr(self, "_desc"):              # the base constructor comes here before _table_init
+            self._invalidate()
+        return out
+
+    def __getstate__(self):
+        state = dict(super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__)
+        for k in ("_desc", "_lr_dev"):          # ctypes descriptors / device scalars: rebuilt on use
+            state[k] = {}
+        for k in ("_armed", "l2_value", "_replay_steps"):
+            state[k] = None
+        state["grad_sources"] = []
+        state["generation"] = self.generation
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        gen = self.__dict__.get("generation", 0)
+        for k in ("_desc", "_lr_dev"):
+            self.__dict__.setdefault(k, {})
+        for k in ("_armed", "l2_value", "_replay_steps"):
+            self.__dict__.setdefault(k, None)
+        self.__dict__.setdefault("grad_sources", [])
+        self.generation = gen + 1
+
+    def owns(self, tensors):
+        mine = {id(p) for g in self.param_groups for p in g["params"]}
+        return all(id(t) in mine for t in tensors)
+
+    def arm_l2(self, tensors, coeffs):
+        """The next step() adds the gradient of sum_t coeffs[t] * sum(tensors[t]^2) itself and reports its value."""
+        self._armed = {}
+        for t, c in zip(tensors, coeffs):
+            self._armed[id(t)] = self._armed.get(id(t), 0.0) + float(c)
+
+    def note_replay(self):
+        """Called before a captured step is replayed: the host-side step counters (Adagrad) still count it."""
+        if self._replay_steps:
+            torch._foreach_add_(self._replay_steps, 1)
+
+    def _l2_by_hand(self, armed):
+        """Fallback path: apply the armed term with ATen ops before torch's own step."""
+        value = None
+        for group in self.param_groups:
+            for p in group["params"]:
+                c = armed.get(id(p), 0.0)
+                if c and p.grad is not None:
+                    p.grad.add_(p.detach(), alpha=2.0 * c)
+                    term = c * p.detach().square().sum()
+                    value = term if value is None else value + term
+        self.l2_value = None if value is None else value.reshape(1)
+
+    def _plain(self, group):                    # hyper-parameters the kernel implements
+        raise NotImplementedError
+
+    def _state_of(self, group, p):              # (accumulator or None, host step counter or None)
+        raise NotImplementedError
+
+    def _native(self):
+        """True when every group can take the kernel: plain hyper-parameters, dense contiguous fp32 CUDA tensors."""
+        if getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
+            return False
+        for group in self.param_groups:
+            if not self._plain(group) or not isinstance(group["lr"], float) or group["maximize"] or \
+                    group["differentiable"] or group["weight_decay"] != 0:
+                return False
+            for p in group["params"]:
+                g = p.grad
+                if g is None:
+                    continue
+                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and not g.is_sparse and
+                        g.dtype == torch.float32 and g.is_contiguous() and g.device == p.device):
+                    return False
+        return True
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        armed, self._armed = self._armed, None
+        self.l2_value = None
+        if closure is not None or not self._native():
+            if armed:
+                self._l2_by_hand(armed)
+            return super().step(closure)
+        self.sync_lr()
+        lib = _lib.load()
+        from . import ops                              # per-kernel timing hook of bench.py
+        ada = self._KERNEL == "adagrad"
+        capturing = torch.cuda.is_current_stream_capturing()
+        host_steps = []
+        for gi, group in enumerate(self.param_groups):
+            params = [p for p in group["params"] if p.grad is not None]
+            if not params:
+                continue
+            grads = [p.grad for p in params]
+            states = [self._state_of(group, p) for p in params]
+            host_steps += [st[1] for st in states if st[1] is not None]
+            T = len(params)
+            l2 = tuple(armed.get(id(p), 0.0) for p in params) if armed else None
+            key = (tuple(p.data_ptr() for p in params), tuple(st[0].data_ptr() for st in states if st[0] is not None), l2)
+            hit = self._desc.get(gi)
+            if hit is None or hit[0] != key:
+                arr = (_lib.OptTensor * T)()
+                for k in range(T):
+                    arr[k].param, arr[k].numel = params[k].data_ptr(), params[k].numel()
+                    arr[k].state = states[k][0].data_ptr() if states[k][0] is not None else None
+                    arr[k].l2 = l2[k] if l2 is not None else 0.0
+                hit = self._desc[gi] = (key, arr)
+            arr = hit[1]
+            arenas = [a for src in self.grad_sources for a in src.arenas() if a.pending]
+            nbytes = 0.0
+            for k in range(T):
+                gp = grads[k].data_ptr()
+                arr[k].grad, arr[k].grad_marks = gp, None
+                for a in arenas:                       # a view of a kept gradient buffer: read it by its marks
+                    mp = a.marks_ptr(gp)
+                    if mp is not None and params[k].data_ptr() % 16 == 0 and (arr[k].state or 0) % 16 == 0:
+                        arr[k].grad_marks = mp
+                        a.consumed(gp)
+                        break
+                per = 16.0 if ada else 8.0             # the byte model of DESIGN.md (K7s / K7g)
+                if arr[k].grad_marks:
+                    nbytes += params[k].numel() * (0.0625 if arr[k].l2 == 0.0 else per + 0.0625)
+                else:
+                    nbytes += params[k].numel() * (per + 4.0)
+            dev = params[0].device
+            ws = val = None
+            if l2 is not None and any(l2):
+                ws = torch.empty(lib.xdfm_opt_step_ws_elems(T), dtype=torch.float32, device=dev)
+                val = torch.empty(1, dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            lr_dev = self._lr_dev.get(gi)
+            lr_ptr = lr_dev[1].data_ptr() if lr_dev is not None else None
+            ws_ptr, val_ptr = (ws.data_ptr(), val.data_ptr()) if val is not None else (None, None)
+            if ada:
+                launch = lambda: lib.xdfm_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
+                                                       float(group["eps"]), ws_ptr, val_ptr, stream)
+            else:
+                launch = lambda: lib.xdfm_sgd_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
+                                                   ws_ptr, val_ptr, stream)
+            _lib.check(ops._run("%s_step[bytes]" % self._KERNEL, nbytes, launch), "%s_step" % self._KERNEL)
+            if val is not None:
+                self.l2_value = val if self.l2_value is None else self.l2_value + val
+        if host_steps:
+            if capturing:
+                self._replay_steps = host_steps        # nothing runs during a capture: every replay counts (note_replay)
+            else:
+                torch._foreach_add_(host_steps, 1)
+        return None
+
+
+class TableSGD(_TableStep, torch.optim.SGD):
+    """torch.optim.SGD whose step is K7s (`xdfm_sgd_step`) for momentum 0 (the reference's `compile("sgd")`, lr 0.01).
+    Momentum, dampening, nesterov, weight decay, maximize, tensor learning rates, sparse / non-fp32 / non-CUDA tensors and
+    closures fall back to torch.optim.SGD.step with the armed L2 term applied by hand."""
+    _KERNEL = "sgd"
+
+    def __init__(self, params, lr=0.01, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False):
+        super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                         nesterov=nesterov, maximize=maximize)
+        self._table_init()
+
+    def _plain(self, group):
+        return group["momentum"] == 0 and group["dampening"] == 0 and not group["nesterov"]
+
+    def _state_of(self, group, p):
+        return None, None
+
+
+class TableAdagrad(_TableStep, torch.optim.Adagrad):
+    """torch.optim.Adagrad whose step is K7g (`xdfm_adagrad_step`) for lr_decay 0 (the reference's `compile("adagrad")`:
+    lr 0.01, eps 1e-10).  State is torch's: `sum` per parameter and a host-resident `step` counter, which the update does
+    not read but which still counts every step, replayed ones included (`note_replay`).  A non-zero
+    `initial_accumulator_value` is only an initial state.  lr_decay, weight decay, maximize, tensor learning rates,
+    sparse / non-fp32 / non-CUDA tensors and closures fall back to torch.optim.Adagrad.step."""
+    _KERNEL = "adagrad"
+
+    def __init__(self, params, lr=0.01, lr_decay=0, weight_decay=0, initial_accumulator_value=0, eps=1e-10, *,
+                 maximize=False):
+        super().__init__(params, lr=lr, lr_decay=lr_decay, weight_decay=weight_decay,
+                         initial_accumulator_value=initial_accumulator_value, eps=eps, maximize=maximize)
+        self._table_init()
+
+    def _plain(self, group):
+        return group["lr_decay"] == 0 and group["eps"] > 0 and not group.get("fused")
+
+    def _state_of(self, group, p):
+        st = self.state[p]
+        acc = st["sum"]
+        if not (acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous()):
+            raise RuntimeError("xdfm TableAdagrad: the accumulator of a CUDA parameter must be a contiguous fp32 CUDA tensor")
+        return acc, st["step"]
