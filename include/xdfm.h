@@ -39,7 +39,8 @@
  * xdfm_cin_attn_pool_bwd_det (K5's parameter gradients without float atomics); xdfm_cin_level_fwd_ex (direct-connect sums
  * and ReLU sign bits from the forward's epilogue; the direct-connect half of a level is never stored).
  * ABI 8 additions (no existing struct or signature changed): xdfm_opt_tensor, xdfm_opt_step_ws_elems, xdfm_sgd_step,
- * xdfm_adagrad_step (K7s / K7g: the streaming sweep for the trainer's two other optimizers).
+ * xdfm_adagrad_step (K7s / K7g: the streaming sweep for the trainer's two other optimizers); xdfm_opt_clock, xdfm_opt_rows,
+ * xdfm_sgd_step_deferred, xdfm_adagrad_step_deferred, xdfm_opt_catchup_rows, xdfm_opt_flush (K7sd / K7gd: their deferred form).
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -498,6 +499,57 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
  * clock[0] = 0, every `last` byte 0). */
 int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double beta1, double beta2,
                     double eps, float* backlog, void* stream);
+
+/* ------------------------------------------------------------------ deferred SGD / Adagrad for the tables (K7sd, K7gd)
+ * K7d's scheme for K7s / K7g, same bits as their sweep.  With l2 > 0 a row no batch touches still sees the gradient
+ * 2*l2*w, so the sweep updates every table parameter every step; such a row evolves by a recurrence in its own state and
+ * the step's rate only -- SGD: p = fma(-lr_t, 2 l2 p, p); Adagrad: g' = 2 l2 p, s = s + g' g', p = fma(-lr_t, g' /
+ * (sqrt(s) + eps), p) -- and the kernels below replay the steps a chunk missed in registers, through the sweep's own
+ * element update (csrc/opt_math.h: one definition, IEEE sqrt and division), when the chunk is needed: before a batch
+ * gathers it (xdfm_opt_catchup_rows), when a gradient arrives for it (the step) and every F steps for all chunks
+ * (xdfm_opt_flush).  8 / 16 bytes per table parameter move once per F steps instead of once per step.
+ * clock: device int[2] = {steps since the last flush, steps before it}; rates: device float[cap], per step since the last
+ * flush the -(float)lr that step used (from lr_dev when given), written by the step itself: a replayed HIP graph follows
+ * a learning-rate schedule.  backlog: one 64-bit device cell, zeroed once by the caller; the L2 value of every replayed
+ * step (of the weights before that update) is ADDED to it in 2^-40 fixed point (integer adds: order-independent).  cell:
+ * 64-bit device scratch of the step, zero between calls.  Both 8-byte aligned. */
+typedef struct {
+    int* clock;
+    float* rates;
+    int cap;            /* steps the table holds: flush before clock[0] reaches it */
+    unsigned long long* backlog;
+    unsigned long long* cell;
+} xdfm_opt_clock;
+/* xdfm_sgd_step / xdfm_adagrad_step with a clock: advance it, record the step's rate.  last: host array [T]; last[t] ==
+ * NULL: tensor t is stepped as xdfm_sgd_step / xdfm_adagrad_step step it.  Otherwise tensor t is deferred (needs l2 > 0 and
+ * grad_marks; last[t]: device bytes, at least numel / 4 + 4 of them, 4-byte aligned, zero at the start and after a flush = the
+ * step since the last flush up to which the chunk is updated): only its mark bytes are read, 16 per load; a marked chunk
+ * replays the steps it still misses with g = 0, takes this step with its gradient, gets zeros written back to the
+ * gradient, its mark cleared and last = clock[0].  The numel % 4 tail elements are updated every step.  l2_value: the
+ * term's value for the chunks this step touched plus the tensors without `last`.  Errors (NULL descriptors, T <= 0, a bad
+ * clock, cap <= 2 (hence cap <= 0), a deferred tensor without grad_marks or with l2 == 0, Adagrad without state, eps <= 0) are reported
+ * before any device work. */
+int xdfm_sgd_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
+                           double lr, const double* lr_dev, float* l2_ws, float* l2_value, void* stream);
+int xdfm_adagrad_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
+                               double lr, const double* lr_dev, double eps, float* l2_ws, float* l2_value, void* stream);
+/* Device-side tables of one gather's fields; param[f] == NULL: field f is not deferred. */
+typedef struct {
+    float* const* param;            /* device array [m] */
+    float* const* state;            /* Adagrad: the accumulators; SGD: NULL */
+    unsigned char* const* last;
+    const float* l2;                /* device array [m] */
+} xdfm_opt_rows;
+/* Brings the rows a batch is about to gather (X, cols, vocab as in xdfm_embed_gather_fwd; lin may be NULL) up to the
+ * clock: one thread per (example, field, 16-byte chunk of the row), the first to reach a chunk claims it by an integer
+ * compare-and-swap on the word of its `last` byte.  adagrad: 0 = SGD (eps unused), 1 = Adagrad. */
+int xdfm_opt_catchup_rows(int adagrad, const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
+                          const xdfm_opt_rows* emb, const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps,
+                          void* stream);
+/* Brings every chunk of the tensors (all deferred: last[t] != NULL) up to the clock, then resets it (clock[1] += clock[0],
+ * clock[0] = 0, every `last` byte 0). */
+int xdfm_opt_flush(int adagrad, const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
+                   double eps, void* stream);
 
 /* Test hook: compares the replay's short forms (csrc/adam_math.h) with the reference spellings ON THE DEVICE.
  * mode 0: square root, n = 2^32 bit patterns; 1: division by a step's constant, n = steps * 2^24 numerators; 2: general

@@ -9,7 +9,13 @@ synchronise, after a warm-up that goes past the graph capture.  Prints one table
 ms/step of both paths, their ratio, the sweep kernel's bytes per second by the byte model of DESIGN.md (K7s / K7g),
 and launches per step (graph nodes for the replayed step; kernels seen by torch.profiler for the eager one).
 
-    python tools/optim_probe.py [--steps 200] [--vocab mid,criteo-card] [--optimizers sgd,adagrad] [--out FILE.json]
+A third arm, `deferred`, is the native step with the deferred (exact) table update (K7sd / K7gd, `deferred=True`) beside
+the native sweep (`deferred=False`).  Its timed blocks end with a flush inside the timed region, and a block is longer than
+the flush period, so every deferred update is paid for inside the time reported.  For that arm the tool also prints the
+flush (ms per flush, and amortised over the period) and the catch-up launch (us), from HIP events around them.
+
+    python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad] [--arms sweep,deferred,stock]
+                                [--out FILE.json]
 """
 import argparse
 import json
@@ -26,7 +32,7 @@ import torch                                     # noqa: E402
 import bench                                     # noqa: E402
 
 
-def build(cfg, vocab, dev, optimizer, stock):
+def build(cfg, vocab, dev, optimizer, stock, deferred=False):
     from deepctr.inputs import DenseFeat, SparseFeat
     from deepctr.models import xDeepFM
     cols = [SparseFeat("C%d" % (i + 1), v, cfg["emb_dim"]) for i, v in enumerate(vocab)]
@@ -37,6 +43,7 @@ def build(cfg, vocab, dev, optimizer, stock):
         model.compile(opt, "binary_crossentropy", metrics=[])
     else:
         model.compile(optimizer, "binary_crossentropy", metrics=[])
+        model.optim.deferred = bool(deferred)
     for pg in model.optim.param_groups:          # a rate at which a sum-reduced loss over 4096 rows stays finite
         pg["lr"] = 1e-5 if optimizer == "sgd" else 1e-3
     model.train()
@@ -49,7 +56,41 @@ def timed(model, batches, steps, k0):
         xb, yb = batches[(k0 + k) % len(batches)]
         model.train_on_batch(xb, yb)
         torch.cuda.synchronize()
+    if hasattr(model.optim, "flush"):            # deferred arm: what the block still owes is paid inside it
+        model.optim.flush()
+        torch.cuda.synchronize()
     return time.perf_counter() - t0
+
+
+def deferred_parts(model, batches, reps=3):
+    """(ms per flush after a full period of steps, us per catch-up launch) of a model on the deferred path, by HIP events."""
+    opt = model.optim
+    plan = model._gather_plan()
+    flush_ms, catch_us = [], []
+    k = 0
+    for _ in range(reps):
+        opt.flush()
+        while opt._since < opt.flush_every:
+            model.train_on_batch(*batches[k % len(batches)])
+            k += 1
+            if opt._since == opt.flush_every // 2:          # rows of a fresh batch, half a period behind
+                X, emb, lin = plan.last_gather
+                Xn = batches[(k + 3) % len(batches)][0]
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                opt._catchup(plan, Xn, emb, lin)
+                e1.record()
+                torch.cuda.synchronize()
+                catch_us.append(e0.elapsed_time(e1) * 1e3)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        opt.flush()
+        e1.record()
+        torch.cuda.synchronize()
+        flush_ms.append(e0.elapsed_time(e1))
+    return sorted(flush_ms)[len(flush_ms) // 2], sorted(catch_us)[len(catch_us) // 2]
 
 
 def eager_launches(model, batches):
@@ -82,53 +123,69 @@ def kernel_rate(model, batches, optimizer):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--block", type=int, default=50, help="steps per alternating block")
+    ap.add_argument("--steps", type=int, default=256)
+    ap.add_argument("--block", type=int, default=128, help="steps per alternating block (longer than the flush period)")
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--vocab", default="mid,criteo-card")
     ap.add_argument("--optimizers", default="sgd,adagrad")
+    ap.add_argument("--arms", default="sweep,deferred,stock")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = bench.WORKLOADS["criteo_c2"]
     B = cfg["batch"]
+    arms = args.arms.split(",")
     results = []
     for preset in args.vocab.split(","):
         vocab = bench.preset_vocab(preset, cfg["n_sparse"])
         batches = [(torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev))
                    for X, y in bench.synthetic_batches(8, B, vocab, cfg["n_dense"], seed=2025)]
         for optimizer in args.optimizers.split(","):
-            new = build(cfg, vocab, dev, optimizer, stock=False)
-            old = build(cfg, vocab, dev, optimizer, stock=True)
-            for m in (new, old):
+            models = {a: build(cfg, vocab, dev, optimizer, stock=a == "stock", deferred=a == "deferred") for a in arms}
+            for m in models.values():
                 timed(m, batches, args.warmup, 0)
-            n_table = sum(t.numel() for t in new._gather_tables())
-            t_new = t_old = 0.0
+            native = models.get("sweep", models.get("deferred"))
+            n_table = sum(t.numel() for t in native._gather_tables()) if native is not None else 0
+            secs = {a: 0.0 for a in arms}
             done = 0
             while done < args.steps:
                 n = min(args.block, args.steps - done)
-                t_new += timed(new, batches, n, done)
-                t_old += timed(old, batches, n, done)
+                for a in arms:
+                    secs[a] += timed(models[a], batches, n, done)
                 done += n
-            step = new.__dict__["_graphed_step"]
-            nodes = [e.nodes for e in step.entries.values() if e.graph is not None]
-            launches_old = eager_launches(old, batches)
-            nbytes, secs = kernel_rate(new, batches, optimizer)
-            row = dict(vocab=preset, table_params=n_table, optimizer=optimizer, steps=args.steps,
-                       ms_new=round(t_new / args.steps * 1e3, 4), ms_stock=round(t_old / args.steps * 1e3, 4),
-                       speedup=round(t_old / t_new, 3), replays=step.replays, graph_nodes=nodes[0] if nodes else None,
-                       launches_stock=launches_old, sweep_bytes=int(nbytes), sweep_us=round(secs * 1e6, 2),
-                       sweep_TBps=round(nbytes / secs / 1e12, 3))
+            row = dict(vocab=preset, table_params=n_table, optimizer=optimizer, steps=args.steps, block=args.block)
+            for a in arms:
+                row["ms_" + a] = round(secs[a] / args.steps * 1e3, 4)
+            if "sweep" in models:
+                step = models["sweep"].__dict__["_graphed_step"]
+                nodes = [e.nodes for e in step.entries.values() if e.graph is not None]
+                nbytes, ksecs = kernel_rate(models["sweep"], batches, optimizer)
+                row.update(replays=step.replays, graph_nodes=nodes[0] if nodes else None, sweep_bytes=int(nbytes),
+                           sweep_us=round(ksecs * 1e6, 2), sweep_TBps=round(nbytes / ksecs / 1e12, 3))
+            if "stock" in models:
+                row["launches_stock"] = eager_launches(models["stock"], batches)
+                if "sweep" in models:
+                    row["speedup"] = round(secs["stock"] / secs["sweep"], 3)
+            if "deferred" in models:
+                opt = models["deferred"].optim
+                flush_ms, catch_us = deferred_parts(models["deferred"], batches)
+                nbytes, ksecs = kernel_rate(models["deferred"], batches, optimizer)
+                opt.flush()
+                row.update(flush_every=opt.flush_every, deferred_steps=opt.path_counts["scan"], flush_ms=round(flush_ms, 3),
+                           flush_ms_per_step=round(flush_ms / opt.flush_every, 4), catchup_us=round(catch_us, 1),
+                           scan_us=round(ksecs * 1e6, 2))
             print(json.dumps(row), flush=True)
             results.append(row)
-            del new, old, step
+            del models, native
             torch.cuda.empty_cache()
-    print("| vocabulary | optimizer | new ms/step | stock ms/step | stock / new | sweep us | sweep TB/s | launches new (graph nodes) | launches stock |")
-    print("|---|---|---|---|---|---|---|---|---|")
+    g = lambda r, k, f="%.3f": (f % r[k]) if isinstance(r.get(k), (int, float)) else "-"
+    print("| vocabulary | optimizer | sweep ms/step | deferred ms/step | stock ms/step | stock / sweep | flush ms | flush ms/step | catch-up us | step scan us | sweep us | sweep TB/s | launches sweep (graph nodes) | launches stock |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     for r in results:
-        print("| %s (%.0f M table parameters) | %s | %.3f | %.3f | %.2f | %.1f | %.2f | 1 (%s) | %s |" % (
-            r["vocab"], r["table_params"] / 1e6, r["optimizer"], r["ms_new"], r["ms_stock"], r["speedup"], r["sweep_us"],
-            r["sweep_TBps"], r["graph_nodes"], r["launches_stock"]))
+        print("| %s (%.0f M table parameters) | %s | %s | %s | %s | %s | %s | %s | %s | %s | %s | %s | 1 (%s) | %s |" % (
+            r["vocab"], r["table_params"] / 1e6, r["optimizer"], g(r, "ms_sweep"), g(r, "ms_deferred"), g(r, "ms_stock"),
+            g(r, "speedup", "%.2f"), g(r, "flush_ms"), g(r, "flush_ms_per_step"), g(r, "catchup_us", "%.1f"), g(r, "scan_us", "%.1f"),
+            g(r, "sweep_us", "%.1f"), g(r, "sweep_TBps", "%.2f"), r.get("graph_nodes", "-"), r.get("launches_stock", "-")))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:

@@ -1,0 +1,41 @@
+// The element update of the SGD / Adagrad steps (K7s / K7g, sgd_adagrad.hip) and of their deferred form (K7sd / K7gd,
+// sgd_adagrad_deferred.hip): ONE definition, included by both translation units.  The deferred kernels replay the steps a
+// chunk missed by calling this very function with g = 0 (an opaque zero, as the sweep's unmarked chunks do) and the rate
+// the missed step used -- the bit identity of the two paths rests on there being nothing else that spells the arithmetic.
+// Both units are compiled with the same flags: sqrtf and / expand to hipcc's correctly rounded sequences in either.
+#pragma once
+#include <hip/hip_runtime.h>
+
+typedef float opt_v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float4* opt_at4(float4* base, unsigned byte_off) {
+    return reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off);
+}
+// p and the accumulator are read once and written once per pass: non-temporal
+__device__ __forceinline__ float4 opt_ld(const float4* a) {
+    const opt_v4f t = __builtin_nontemporal_load(reinterpret_cast<const opt_v4f*>(a));
+    return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ void opt_st(float4* a, const float4& x) {
+    const opt_v4f t = {x.x, x.y, x.z, x.w};
+    __builtin_nontemporal_store(t, reinterpret_cast<opt_v4f*>(a));
+}
+
+// One element.  The fusions are spelled out and the compiler's own contraction is off, so that the marked, the dense, the
+// scalar and the replaying loops give the same bits.  `sq` collects p^2 of the weight BEFORE the update (the L2 term's value).
+template <bool ADA>
+__device__ __forceinline__ void opt_one(float& p, float& s, float g, float g2, float nlr, float eps, float& sq) {
+#pragma clang fp contract(off)
+    sq = fmaf(p, p, sq);
+    const float gp = fmaf(g2, p, g);
+    if constexpr (ADA) {
+        s = s + gp * gp;
+        p = fmaf(nlr, gp / (sqrtf(s) + eps), p);
+    } else {
+        p = fmaf(nlr, gp, p);
+    }
+}
+template <bool ADA>
+__device__ __forceinline__ void opt_four(float4& p, float4& s, const float4& g, float g2, float nlr, float eps, float& sq) {
+    opt_one<ADA>(p.x, s.x, g.x, g2, nlr, eps, sq); opt_one<ADA>(p.y, s.y, g.y, g2, nlr, eps, sq);
+    opt_one<ADA>(p.z, s.z, g.z, g2, nlr, eps, sq); opt_one<ADA>(p.w, s.w, g.w, g2, nlr, eps, sq);
+}

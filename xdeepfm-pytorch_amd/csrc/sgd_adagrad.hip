@@ -17,6 +17,7 @@
 // Descriptors by value in the kernel arguments, a 1-D grid shared out by tensor size, the learning rate as an argument
 // or from one device double, per-block L2 partials summed in a fixed order by a finish kernel: all as K7.
 #include "xdfm_internal.h"
+#include "opt_math.h"      // opt_one / opt_four: the element update, shared with the deferred kernels
 
 #include <algorithm>
 #include <vector>
@@ -26,43 +27,9 @@
 #define OPT_BLOCK_ELEMS 8192    // a tensor gets one block per this many elements
 #define OPT_CHUNK 64            // tensors per launch: 64 descriptors of 48 bytes + first[] stay inside the 4 KB argument block
 
-typedef float opt_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4* opt_at4(float4* base, unsigned byte_off) {
-    return reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off);
-}
-// p and the accumulator are read once and written once per step: non-temporal
-__device__ __forceinline__ float4 opt_ld(const float4* a) {
-    const opt_v4f t = __builtin_nontemporal_load(reinterpret_cast<const opt_v4f*>(a));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void opt_st(float4* a, const float4& x) {
-    const opt_v4f t = {x.x, x.y, x.z, x.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<opt_v4f*>(a));
-}
-
 struct OptDev { float* param; float* grad; float* state; unsigned char* grad_marks; long numel; float l2; };
 struct OptBatch { OptDev t[OPT_CHUNK]; int first[OPT_CHUNK + 1]; };
 static_assert(sizeof(OptBatch) + 128 <= 4096, "the optimizer kernels' argument block");
-
-// One element.  The fusions are spelled out and the compiler's own contraction is off, so that the marked, the dense and
-// the scalar loops give the same bits.  `sq` collects p^2 of the weight BEFORE the update (the L2 term's value).
-template <bool ADA>
-__device__ __forceinline__ void opt_one(float& p, float& s, float g, float g2, float nlr, float eps, float& sq) {
-#pragma clang fp contract(off)
-    sq = fmaf(p, p, sq);
-    const float gp = fmaf(g2, p, g);
-    if constexpr (ADA) {
-        s = s + gp * gp;
-        p = fmaf(nlr, gp / (sqrtf(s) + eps), p);
-    } else {
-        p = fmaf(nlr, gp, p);
-    }
-}
-template <bool ADA>
-__device__ __forceinline__ void opt_four(float4& p, float4& s, const float4& g, float g2, float nlr, float eps, float& sq) {
-    opt_one<ADA>(p.x, s.x, g.x, g2, nlr, eps, sq); opt_one<ADA>(p.y, s.y, g.y, g2, nlr, eps, sq);
-    opt_one<ADA>(p.z, s.z, g.z, g2, nlr, eps, sq); opt_one<ADA>(p.w, s.w, g.w, g2, nlr, eps, sq);
-}
 
 // chunks per array and thread in flight: SGD streams one array, Adagrad two -- eight 16-byte loads per thread either way
 template <bool ADA> struct OptFlight { static constexpr int N = ADA ? 4 : 8; };
@@ -279,6 +246,13 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
     }
     if (l2_value) hipLaunchKernelGGL(opt_l2_finish_kernel, dim3(1), dim3(1024), 0, st, l2_ws, slot0, l2_value);
     return xdfm_check_launch(what);
+}
+
+// the sweep over the tensors the deferred step (sgd_adagrad_deferred.hip) does not defer: the same launches as below
+int xdfm_opt_step_dense(bool ada, const char* what, const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
+                        float* l2_ws, float* l2_value, void* stream) {
+    return ada ? opt_step_impl<true>(what, tensors, T, lr, lr_dev, eps, l2_ws, l2_value, stream)
+               : opt_step_impl<false>(what, tensors, T, lr, lr_dev, 0.0, l2_ws, l2_value, stream);
 }
 
 extern "C" {

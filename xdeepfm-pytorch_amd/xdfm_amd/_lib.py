@@ -79,6 +79,10 @@ SIGNATURES = {
     "xdfm_opt_step_ws_elems": (c_size_t, [c_int]),
     "xdfm_sgd_step": (c_int, [P, c_int, c_double, P, P, P, P]),
     "xdfm_adagrad_step": (c_int, [P, c_int, c_double, P, c_double, P, P, P]),
+    "xdfm_sgd_step_deferred": (c_int, [P, P, c_int, P, c_double, P, P, P, P]),
+    "xdfm_adagrad_step_deferred": (c_int, [P, P, c_int, P, c_double, P, c_double, P, P, P]),
+    "xdfm_opt_catchup_rows": (c_int, [c_int, P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, P]),
+    "xdfm_opt_flush": (c_int, [c_int, P, P, c_int, P, c_double, P]),
     "xdfm_vocab_lse_update": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_softmax_grad": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_ce_x3_supported": (c_int, [c_int]),
@@ -113,6 +117,16 @@ class OptTensor(ctypes.Structure):
     """xdfm_opt_tensor of include/xdfm.h (SGD / Adagrad; `state` is Adagrad's accumulator)"""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("state", c_void_p), ("numel", c_long), ("l2", ctypes.c_float),
                 ("grad_marks", c_void_p)]
+
+
+class OptClock(ctypes.Structure):
+    """xdfm_opt_clock of include/xdfm.h (deferred SGD / Adagrad)"""
+    _fields_ = [("clock", c_void_p), ("rates", c_void_p), ("cap", c_int), ("backlog", c_void_p), ("cell", c_void_p)]
+
+
+class OptRows(ctypes.Structure):
+    """xdfm_opt_rows of include/xdfm.h (device pointer tables of one gather's fields)"""
+    _fields_ = [("param", c_void_p), ("state", c_void_p), ("last", c_void_p), ("l2", c_void_p)]
 
 
 class AdamClock(ctypes.Structure):

@@ -16,7 +16,8 @@ their chunk marks: K7 skips the untouched rows of the dense table gradients and 
 
 `TableSGD` and `TableAdagrad` (K7s / K7g, `xdfm_sgd_step` / `xdfm_adagrad_step`) give the trainer's two other optimizers
 (`--optimizer sgd|adagrad`, basemodel.py:447-461) the same sweep, armed L2 term, marked gradients and device-resident
-learning rate; their state layout is that of torch.optim.SGD / torch.optim.Adagrad."""
+learning rate; their state layout is that of torch.optim.SGD / torch.optim.Adagrad.  Tables with an L2 term may take the
+deferred (exact) form of those steps (K7sd / K7gd, `xdfm_sgd_step_deferred` / `xdfm_adagrad_step_deferred`), as TableAdam's do."""
 import ctypes
 import os
 
@@ -26,6 +27,10 @@ from . import _lib
 
 DEFER_CAP = 256          # steps the clock's constant table holds (the `last` bytes count steps since the last flush)
 DEFER_MIN_NUMEL = int(os.environ.get("XDFM_ADAM_DEFER_MIN_NUMEL", 1 << 26))   # "auto": tables of fewer parameters in total take the dense sweep
+# The floor of "auto" for TableSGD / TableAdagrad (K7sd / K7gd), never below Adam's.  Measured: the sweep wins by
+# 5 % at 44 M table parameters, the deferral by 29 % (SGD) / 36 % (Adagrad) at 574 M; the straight line between the two puts
+# the crossover near 94 M (SGD) / 79 M (Adagrad).  2^27 is above both.
+OPT_DEFER_MIN_NUMEL = max(int(os.environ.get("XDFM_OPT_DEFER_MIN_NUMEL", 1 << 27)), 1 << 26)
 ROWS_MIN_NUMEL = 1 << 20  # tables at least this large get the step's update by the batch's rows (XDFM_ADAM_ROWS_MIN_NUMEL overrides)
 
 
@@ -476,7 +481,20 @@ class _TableStep(object):
     table_step = True
     _KERNEL = None               # "sgd" / "adagrad"
 
-    def _table_init(self):
+    def _table_init(self, deferred=None, flush_every=64):
+        # Deferred (exact) update of the tables, include/xdfm.h "K7sd / K7gd": same bits as the dense sweep, but a row with
+        # an L2 term is brought up to date when a batch gathers it, when a gradient arrives for it, and every `flush_every`
+        # steps for all rows.  `deferred`: True / False / "auto" (None: XDFM_OPT_DEFERRED = 1 / 0 / auto, default auto):
+        # "auto" defers when the gathers' tables hold at least OPT_DEFER_MIN_NUMEL parameters.  Applies, like the marks,
+        # inside the model's own train step in a single process.
+        env = os.environ.get("XDFM_OPT_DEFERRED", "auto")
+        self.deferred = (False if env == "0" else True if env == "1" else "auto") if deferred is None else \
+            (deferred if deferred == "auto" else bool(deferred))
+        self.flush_every = max(1, min(int(os.environ.get("XDFM_OPT_FLUSH_EVERY", flush_every)), DEFER_CAP - 8))
+        self._def = None            # clock, rates, per-table `last` bytes, backlog (built by the first deferred step)
+        self._since = 0             # steps since the last flush (host count of what the device clock holds)
+        self._auto_numel = None
+        self.path_counts = {"scan": 0}      # deferred steps issued (or captured): by a scan of the mark bytes
         self._armed = None          # id(parameter) -> L2 strength, for the next step only
         self._desc = {}             # group index -> (key, ctypes array of xdfm_opt_tensor)
         self.l2_value = None        # [1] device tensor: value of the armed L2 term at the last step
@@ -507,30 +525,161 @@ class _TableStep(object):
     def _invalidate(self):
         """State tensors may have been replaced: forget the cached descriptors and make every captured graph that baked
         their addresses stale (graphstep._signature hashes `generation`)."""
+        self.flush()                 # no-op when the caller flushed before it replaced the state
         self._desc = {}
         self._lr_dev = {}
         self._replay_steps = None
         self.generation += 1
+        self._auto_numel = None      # the "auto" decision follows the param groups
+        self._drop_deferred()
 
     def load_state_dict(self, state_dict):
+        self.flush()                 # rows that still owe replayed steps get them from the OLD accumulators, before those go
         out = super().load_state_dict(state_dict)
         self._invalidate()
         return out
 
     def add_param_group(self, param_group):
-        out = super().add_param_group(param_group)
         if hasattr(self, "_desc"):              # the base constructor comes here before _table_init
+            self.flush()
+        out = super().add_param_group(param_group)
+        if hasattr(self, "_desc"):
             self._invalidate()
         return out
 
+    def state_dict(self):
+        # flush, then drop the deferred state: what is handed out is current and shares nothing with the deferral.  A graph
+        # captured with the catch-up and the clock baked in is stale from here on (`generation`); the next eager step of
+        # the model builds the state again.
+        self.flush()
+        if self.__dict__.get("_def") is not None:
+            self._drop_deferred()
+            self.generation += 1
+        return super().state_dict()
+
+    # ------------------------------------------------------------------ deferred update of the tables (K7sd / K7gd)
+    def _drop_deferred(self):
+        d = self.__dict__.get("_def")
+        if d is not None:
+            for plan in d["plans"]:
+                plan.catchup = None
+            self.__dict__["_backlog_kept"] = d["backlog"]      # the L2 value of replayed steps nobody has taken yet survives
+        self._def = None
+        self._since = 0
+
+    def _deferred_state(self, dev):
+        if self._def is None:
+            i64 = dict(dtype=torch.int64, device=dev)
+            kept = self.__dict__.pop("_backlog_kept", None)
+            d = self._def = dict(clock=torch.zeros(2, dtype=torch.int32, device=dev),
+                                 rates=torch.zeros(DEFER_CAP, dtype=torch.float32, device=dev),
+                                 backlog=kept if kept is not None and kept.device == dev else torch.zeros(1, **i64),
+                                 cell=torch.zeros(1, **i64), last={}, tensors={}, rows={}, plans=[], eps=None)
+            d["clk"] = _lib.OptClock(d["clock"].data_ptr(), d["rates"].data_ptr(), DEFER_CAP, d["backlog"].data_ptr(),
+                                     d["cell"].data_ptr())
+            for src in self.grad_sources:             # the gathers whose rows must be current before they are read
+                if hasattr(src, "catchup"):
+                    src.catchup = self._catchup
+                    d["plans"].append(src)
+            self.generation += 1                       # a step captured without the catch-up launch is stale
+        return self._def
+
+    def _last_bytes(self, p):
+        d = self._def
+        hit = d["last"].get(p.data_ptr())
+        if hit is None:
+            hit = d["last"][p.data_ptr()] = torch.zeros(p.numel() // 4 + 8, dtype=torch.uint8, device=p.device)
+        return hit
+
+    def _catchup(self, plan, X, emb_tables, lin_tables):
+        """Called by the gather (ops.EmbedGather.forward) before it reads the rows of X."""
+        d = self.__dict__.get("_def")
+        if d is None or not d["tensors"]:
+            return
+        if self._since == 0 and not torch.cuda.is_current_stream_capturing():
+            return
+        key = (tuple(t.data_ptr() for t in emb_tables), tuple(t.data_ptr() for t in lin_tables))
+        rows = d["rows"].get(key)
+        if rows is None:
+            # The pointer tables are built with torch.tensor(..., device=): a host-to-device copy from pageable memory, which
+            # must not happen inside a capture.  It does not: GraphedStep captures after eager warm-up steps, `_def` is built
+            # by an eager step (which makes every older graph stale), and the eager step after that one comes here with
+            # `_since > 0` and fills this cache for the same tables.  Should a capture get here first all the same, the copy
+            # fails the capture and the model falls back to eager steps (graphstep._capture).
+            def table_of(ts):
+                # a field whose table is not deferred (no L2 term, frozen) has a null entry: the kernel leaves it alone
+                ent = [d["tensors"].get(t.data_ptr()) for t in ts]
+                if not ts or all(e is None for e in ent):
+                    return None, None
+                dev = ts[0].device
+                mk = lambda vals: torch.tensor(vals, dtype=torch.int64, device=dev)
+                arrs = (mk([t.data_ptr() if e is not None else 0 for t, e in zip(ts, ent)]),
+                        mk([e[0].data_ptr() if e is not None and e[0] is not None else 0 for e in ent]),
+                        mk([e[1].data_ptr() if e is not None else 0 for e in ent]),
+                        torch.tensor([e[2] if e is not None else 0.0 for e in ent], dtype=torch.float32, device=dev))
+                return _lib.OptRows(*[a.data_ptr() for a in arrs]), arrs
+            e_struct, e_keep = table_of(list(emb_tables))
+            l_struct, l_keep = table_of(list(lin_tables))
+            if e_struct is None and l_struct is not None:      # only linear tables are deferred: an all-null embedding side
+                dev = X.device
+                nul = torch.zeros(len(emb_tables), dtype=torch.int64, device=dev)
+                zl2 = torch.zeros(len(emb_tables), dtype=torch.float32, device=dev)
+                e_struct, e_keep = _lib.OptRows(nul.data_ptr(), nul.data_ptr(), nul.data_ptr(), zl2.data_ptr()), (nul, zl2)
+            rows = d["rows"][key] = (e_struct, l_struct, e_keep, l_keep)
+        e_struct, l_struct = rows[0], rows[1]
+        if e_struct is None:
+            return                                      # tables this optimizer does not update by deferral
+        cols, vocab, _, _ = plan.on(X.device)
+        ada = self._KERNEL == "adagrad"
+        _lib.check(_lib.load().xdfm_opt_catchup_rows(
+            1 if ada else 0, X.data_ptr(), X.stride(0), X.shape[0], cols.data_ptr(), vocab.data_ptr(), plan.m, plan.D,
+            ctypes.byref(e_struct), ctypes.byref(l_struct) if l_struct is not None else None, ctypes.byref(d["clk"]),
+            float(d["eps"] or 0.0), torch.cuda.current_stream(X.device).cuda_stream), "opt_catchup_rows")
+
+    @torch.no_grad()
+    def flush(self):
+        """Every deferred chunk up to date; afterwards parameters and accumulators are what the dense sweep would hold."""
+        d = self.__dict__.get("_def")
+        if d is None or self._since == 0:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("xdfm %s: flush inside a HIP-graph capture" % type(self).__name__)
+        ent = list(d["tensors"].items())
+        if ent:
+            arr = (_lib.OptTensor * len(ent))()
+            last = (ctypes.c_void_p * len(ent))()
+            for k, (ptr, (state, lb, l2, numel)) in enumerate(ent):
+                arr[k].param, arr[k].numel, arr[k].l2 = ptr, numel, l2
+                arr[k].state = state.data_ptr() if state is not None else None
+                last[k] = lb.data_ptr()
+            dev = d["clock"].device
+            _lib.check(_lib.load().xdfm_opt_flush(1 if self._KERNEL == "adagrad" else 0, ctypes.cast(arr, ctypes.c_void_p),
+                                                  ctypes.cast(last, ctypes.c_void_p), len(ent), ctypes.byref(d["clk"]),
+                                                  float(d["eps"] or 0.0), torch.cuda.current_stream(dev).cuda_stream), "opt_flush")
+        self._since = 0
+
+    def take_backlog(self):
+        """L2 value of the replayed steps since the last call (a host float; syncs).  Over an epoch, the per-step L2 values
+        plus this equal the dense path's sum."""
+        d = self.__dict__.get("_def")
+        cell = d["backlog"] if d is not None else self.__dict__.get("_backlog_kept")
+        if cell is None:
+            return 0.0
+        v = float(cell.item()) / float(1 << 40)
+        cell.zero_()
+        return v
+
     def __getstate__(self):
+        self.flush()                            # a pickled optimizer (torch.save(model)) goes with current rows
         state = dict(super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__)
         for k in ("_desc", "_lr_dev"):          # ctypes descriptors / device scalars: rebuilt on use
             state[k] = {}
-        for k in ("_armed", "l2_value", "_replay_steps"):
+        for k in ("_armed", "l2_value", "_replay_steps", "_def", "_auto_numel", "_backlog_kept"):
             state[k] = None
+        state["_since"] = 0
         state["grad_sources"] = []
         state["generation"] = self.generation
+        state["deferred"], state["flush_every"] = self.deferred, self.flush_every
         return state
 
     def __setstate__(self, state):
@@ -541,6 +690,12 @@ class _TableStep(object):
         for k in ("_armed", "l2_value", "_replay_steps"):
             self.__dict__.setdefault(k, None)
         self.__dict__.setdefault("grad_sources", [])
+        self.__dict__.setdefault("deferred", False)
+        self.__dict__.setdefault("flush_every", 64)
+        self.__dict__.setdefault("path_counts", {"scan": 0})
+        self.__dict__["_def"] = None
+        self.__dict__["_since"] = 0
+        self.__dict__["_auto_numel"] = None
         self.generation = gen + 1
 
     def owns(self, tensors):
@@ -554,9 +709,14 @@ class _TableStep(object):
             self._armed[id(t)] = self._armed.get(id(t), 0.0) + float(c)
 
     def note_replay(self):
-        """Called before a captured step is replayed: the host-side step counters (Adagrad) still count it."""
+        """Called before a captured step is replayed (its Python does not run): the host-side step counters (Adagrad)
+        still count it; deferred update: periodic flush, step count."""
         if self._replay_steps:
             torch._foreach_add_(self._replay_steps, 1)
+        if self.__dict__.get("_def") is not None:
+            if self._since >= self.flush_every:
+                self.flush()
+            self._since += 1
 
     def _l2_by_hand(self, armed):
         """Fallback path: apply the armed term with ATen ops before torch's own step."""
@@ -598,12 +758,14 @@ class _TableStep(object):
         armed, self._armed = self._armed, None
         self.l2_value = None
         if closure is not None or not self._native():
+            self.flush()                               # the stock step updates every row: they must be current
             if armed:
                 self._l2_by_hand(armed)
             return super().step(closure)
         self.sync_lr()
         lib = _lib.load()
         from . import ops                              # per-kernel timing hook of bench.py
+        from . import dist as xdist
         ada = self._KERNEL == "adagrad"
         capturing = torch.cuda.is_current_stream_capturing()
         host_steps = []
@@ -627,7 +789,22 @@ class _TableStep(object):
                 hit = self._desc[gi] = (key, arr)
             arr = hit[1]
             arenas = [a for src in self.grad_sources for a in src.arenas() if a.pending]
-            nbytes = 0.0
+            # Deferral: the tables of the gathers that feed this optimizer, in group 0, with an L2 term and marked gradients,
+            # in a single process (a row-parallel run keeps the sweep).  With l2 == 0 the sweep's exact shortcut already
+            # skips untouched chunks: nothing to defer.
+            defer_ok = bool(self.deferred) and gi == 0 and l2 is not None and xdist.current() is None
+            table_ptrs = set()
+            if defer_ok:
+                for src in self.grad_sources:
+                    lg = getattr(src, "last_gather", None)
+                    if lg is not None:
+                        table_ptrs.update(t.data_ptr() for t in lg[1])
+                        table_ptrs.update(t.data_ptr() for t in lg[2])
+            if defer_ok and self.deferred == "auto":
+                if self.__dict__.get("_auto_numel") is None:           # the tables' sizes do not change: decided once
+                    self._auto_numel = sum(p.numel() for p in params if p.data_ptr() in table_ptrs)
+                defer_ok = self._auto_numel >= OPT_DEFER_MIN_NUMEL
+            deferred_now = []
             for k in range(T):
                 gp = grads[k].data_ptr()
                 arr[k].grad, arr[k].grad_marks = gp, None
@@ -635,14 +812,53 @@ class _TableStep(object):
                     mp = a.marks_ptr(gp)
                     if mp is not None and params[k].data_ptr() % 16 == 0 and (arr[k].state or 0) % 16 == 0:
                         arr[k].grad_marks = mp
+                        if defer_ok and l2[k] > 0.0 and params[k].data_ptr() in table_ptrs:
+                            deferred_now.append(k)
                         a.consumed(gp)
                         break
+            dev = params[0].device
+            d = self.__dict__.get("_def")
+            last_arr = None
+            if gi != 0:
+                pass                                   # the deferred tables live in group 0: a later group leaves their clock alone
+            elif d is not None and not deferred_now:
+                # tables that were deferred arrive without marks (a user-driven loop) or may no longer be deferred: bring
+                # everything up to date and take this step densely.  Inside a capture with steps owed, flush() raises: the
+                # capture fails and GraphedStep goes on eagerly (its warm-up steps come through here first, so a capture
+                # normally finds `_since == 0` or marked gradients).
+                self.flush()
+            elif deferred_now:
+                if d is None and not capturing:        # state is built by an eager step, never inside a capture
+                    d = self._deferred_state(dev)
+                if d is None:
+                    deferred_now = []
+                else:
+                    want = {params[k].data_ptr(): (states[k][0], float(l2[k]), params[k].numel()) for k in deferred_now}
+                    eps = float(group["eps"]) if ada else None
+                    same = d["eps"] == eps and len(want) == len(d["tensors"]) and all(
+                        ptr in d["tensors"] and d["tensors"][ptr][0] is w[0] and d["tensors"][ptr][2] == w[1]
+                        for ptr, w in want.items())
+                    if not same:
+                        # the set of deferred tables, an L2 strength or eps changed: the replays assumed the old ones
+                        if capturing:                  # (the `last` bytes are allocated and zeroed by an eager step)
+                            raise RuntimeError("xdfm %s: the deferred tables changed inside a HIP-graph capture" % type(self).__name__)
+                        self.flush()
+                        byptr = {params[k].data_ptr(): params[k] for k in deferred_now}
+                        d["tensors"] = {ptr: (w[0], self._last_bytes(byptr[ptr]), w[1], w[2]) for ptr, w in want.items()}
+                        d["rows"], d["eps"] = {}, eps
+                    if not capturing and self._since >= self.flush_every:
+                        self.flush()
+                    last_arr = (ctypes.c_void_p * T)()
+                    for k in deferred_now:
+                        last_arr[k] = d["tensors"][params[k].data_ptr()][1].data_ptr()
+            nbytes = 0.0
+            for k in range(T):
                 per = 16.0 if ada else 8.0             # the byte model of DESIGN.md (K7s / K7g)
                 if arr[k].grad_marks:
-                    nbytes += params[k].numel() * (0.0625 if arr[k].l2 == 0.0 else per + 0.0625)
+                    skip = arr[k].l2 == 0.0 or (last_arr is not None and last_arr[k])
+                    nbytes += params[k].numel() * (0.0625 if skip else per + 0.0625)
                 else:
                     nbytes += params[k].numel() * (per + 4.0)
-            dev = params[0].device
             ws = val = None
             if l2 is not None and any(l2):
                 ws = torch.empty(lib.xdfm_opt_step_ws_elems(T), dtype=torch.float32, device=dev)
@@ -651,7 +867,19 @@ class _TableStep(object):
             lr_dev = self._lr_dev.get(gi)
             lr_ptr = lr_dev[1].data_ptr() if lr_dev is not None else None
             ws_ptr, val_ptr = (ws.data_ptr(), val.data_ptr()) if val is not None else (None, None)
-            if ada:
+            if last_arr is not None:
+                lasts, clk = ctypes.cast(last_arr, ctypes.c_void_p), ctypes.byref(d["clk"])
+                if ada:
+                    launch = lambda: lib.xdfm_adagrad_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
+                                                                    float(group["lr"]), lr_ptr, float(group["eps"]), ws_ptr,
+                                                                    val_ptr, stream)
+                else:
+                    launch = lambda: lib.xdfm_sgd_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
+                                                                float(group["lr"]), lr_ptr, ws_ptr, val_ptr, stream)
+                self.path_counts["scan"] += 1
+                if not capturing:
+                    self._since += 1
+            elif ada:
                 launch = lambda: lib.xdfm_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                        float(group["eps"]), ws_ptr, val_ptr, stream)
             else:
@@ -674,10 +902,11 @@ class TableSGD(_TableStep, torch.optim.SGD):
     closures fall back to torch.optim.SGD.step with the armed L2 term applied by hand."""
     _KERNEL = "sgd"
 
-    def __init__(self, params, lr=0.01, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False):
+    def __init__(self, params, lr=0.01, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
+                 deferred=None, flush_every=64):
         super().__init__(params, lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
                          nesterov=nesterov, maximize=maximize)
-        self._table_init()
+        self._table_init(deferred, flush_every)
 
     def _plain(self, group):
         return group["momentum"] == 0 and group["dampening"] == 0 and not group["nesterov"]
@@ -695,10 +924,10 @@ class TableAdagrad(_TableStep, torch.optim.Adagrad):
     _KERNEL = "adagrad"
 
     def __init__(self, params, lr=0.01, lr_decay=0, weight_decay=0, initial_accumulator_value=0, eps=1e-10, *,
-                 maximize=False):
+                 maximize=False, deferred=None, flush_every=64):
         super().__init__(params, lr=lr, lr_decay=lr_decay, weight_decay=weight_decay,
                          initial_accumulator_value=initial_accumulator_value, eps=eps, maximize=maximize)
-        self._table_init()
+        self._table_init(deferred, flush_every)
 
     def _plain(self, group):
         return group["lr_decay"] == 0 and group["eps"] > 0 and not group.get("fused")
