@@ -40,7 +40,8 @@
  * and ReLU sign bits from the forward's epilogue; the direct-connect half of a level is never stored).
  * ABI 8 additions (no existing struct or signature changed): xdfm_opt_tensor, xdfm_opt_step_ws_elems, xdfm_sgd_step,
  * xdfm_adagrad_step (K7s / K7g: the streaming sweep for the trainer's two other optimizers); xdfm_opt_clock, xdfm_opt_rows,
- * xdfm_sgd_step_deferred, xdfm_adagrad_step_deferred, xdfm_opt_catchup_rows, xdfm_opt_flush (K7sd / K7gd: their deferred form).
+ * xdfm_sgd_step_deferred, xdfm_adagrad_step_deferred, xdfm_opt_catchup_rows, xdfm_opt_flush (K7sd / K7gd: their deferred form);
+ * xdfm_autodis_supported, xdfm_autodis_ws_elems, xdfm_autodis_fwd, xdfm_autodis_bwd (K10: AutoDis of xdeepfm_pro).
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -606,6 +607,33 @@ int xdfm_vocab_ce_bwd_h(const float* pack, int R, int K, const xdfm_vce_field* f
                         float* dh, long lddh, void* stream);
 int xdfm_vocab_ce_bwd_w(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, int n_blk, const long* targets,
                         const float* gpack, const float* lse2, const unsigned* wmax, void* stream);
+
+/* ------------------------------------------------------------------ AutoDis of xdeepfm_pro (K10, csrc/autodis.hip)
+ * replaces: the per-field Python loop of deepctr/xdeepfm_pro/autodis.py:99-125 (Linear(1,K), LeakyReLU(0.2), Linear(K,K),
+ *           division by the field's temperature, softmax, matmul with the field's meta-embeddings, unsqueeze; then cat)
+ *           and its autograd -- about 7 launches per field forward and twice that backward -- by one launch forward and
+ *           one + one finish launch backward, for all F fields and B rows.  fp32 throughout, no float atomics: the
+ *           parameter gradients are per-workgroup partials summed in a fixed order, so a repeated call gives the same bits.
+ *   x       the dense values, x[b * ldx + f] (ldx >= F): the dense columns of a wider row-major matrix are read in place
+ *   meta    [F][K][D]; temp [F]
+ *   proj    DEVICE array of 4 * F device pointers, field-major: Linear(1,K).weight [K], .bias [K], Linear(K,K).weight
+ *           [K][K] (stored [out][in]), .bias [K] -- the tensors stay where the state_dict keeps them
+ *   out     [B][F * D], contiguous: out[b][f * D + d] = sum_k softmax(s / temp[f])_k meta[f][k][d]
+ *   supported   1 for 1 <= K <= 32 and 1 <= D <= 64 (instances for K <= 8 / 16 / 32 with a run-time tail), else 0
+ *   ws_elems    ceil(B / R) * F * (K * D + K * K + 3 * K + 1) floats with R = 256 rows per workgroup for K <= 16 and 128
+ *               for K > 16; 0 outside the envelope
+ *   bwd     g [B][ldg] (ldg >= F * D) is the gradient of out; only x is needed from the forward, which is recomputed.
+ *           flags: bit 0 meta, 1 Linear(1,K).weight, 2 its bias, 3 Linear(K,K).weight, 4 its bias, 5 temp, 6 dx -- the
+ *           gradients asked for.  grads (F * (K * D + K * K + 3 * K + 1) floats; needed with any of bits 0-5, as is ws)
+ *           receives [F][K][D] dmeta | [F][K] dW1 | [F][K] db1 | [F][K][K] dW2 | [F][K] db2 | [F] dtemp; the parts of
+ *           groups not asked for are left untouched.  dx [B][F], contiguous (needed with bit 6).
+ * Any F >= 1 and B >= 1 with ceil(B / 128) * F < 2^31.  Arguments are validated before any device work. */
+int xdfm_autodis_supported(int K, int D);
+size_t xdfm_autodis_ws_elems(long B, int F, int K, int D);
+int xdfm_autodis_fwd(const float* x, long ldx, long B, int F, int K, int D, const float* meta, const float* const* proj,
+                     const float* temp, float* out, void* stream);
+int xdfm_autodis_bwd(const float* x, long ldx, long B, int F, int K, int D, const float* meta, const float* const* proj,
+                     const float* temp, const float* g, long ldg, int flags, float* ws, float* grads, float* dx, void* stream);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,10 @@ SIGNATURES = {
     "xdfm_vocab_ce_pack_g": (c_int, [P, c_int, c_int, P, P]),
     "xdfm_vocab_ce_bwd_h": (c_int, [P, c_int, c_int, P, c_int, P, c_long, P, P, P, P, P, P, P, c_long, P]),
     "xdfm_vocab_ce_bwd_w": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, P, P]),
+    "xdfm_autodis_supported": (c_int, [c_int, c_int]),
+    "xdfm_autodis_ws_elems": (c_size_t, [c_long, c_int, c_int, c_int]),
+    "xdfm_autodis_fwd": (c_int, [P, c_long, c_long, c_int, c_int, c_int, P, P, P, P, P]),
+    "xdfm_autodis_bwd": (c_int, [P, c_long, c_long, c_int, c_int, c_int, P, P, P, P, c_long, c_int, P, P, P, P]),
     "xdfm_colsum_ws_elems": (c_size_t, [c_int]),
     "xdfm_colsum": (c_int, [P, c_long, c_int, c_long, P, P, P]),
     "xdfm_relu_bwd_colsum": (c_int, [P, P, c_long, c_int, c_long, c_long, P, P, P, P]),

@@ -957,6 +957,98 @@ def vocab_heads_ce(hidden, targets, weights, biases):
 
 
 # --------------------------------------------------------------------------------------------- #
+# AutoDis                                                                                        #
+# --------------------------------------------------------------------------------------------- #
+def autodis_supported(K: int, D: int) -> bool:
+    """True when csrc/autodis.hip serves K buckets and embedding width D (1 <= K <= 32, 1 <= D <= 64)."""
+    return bool(_lib.load().xdfm_autodis_supported(int(K), int(D)))
+
+
+def _autodis_table(proj, dev, cache: dict):
+    """Device array of the 4 * F projector pointers, kept in `cache` and rebuilt only when a data_ptr changes
+    (load_state_dict into fresh storage, .to()).  The rebuild is a blocking host-to-device copy, so it must happen
+    outside a graph capture: run the op once eagerly first."""
+    key = (dev,) + tuple(t.data_ptr() for t in proj)
+    hit = cache.get("autodis_table")
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("xdfm: the AutoDis pointer table is stale inside a graph capture -- call the layer once eagerly "
+                           "with these parameters before capturing it")
+    table = torch.tensor(key[1:], dtype=torch.int64).to(dev)
+    cache["autodis_table"] = (key, table)
+    return table
+
+
+class AutoDis(torch.autograd.Function):
+    """out [B, F * D] of AutoDisLayer (deepctr/xdeepfm_pro/autodis.py:99-125) for all F fields in one launch, backward in one
+    launch + a fixed-order finish (csrc/autodis.hip).  x [B, F] (any row stride: the dense columns of a wider matrix
+    are read in place), meta [F, K, D], temp [F], table (_autodis_table), then per field Linear(1,K).weight, .bias,
+    Linear(K,K).weight, .bias.  Only x is kept for the backward; the gradients come back as views of one flat buffer."""
+
+    calls = 0                 # forward passes taken (tests assert that a model reached this path)
+
+    @staticmethod
+    def forward(ctx, x, meta, temp, table, *proj):
+        lib = _lib.load()
+        AutoDis.calls += 1
+        B, F_ = x.shape
+        _, K, D = meta.shape
+        if x.stride(1) != 1 or x.stride(0) < F_:
+            x = x.contiguous()
+        for t in (meta, temp) + proj:
+            if not t.is_contiguous():
+                raise ValueError("xdfm: AutoDis parameters must be contiguous")
+        out = torch.empty(B, F_ * D, dtype=torch.float32, device=x.device)
+        _lib.check(lib.xdfm_autodis_fwd(_ptr(x), x.stride(0), B, F_, K, D, _ptr(meta), _ptr(table), _ptr(temp), _ptr(out), _stream()),
+                   "autodis_fwd")
+        ctx.save_for_backward(x, meta, temp, table, *proj)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x, meta, temp, table = ctx.saved_tensors[:4]
+        B, F_ = x.shape
+        _, K, D = meta.shape
+        need = ctx.needs_input_grad
+        pneed = [any(need[4 + 4 * f + i] for f in range(F_)) for i in range(4)]
+        flags = (1 if need[1] else 0) | (2 if pneed[0] else 0) | (4 if pneed[1] else 0) | (8 if pneed[2] else 0) | \
+            (16 if pneed[3] else 0) | (32 if need[2] else 0) | (64 if need[0] else 0)
+        if flags == 0:
+            return (None,) * (4 + 4 * F_)
+        if g.stride(1) != 1 or g.stride(0) < F_ * D:
+            g = g.contiguous()
+        dev = x.device
+        grads = ws = dx = None
+        if flags & 63:
+            grads = torch.empty(F_ * (K * D + K * K + 3 * K + 1), dtype=torch.float32, device=dev)
+            ws = torch.empty(lib.xdfm_autodis_ws_elems(B, F_, K, D), dtype=torch.float32, device=dev)
+        if flags & 64:
+            dx = torch.empty(B, F_, dtype=torch.float32, device=dev)
+        _lib.check(lib.xdfm_autodis_bwd(_ptr(x), x.stride(0), B, F_, K, D, _ptr(meta), _ptr(table), _ptr(temp), _ptr(g), g.stride(0),
+                                        flags, _ptr(ws), _ptr(grads), _ptr(dx), _stream()), "autodis_bwd")
+        FK, FKD, FKK = F_ * K, F_ * K * D, F_ * K * K
+        dmeta = grads[:FKD].view(F_, K, D) if need[1] else None
+        dtemp = grads[FKD + 3 * FK + FKK:] if need[2] else None
+        dproj = []
+        for f in range(F_):
+            parts = (grads[FKD + f * K:FKD + (f + 1) * K].view(K, 1) if need[4 + 4 * f] else None,
+                     grads[FKD + FK + f * K:FKD + FK + (f + 1) * K] if need[5 + 4 * f] else None,
+                     grads[FKD + 2 * FK + f * K * K:FKD + 2 * FK + (f + 1) * K * K].view(K, K) if need[6 + 4 * f] else None,
+                     grads[FKD + 2 * FK + FKK + f * K:FKD + 2 * FK + FKK + (f + 1) * K] if need[7 + 4 * f] else None)
+            dproj.extend(parts)
+        return (dx, dmeta, dtemp, None, *dproj)
+
+
+def autodis(x, meta, projectors, temp, cache: dict):
+    """[B, F * D] AutoDis embeddings of the dense values x [B, F].  projectors: the 4 * F tensors Linear(1,K).weight, .bias,
+    Linear(K,K).weight, .bias of each field in turn; cache: a dict the caller keeps (it holds the device pointer table)."""
+    _need_cuda(x, "dense values")
+    return AutoDis.apply(x, meta, temp, _autodis_table(projectors, x.device, cache), *projectors)
+
+
+# --------------------------------------------------------------------------------------------- #
 # L2 regulariser                                                                                 #
 # --------------------------------------------------------------------------------------------- #
 class L2Plan:

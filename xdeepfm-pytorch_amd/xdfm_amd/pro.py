@@ -11,9 +11,13 @@ What runs where:
     tiles in the backward; with `sfg_positive_only` (the default) only the rows with label 1 enter the decoder at all --
     masked rows contribute exact zeros to loss and gradients in the reference too (`ce_loss * positive_mask`).  The tile
     GEMMs are library GEMMs (hipBLASLt through torch); a hand-written MFMA kernel for them is the next step (DESIGN 7);
-  * the decoder MLP, LabelAwareAttention and AutoDis are small dense layers on torch ops.
+  * AutoDis runs in one fused launch forward and one (+ a fixed-order finish) backward for all dense fields
+    (`ops.AutoDis`, csrc/autodis.hip) on float32 GPU tensors with K <= 32 buckets and D <= 64; outside that envelope, on
+    the CPU or with XDFM_AUTODIS_NATIVE=0 it is the reference's per-field loop on torch ops;
+  * the decoder MLP and LabelAwareAttention are small dense layers on torch ops.
 The pro train step launches eagerly (the positive-row compaction has a data-dependent shape).
 """
+import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -153,6 +157,7 @@ class AutoDisLayer(nn.Module):
                 nn.Sequential(nn.Linear(1, num_buckets), nn.LeakyReLU(0.2), nn.Linear(num_buckets, num_buckets))
                 for _ in range(num_features)])
             self.feature_temperatures = nn.Parameter(torch.ones(num_features) * temperature)
+        self._native_cache = {}            # device pointer table of the projectors (ops.autodis)
         self.to(device)
 
     def forward(self, dense_values: List[torch.Tensor]):
@@ -160,6 +165,8 @@ class AutoDisLayer(nn.Module):
             batch_size = dense_values[0].shape[0] if dense_values else 1
             return torch.zeros(batch_size, 0, device=self.device), []
         batch_size = dense_values[0].shape[0]
+        if self._native(dense_values):
+            return self.forward_native(torch.cat([v.reshape(batch_size, 1) for v in dense_values], dim=-1))
         dense_embeddings = []
         for i, dense_val in enumerate(dense_values):
             if len(dense_val.shape) == 1:
@@ -168,6 +175,32 @@ class AutoDisLayer(nn.Module):
             weights = F.softmax(scores / self.feature_temperatures[i], dim=-1)
             dense_embeddings.append(torch.matmul(weights, self.meta_embeddings[i]).unsqueeze(1))
         return torch.cat(dense_embeddings, dim=1).view(batch_size, -1), dense_embeddings
+
+    def _native(self, dense_values) -> bool:
+        """The fused kernels (ops.AutoDis) serve float32 GPU tensors inside ops.autodis_supported's envelope unless
+        XDFM_AUTODIS_NATIVE=0; everything else keeps the per-field loop below."""
+        if os.environ.get("XDFM_AUTODIS_NATIVE", "1") == "0":
+            return False
+        if torch.is_tensor(dense_values):
+            tensors = [dense_values]
+            if dense_values.dim() != 2 or dense_values.shape[1] != self.num_features:
+                return False
+        else:
+            tensors = list(dense_values)
+            if len(tensors) != self.num_features or any(t.numel() != tensors[0].shape[0] for t in tensors):
+                return False
+        tensors += [self.meta_embeddings, self.feature_temperatures] + list(self.bucket_projectors.parameters())
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            return False
+        return ops.autodis_supported(self.num_buckets, self.embedding_dim)
+
+    def forward_native(self, x: torch.Tensor):
+        """forward's result from the dense values as ONE [B, F] tensor (any row stride: a column slice of a wider matrix
+        is read in place): one launch for all fields; the list entries are views of the flat output."""
+        proj = [t for seq in self.bucket_projectors for t in (seq[0].weight, seq[0].bias, seq[2].weight, seq[2].bias)]
+        flat = ops.autodis(x, self.meta_embeddings, proj, self.feature_temperatures, self._native_cache)
+        D = self.embedding_dim
+        return flat, [flat[:, i * D:(i + 1) * D].unsqueeze(1) for i in range(self.num_features)]
 
     def get_bucket_indices(self, dense_values: List[torch.Tensor]) -> List[torch.Tensor]:
         out = []
@@ -388,8 +421,12 @@ class xDeepFMPro(BaseModelSFG):
             dnn_input = dnn_in
             if self.use_autodis and self.autodis_encoder is not None and plan.nd > 0:
                 mD = plan.m * plan.D
-                dense_list = [dnn_in[:, mD + k:mD + k + 1] for k in range(plan.nd)]
-                autodis_out, _, _ = self.autodis_encoder(dense_list)
+                ad = self.autodis_encoder.autodis
+                if ad is not None and ad._native(dnn_in[:, mD:]):
+                    autodis_out, _ = ad.forward_native(dnn_in[:, mD:])      # the dense columns in place, one launch
+                else:
+                    dense_list = [dnn_in[:, mD + k:mD + k + 1] for k in range(plan.nd)]
+                    autodis_out, _, _ = self.autodis_encoder(dense_list)
                 dnn_input = torch.cat([dnn_in[:, :mD], autodis_out], dim=-1)
             logit = logit + self.dnn_linear(self.dnn(dnn_input))
         y_pred = self.out(logit)
