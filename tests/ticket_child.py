@@ -1,0 +1,101 @@
+"""The fixed list of cases behind test_gpu_head_reg.py::test_ticketed_finishes_match_two_launch_path_bit_for_bit.
+
+run_cases(dev) runs every kernel family that has a ticketed finish twice in a row and returns all outputs as numpy
+arrays, plus the ticket board (when one is registered) read after every family.  As a program (python ticket_child.py
+OUT.npz, started by the test with XDFM_TICKETS=1 in a fresh process) it registers the board first and writes the arrays
+to OUT.npz; imported by the test, the same function runs on the two-launch path.  The board is registered once per
+process and changes every later launch, which is why the ticketed half never runs inside the pytest process."""
+import os
+import sys
+
+import numpy as np
+
+if __name__ == "__main__":          # as a program: the paths conftest.py sets for the tests (its own directory is there already)
+    _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for _p in (_ROOT, os.path.join(_ROOT, "xdeepfm-pytorch_amd")):
+        if _p not in sys.path:
+            sys.path.insert(0, _p)
+
+import head_reg_drivers as D  # noqa: E402
+import head_reg_ref as R  # noqa: E402
+
+HEAD = ["c1111", "c0000", "k3_k4_b16", "k512_k200_b2048", "k516_k64_b2049", "k64_k4_b65536"]     # both kernels each way
+COLSUM = [(1000, 429), (4099, 63), (16, 65600)]                                                   # 65600: no ticket
+TRAIN_STEPS = 6                # 2 eager steps, the capture, 3 replays
+
+
+def _board(out, tag):
+    import torch
+    from xdfm_amd import _lib
+    torch.cuda.synchronize()
+    if 0 in _lib._BOARDS:
+        out["board/" + tag] = _lib._BOARDS[0].cpu().numpy().copy()
+
+
+def _train(dev, out):
+    import torch
+    from deepctr.inputs import DenseFeat, SparseFeat
+    from deepctr.models import xDeepFM
+    from oracle import xdeepfm_oracle as orc
+    vocab, nd, D = [50, 31, 77, 12, 9, 40], 3, 8
+    cols = [SparseFeat("C%d" % (i + 1), v, D) for i, v in enumerate(vocab)] + [DenseFeat("I%d" % (i + 1), 1) for i in range(nd)]
+    torch.manual_seed(1234)
+    model = xDeepFM(cols, cols, dnn_hidden_units=(32, 16), cin_layer_size=(16, 8), l2_reg_dnn=1e-4, l2_reg_embedding=1e-4,
+                    device=dev)
+    model.compile("adam", "binary_crossentropy", metrics=[])
+    model.train()
+    for s in range(TRAIN_STEPS):
+        X, y = orc.synthetic_batch(256, vocab, nd, seed=300 + s)
+        res = model.train_on_batch(torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev))
+        out["train/step%d_pred" % s] = res[0].detach().cpu().numpy().copy()
+        out["train/step%d_loss" % s] = res[1].detach().cpu().numpy().copy()
+        out["train/step%d_total" % s] = res[2].detach().cpu().numpy().copy()
+        _board(out, "train_step%d" % s)
+    for k, v in model.state_dict().items():
+        out["train/final_" + k] = v.detach().cpu().numpy().copy()
+    return model.__dict__["_graphed_step"].replays
+
+
+def run_cases(dev):
+    from xdfm_amd import _lib
+    out = {}
+    for name in HEAD:
+        c = R.make_head_case(name)
+        for rep in (0, 1):
+            for k, v in D.run_head(c, dev).items():
+                out["head/%s/%d/%s" % (name, rep, k)] = v
+        if c["lin"] is None:                                  # the backward of a case ops.Head cannot differentiate
+            g, db = D.head_g_aux(out["head/%s/1/pred" % name], c["y"], c["gloss"], dev)
+            out["head/%s/aux_g" % name], out["head/%s/aux_dbias" % name] = g, np.array(db)
+        _board(out, "head_" + name)
+    for rows, cols in COLSUM:
+        for relu in (False, True):
+            g, y = R.make_colsum_case(rows, cols, relu)
+            for rep, r in enumerate(D.run_colsum(g, y, cols, dev)):
+                tag = "colsum%s/%dx%d/%d" % ("_relu" if relu else "", rows, cols, rep)
+                out[tag + "/out"] = r["out"]
+                out[tag + "/guards"] = np.array(int(r["guards"]))
+                if relu:
+                    out[tag + "/gz"] = r["gz"]
+            _board(out, "colsum%s_%dx%d" % ("_relu" if relu else "", rows, cols))
+    out["meta/replays"] = np.array(_train(dev, out))
+    _board(out, "end")
+    out["meta/board_registered"] = np.array(int(0 in _lib._BOARDS))
+    return out
+
+
+def main(path):
+    import torch
+    from xdfm_amd import _lib
+    assert os.environ.get("XDFM_TICKETS") == "1", "start this program with XDFM_TICKETS=1"
+    dev = torch.device("cuda:0")
+    _lib.ticket_board(dev)                 # before the first launch: the head op does not pass through ops._need_cuda
+    assert 0 in _lib._BOARDS, "no ticket board was registered"
+    out = run_cases(dev)
+    np.savez(path, **out)
+    print("ticket_child: %d arrays, %d board readings, %d graph replays" % (
+        len(out), sum(k.startswith("board/") for k in out), int(out["meta/replays"])))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])

@@ -191,7 +191,8 @@ def ticket_board(device):
     work of the separate "finish" launches (include/xdfm.h, xdfm_set_ticket_board).  Measured on MI355X (round 3): the
     captured step shrinks from 48 to 40 nodes and gets SLOWER, 2.05 against 1.97 ms -- a block that draws a ticket first
     waits for its own stores, the device-scope atomic is a ~2 us round trip, and the finishing block's acquire invalidates
-    its XCD's L2 under the blocks still running (the fused dOut pass: 44 -> 83 us).  Off by default; the tests run both."""
+    its XCD's L2 under the blocks still running (the fused dOut pass: 44 -> 83 us).  Off by default; the tests run both
+    (tests/test_gpu_head_reg.py::test_ticketed_finishes_match_two_launch_path_bit_for_bit, the board in a child process)."""
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx in _BOARDS or os.environ.get("XDFM_TICKETS", "0") != "1":
         return
