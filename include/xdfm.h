@@ -41,6 +41,7 @@
  * ABI 8 additions (no existing struct or signature changed): xdfm_opt_tensor, xdfm_opt_step_ws_elems, xdfm_sgd_step,
  * xdfm_adagrad_step (K7s / K7g: the streaming sweep for the trainer's two other optimizers); xdfm_opt_clock, xdfm_opt_rows,
  * xdfm_sgd_step_deferred, xdfm_adagrad_step_deferred, xdfm_opt_catchup_rows, xdfm_opt_flush (K7sd / K7gd: their deferred form);
+ * xdfm_rmsprop_step, xdfm_rmsprop_step_deferred, xdfm_rmsprop_catchup_rows, xdfm_rmsprop_flush (K7r / K7rd: RMSprop);
  * xdfm_autodis_supported, xdfm_autodis_ws_elems, xdfm_autodis_fwd, xdfm_autodis_bwd (K10: AutoDis of xdeepfm_pro).
  */
 #ifndef XDFM_H
@@ -437,7 +438,7 @@ int xdfm_adam_step_lr(const xdfm_adam_tensor* tensors, int T, double lr, const d
 typedef struct {
     float* param;
     float* grad;
-    float* state;                   /* Adagrad: the accumulator ("sum"); SGD: NULL */
+    float* state;                   /* Adagrad: the accumulator ("sum"); RMSprop: "square_avg"; SGD: NULL */
     long numel;
     float l2;
     unsigned char* grad_marks;      /* NULL: grad is read in full and left alone */
@@ -447,6 +448,16 @@ int xdfm_sgd_step(const xdfm_opt_tensor* tensors, int T, double lr, const double
                   void* stream);
 int xdfm_adagrad_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps, float* l2_ws,
                       float* l2_value, void* stream);
+/* RMSprop (K7r) -- replaces: torch.optim.RMSprop(params).step(), the fourth string of basemodel.py:447-461 -- for
+ * momentum 0, not centered, no weight decay: the same sweep, descriptors (`state` is the accumulator "square_avg"), rate,
+ * L2 term and marks, 16 bytes per parameter, in ATen's order (torch/optim/rmsprop.py):
+ *   g' = fma(2 l2, p, g);   v = fma(1 - alpha, g' g', alpha v);   p = fma(-lr, g' / (sqrt(v) + eps), p)
+ * with alpha and 1 - alpha (taken in double) rounded to float.  v decays in every step whatever the gradient, so the exact
+ * shortcut of K7s / K7g does not apply: an unmarked chunk of a tensor with l2 == 0 is computed with g = 0 like any other
+ * (its p keeps its bits, its v becomes alpha v).  Marks on / off give the same bits.  Errors (as above; eps <= 0, alpha
+ * outside [0, 1), a tensor without `state`) are reported before any device work. */
+int xdfm_rmsprop_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double alpha, double eps,
+                      float* l2_ws, float* l2_value, void* stream);
 
 /* ------------------------------------------------------------------ deferred Adam for the tables (K7d)
  * Same arithmetic, same results, bit for bit, as the dense sweep above -- but the sweep's 24 bytes per table parameter
@@ -551,6 +562,17 @@ int xdfm_opt_catchup_rows(int adagrad, const float* X, long ldx, int B, const in
  * clock[0] = 0, every `last` byte 0). */
 int xdfm_opt_flush(int adagrad, const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                    double eps, void* stream);
+/* K7rd: the same three for RMSprop (the signatures above carry no alpha).  An untouched row with l2 > 0 evolves by
+ * g' = 2 l2 p, v = fma(1 - alpha, g' g', alpha v), p = fma(-lr_t, g' / (sqrt(v) + eps), p); clock, `last` bytes, backlog and
+ * cell are those of K7sd / K7gd, and so are the errors (plus alpha outside [0, 1)). */
+int xdfm_rmsprop_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
+                               double lr, const double* lr_dev, double alpha, double eps, float* l2_ws, float* l2_value,
+                               void* stream);
+int xdfm_rmsprop_catchup_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
+                              const xdfm_opt_rows* emb, const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double alpha,
+                              double eps, void* stream);
+int xdfm_rmsprop_flush(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double alpha,
+                       double eps, void* stream);
 
 /* Test hook: compares the replay's short forms (csrc/adam_math.h) with the reference spellings ON THE DEVICE.
  * mode 0: square root, n = 2^32 bit patterns; 1: division by a step's constant, n = steps * 2^24 numerators; 2: general

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the train step with `compile("sgd")` / `compile("adagrad")` (K7s / K7g: native sweep, fused L2 term, marked
-gradients, graph replay) against the stock path the same strings took before (a torch.optim.SGD / Adagrad OBJECT handed
+"""A/B of the train step with `compile("sgd")` / `compile("adagrad")` / `compile("rmsprop")` (K7s / K7g / K7r: native sweep,
+fused L2 term, marked gradients, graph replay) against the stock path the same strings took before (a torch.optim.SGD /
+Adagrad / RMSprop OBJECT handed
 to compile: eager launches, K6 value pass, table-sized L2 gradients, zero-filled dense table gradients).
 
 BASELINE config 2's model (bench.py criteo_c2), B = 4096, at the mid (1e5 rows per field) and the Criteo-card
@@ -9,12 +10,12 @@ synchronise, after a warm-up that goes past the graph capture.  Prints one table
 ms/step of both paths, their ratio, the sweep kernel's bytes per second by the byte model of DESIGN.md (K7s / K7g),
 and launches per step (graph nodes for the replayed step; kernels seen by torch.profiler for the eager one).
 
-A third arm, `deferred`, is the native step with the deferred (exact) table update (K7sd / K7gd, `deferred=True`) beside
+A third arm, `deferred`, is the native step with the deferred (exact) table update (K7sd / K7gd / K7rd, `deferred=True`) beside
 the native sweep (`deferred=False`).  Its timed blocks end with a flush inside the timed region, and a block is longer than
 the flush period, so every deferred update is paid for inside the time reported.  For that arm the tool also prints the
 flush (ms per flush, and amortised over the period) and the catch-up launch (us), from HIP events around them.
 
-    python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad] [--arms sweep,deferred,stock]
+    python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad,rmsprop] [--arms sweep,deferred,stock]
                                 [--out FILE.json]
 """
 import argparse
@@ -39,13 +40,14 @@ def build(cfg, vocab, dev, optimizer, stock, deferred=False):
     cols += [DenseFeat("I%d" % (i + 1), 1) for i in range(cfg["n_dense"])]
     model = xDeepFM(cols, cols, dnn_hidden_units=cfg["dnn"], cin_layer_size=cfg["cin"], l2_reg_dnn=1e-5, device=dev)
     if stock:
-        opt = torch.optim.SGD(model.parameters(), lr=0.01) if optimizer == "sgd" else torch.optim.Adagrad(model.parameters())
+        opt = {"sgd": lambda p: torch.optim.SGD(p, lr=0.01), "adagrad": torch.optim.Adagrad,
+               "rmsprop": torch.optim.RMSprop}[optimizer](model.parameters())
         model.compile(opt, "binary_crossentropy", metrics=[])
     else:
         model.compile(optimizer, "binary_crossentropy", metrics=[])
         model.optim.deferred = bool(deferred)
     for pg in model.optim.param_groups:          # a rate at which a sum-reduced loss over 4096 rows stays finite
-        pg["lr"] = 1e-5 if optimizer == "sgd" else 1e-3
+        pg["lr"] = {"sgd": 1e-5, "adagrad": 1e-3, "rmsprop": 1e-4}[optimizer]
     model.train()
     return model
 
@@ -127,7 +129,7 @@ def main():
     ap.add_argument("--block", type=int, default=128, help="steps per alternating block (longer than the flush period)")
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--vocab", default="mid,criteo-card")
-    ap.add_argument("--optimizers", default="sgd,adagrad")
+    ap.add_argument("--optimizers", default="sgd,adagrad,rmsprop")
     ap.add_argument("--arms", default="sweep,deferred,stock")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()

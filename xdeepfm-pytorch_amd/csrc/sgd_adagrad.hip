@@ -1,6 +1,7 @@
-// K7s / K7g: SGD (momentum 0) and Adagrad (lr_decay 0) steps over all parameters -- the streaming sweep of K7
-// (adam.hip) for the two other optimizers the trainer offers (xdftrain.py:723 --optimizer adam|adagrad|sgd,
-// deepctr/models/basemodel.py:447-461).  One kernel template, two instances.
+// K7s / K7g / K7r: SGD (momentum 0), Adagrad (lr_decay 0) and RMSprop (momentum 0, not centered) steps over all
+// parameters -- the streaming sweep of K7 (adam.hip) for the other optimizers the trainer offers (xdftrain.py:723
+// --optimizer adam|adagrad|sgd; "rmsprop" is the fourth string of deepctr/models/basemodel.py:447-461).  One kernel
+// template, three instances.
 //
 // replaces torch.optim.SGD.step() / torch.optim.Adagrad.step() plus the passes the stock path needs around them
 // (zero fill of the dense table gradients, value and gradient of the L2 term).  Per parameter and step the sweep
@@ -14,6 +15,9 @@
 //   g' = fma(2 l2, p, g)
 //   SGD:      p = fma(-lr, g', p)
 //   Adagrad:  s = s + g' g';   p = fma(-lr, g' / (sqrt(s) + eps), p)        IEEE sqrt and division
+//   RMSprop:  v = fma(1 - alpha, g' g', alpha v);   p = fma(-lr, g' / (sqrt(v) + eps), p)   (torch/optim/rmsprop.py: mul_(alpha),
+//             addcmul_(g, g, 1 - alpha), sqrt().add_(eps), addcdiv_).  v decays in EVERY step, so for RMSprop an unmarked chunk of
+//             a tensor without an L2 term is no no-op: it is computed like any other (16 bytes per parameter), g' = 0 leaves p's bits.
 // Descriptors by value in the kernel arguments, a 1-D grid shared out by tensor size, the learning rate as an argument
 // or from one device double, per-block L2 partials summed in a fixed order by a finish kernel: all as K7.
 #include "xdfm_internal.h"
@@ -32,13 +36,14 @@ struct OptBatch { OptDev t[OPT_CHUNK]; int first[OPT_CHUNK + 1]; };
 static_assert(sizeof(OptBatch) + 128 <= 4096, "the optimizer kernels' argument block");
 
 // chunks per array and thread in flight: SGD streams one array, Adagrad two -- eight 16-byte loads per thread either way
-template <bool ADA> struct OptFlight { static constexpr int N = ADA ? 4 : 8; };
+template <int K> struct OptFlight { static constexpr int N = K != OPT_SGD ? 4 : 8; };
 
-template <bool ADA>
+template <int K>
 __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch batch, int cnt, int slot0, double lr_arg,
-                                                               const double* __restrict__ lr_dev, float eps,
+                                                               const double* __restrict__ lr_dev, const OptHyper hyp,
                                                                float* __restrict__ l2_part) {
-    constexpr int NF = OptFlight<ADA>::N;
+    constexpr int NF = OptFlight<K>::N;
+    constexpr bool ADA = K != OPT_SGD;                 // an accumulator is streamed beside p
     // the learning rate as a kernel argument, or read from device memory (a captured HIP graph follows a schedule)
     const double lr = lr_dev ? *lr_dev : lr_arg;
     const float nlr = -(float)lr;
@@ -68,15 +73,16 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
     const float4 zero4 = make_float4(zf, zf, zf, zf);
     const unsigned tx = threadIdx.x, tx16 = tx * 16u;
     long i = tid;
-    if (marks && l2c == 0.f) {
+    if (marks && l2c == 0.f && K != OPT_RMSPROP) {
         // No L2 term: an unmarked chunk has g' == 0 -- p and the accumulator keep their bits, so the chunk is not read
-        // at all.  The scan reads the mark bytes 16 at a time (one uint4 per lane and load), two groups per thread in
+        // at all.  (Not RMSprop: its accumulator decays to alpha * v whatever the gradient, so every chunk is a real update
+        // and takes the branch below -- with g' == 0 that update leaves the bits of p as they are.)  The scan reads the mark bytes 16 at a time (one uint4 per lane and load), two groups per thread in
         // flight; the chunks in front of the marks' first 16-byte boundary and behind the last whole group go one by one.
         auto process = [&](long e) {
             float4 pa = p4[e], sa = ADA ? s4[e] : zero4;
             const float4 ga = g4[e];
             g4[e] = zero4; marks[e] = 0;
-            opt_four<ADA>(pa, sa, ga, g2, nlr, eps, sq);
+            opt_four<K>(pa, sa, ga, g2, nlr, hyp, sq);
             p4[e] = pa;
             if constexpr (ADA) s4[e] = sa;
         };
@@ -132,7 +138,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
             }
 #pragma unroll
             for (int q = 0; q < NF; ++q) {
-                opt_four<ADA>(P[q], S[q], G[q], g2, nlr, eps, sq);
+                opt_four<K>(P[q], S[q], G[q], g2, nlr, hyp, sq);
                 opt_st(opt_at4(p4 + (iu + q * stride), tx16), P[q]);
                 if constexpr (ADA) opt_st(opt_at4(s4 + (iu + q * stride), tx16), S[q]);
             }
@@ -143,7 +149,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
             float4 pa = opt_ld(p4 + i), sa = ADA ? opt_ld(s4 + i) : zero4;
             float4 ga = zero4;
             if (ka) { ga = g4[i]; g4[i] = zero4; marks[i] = 0; }
-            opt_four<ADA>(pa, sa, ga, g2, nlr, eps, sq);
+            opt_four<K>(pa, sa, ga, g2, nlr, hyp, sq);
             opt_st(p4 + i, pa);
             if constexpr (ADA) opt_st(s4 + i, sa);
         }
@@ -159,7 +165,7 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
         }
 #pragma unroll
         for (int q = 0; q < NF; ++q) {
-            opt_four<ADA>(P[q], S[q], G[q], g2, nlr, eps, sq);
+            opt_four<K>(P[q], S[q], G[q], g2, nlr, hyp, sq);
             opt_st(opt_at4(p4 + (iu + q * stride), tx16), P[q]);
             if constexpr (ADA) opt_st(opt_at4(s4 + (iu + q * stride), tx16), S[q]);
         }
@@ -168,13 +174,13 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
     for (; i < n4; i += stride) {
         float4 pa = opt_ld(p4 + i), sa = ADA ? opt_ld(s4 + i) : zero4;
         const float4 ga = opt_ld(g4 + i);
-        opt_four<ADA>(pa, sa, ga, g2, nlr, eps, sq);
+        opt_four<K>(pa, sa, ga, g2, nlr, hyp, sq);
         opt_st(p4 + i, pa);
         if constexpr (ADA) opt_st(s4 + i, sa);
     }
     for (long k = 4 * n4 + tid; k < n; k += stride) {  // the numel % 4 tail (always read); whole unaligned tensors
         float pa = p[k], sa = ADA ? s[k] : zf;
-        opt_one<ADA>(pa, sa, g[k], g2, nlr, eps, sq);
+        opt_one<K>(pa, sa, g[k], g2, nlr, hyp, sq);
         p[k] = pa;
         if constexpr (ADA) s[k] = sa;
         if (marks) { g[k] = 0.f; marks[k >> 2] = 0; }
@@ -202,12 +208,14 @@ __global__ __launch_bounds__(1024) void opt_l2_finish_kernel(const float* __rest
     if (threadIdx.x == 0) out[0] = acc[0];
 }
 
-template <bool ADA>
+template <int K>
 static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
-                         float* l2_ws, float* l2_value, void* stream) {
+                         double alpha, float* l2_ws, float* l2_value, void* stream) {
+    constexpr bool ADA = K != OPT_SGD;
     XDFM_REQUIRE(tensors, "%s: null pointer", what);
     XDFM_REQUIRE(T > 0 && T <= 65535, "%s: bad tensor count %d", what, T);
     XDFM_REQUIRE(lr >= 0 && (!ADA || eps > 0), "%s: bad hyper-parameters", what);
+    XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "%s: bad hyper-parameters (alpha %g is outside [0, 1))", what, alpha);
     XDFM_REQUIRE(!l2_value || l2_ws, "%s: l2_value needs l2_ws", what);
     for (int t = 0; t < T; ++t)
         XDFM_REQUIRE(tensors[t].param && tensors[t].grad && tensors[t].numel >= 0 && tensors[t].l2 >= 0,
@@ -240,8 +248,8 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
             if (nb > OPT_BX) nb = OPT_BX;
             batch.first[k + 1] = batch.first[k] + (int)nb;
         }
-        hipLaunchKernelGGL(opt_step_kernel<ADA>, dim3(batch.first[cnt]), dim3(OPT_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev,
-                           (float)eps, l2_value ? l2_ws : nullptr);
+        hipLaunchKernelGGL(opt_step_kernel<K>, dim3(batch.first[cnt]), dim3(OPT_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev,
+                           opt_hyper(K, eps, alpha), l2_value ? l2_ws : nullptr);
         slot0 += batch.first[cnt];
     }
     if (l2_value) hipLaunchKernelGGL(opt_l2_finish_kernel, dim3(1), dim3(1024), 0, st, l2_ws, slot0, l2_value);
@@ -249,10 +257,11 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
 }
 
 // the sweep over the tensors the deferred step (sgd_adagrad_deferred.hip) does not defer: the same launches as below
-int xdfm_opt_step_dense(bool ada, const char* what, const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
-                        float* l2_ws, float* l2_value, void* stream) {
-    return ada ? opt_step_impl<true>(what, tensors, T, lr, lr_dev, eps, l2_ws, l2_value, stream)
-               : opt_step_impl<false>(what, tensors, T, lr, lr_dev, 0.0, l2_ws, l2_value, stream);
+int xdfm_opt_step_dense(int kind, const char* what, const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
+                        double alpha, float* l2_ws, float* l2_value, void* stream) {
+    return kind == OPT_RMSPROP   ? opt_step_impl<OPT_RMSPROP>(what, tensors, T, lr, lr_dev, eps, alpha, l2_ws, l2_value, stream)
+           : kind == OPT_ADAGRAD ? opt_step_impl<OPT_ADAGRAD>(what, tensors, T, lr, lr_dev, eps, 0.0, l2_ws, l2_value, stream)
+                                 : opt_step_impl<OPT_SGD>(what, tensors, T, lr, lr_dev, 0.0, 0.0, l2_ws, l2_value, stream);
 }
 
 extern "C" {
@@ -261,12 +270,17 @@ size_t xdfm_opt_step_ws_elems(int T) { return T > 0 ? (size_t)T * OPT_BX : 0; }
 
 int xdfm_sgd_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, float* l2_ws, float* l2_value,
                   void* stream) {
-    return opt_step_impl<false>("sgd_step", tensors, T, lr, lr_dev, 0.0, l2_ws, l2_value, stream);
+    return opt_step_impl<OPT_SGD>("sgd_step", tensors, T, lr, lr_dev, 0.0, 0.0, l2_ws, l2_value, stream);
 }
 
 int xdfm_adagrad_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps, float* l2_ws,
                       float* l2_value, void* stream) {
-    return opt_step_impl<true>("adagrad_step", tensors, T, lr, lr_dev, eps, l2_ws, l2_value, stream);
+    return opt_step_impl<OPT_ADAGRAD>("adagrad_step", tensors, T, lr, lr_dev, eps, 0.0, l2_ws, l2_value, stream);
+}
+
+int xdfm_rmsprop_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double alpha, double eps,
+                      float* l2_ws, float* l2_value, void* stream) {
+    return opt_step_impl<OPT_RMSPROP>("rmsprop_step", tensors, T, lr, lr_dev, eps, alpha, l2_ws, l2_value, stream);
 }
 
 }  // extern "C"

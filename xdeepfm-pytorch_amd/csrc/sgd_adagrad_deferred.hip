@@ -76,11 +76,12 @@ __device__ __forceinline__ int opt_wave_min(int v) {
 // ---------------------------------------------------------------------------------------------
 // the step: a scan of the mark bytes of the deferred tensors
 // ---------------------------------------------------------------------------------------------
-template <bool ADA>
+template <int K>
 __global__ __launch_bounds__(OPTD_THREADS) void opt_step_deferred_kernel(const OptDefBatch batch, int cnt, const int* __restrict__ clock,
-                                                                         const float* __restrict__ rates, float eps,
+                                                                         const float* __restrict__ rates, const OptHyper hyp,
                                                                          unsigned long long* __restrict__ backlog,
                                                                          unsigned long long* __restrict__ cell) {
+    constexpr bool ADA = K != OPT_SGD;                 // an accumulator goes with p
     int ti = 0;                                        // wave-uniform search
     for (int k = 1; k < cnt; ++k) ti += (int)blockIdx.x >= batch.first[k] ? 1 : 0;
     const int lb = (int)blockIdx.x - batch.first[ti];
@@ -112,8 +113,8 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_step_deferred_kernel(const O
         const float4 ga = g4[e];
         g4[e] = zero4; marks[e] = 0;
         for (int st = (int)last[e] + 1; st < t; ++st)   // steps the catch-up did not bring (rows no gather announced)
-            opt_four<ADA>(pa, sa, zero4, g2, rates[st], eps, sqr);
-        opt_four<ADA>(pa, sa, ga, g2, nlr, eps, sq);
+            opt_four<K>(pa, sa, zero4, g2, rates[st], hyp, sqr);
+        opt_four<K>(pa, sa, ga, g2, nlr, hyp, sq);
         p4[e] = pa;
         if constexpr (ADA) s4[e] = sa;
         last[e] = (unsigned char)t;
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_step_deferred_kernel(const O
     }
     for (long k = 4 * n4 + tid; k < n; k += stride) {  // the numel % 4 tail: updated densely in every step, like the sweep does
         float pa = p[k], sa = ADA ? s[k] : zf;
-        opt_one<ADA>(pa, sa, g[k], g2, nlr, eps, sq);
+        opt_one<K>(pa, sa, g[k], g2, nlr, hyp, sq);
         p[k] = pa;
         if constexpr (ADA) s[k] = sa;
         g[k] = 0.f; marks[k >> 2] = 0;
@@ -163,11 +164,12 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_step_deferred_kernel(const O
 // ---------------------------------------------------------------------------------------------
 struct OptRowsDev { float* const* p; float* const* s; unsigned char* const* last; const float* l2; };
 
-template <bool ADA>
+template <int K>
 __global__ __launch_bounds__(OPTD_THREADS) void opt_catchup_rows_kernel(
     const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
-    OptRowsDev emb, OptRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ rates, float eps,
+    OptRowsDev emb, OptRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ rates, const OptHyper hyp,
     unsigned long long* __restrict__ backlog) {
+    constexpr bool ADA = K != OPT_SGD;
     const int t = clock[0];
     const int QE = (D + 3) / 4 + ((D & 3) ? 1 : 0);     // chunks a row of D floats can straddle
     const int QT = QE + (has_lin ? 1 : 0);
@@ -229,7 +231,7 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_catchup_rows_kernel(
         const float nlr = rates[st];
         float4 pn = pa, sn = sa;
         float sqn = sqr;
-        opt_four<ADA>(pn, sn, zero4, g2, nlr, eps, sqn);
+        opt_four<K>(pn, sn, zero4, g2, nlr, hyp, sqn);
         if (act && st > old) { pa = pn; sa = sn; sqr = sqn; }       // a select, not a branch around the arithmetic
     }
     if (act) { *p4 = pa; if constexpr (ADA) *s4 = sa; }
@@ -243,13 +245,14 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_catchup_rows_kernel(
 // division deep), so a thread carries several chunks = 4 * N independent chains through the steps.  The step is computed
 // for every chunk and taken by a select (a chunk that is ahead, or a lane behind the end, keeps its registers): a branch
 // per chunk would put the chunks of a thread one after the other again.
-template <bool ADA> struct OptFlushFlight { static constexpr int N = ADA ? 2 : 4; };
+template <int K> struct OptFlushFlight { static constexpr int N = K != OPT_SGD ? 2 : 4; };
 
-template <bool ADA>
+template <int K>
 __global__ __launch_bounds__(OPTD_THREADS) void opt_flush_kernel(const OptDefBatch batch, int cnt, const int* __restrict__ clock,
-                                                                 const float* __restrict__ rates, float eps,
+                                                                 const float* __restrict__ rates, const OptHyper hyp,
                                                                  unsigned long long* __restrict__ backlog) {
-    constexpr int NF = OptFlushFlight<ADA>::N;
+    constexpr int NF = OptFlushFlight<K>::N;
+    constexpr bool ADA = K != OPT_SGD;
     int ti = 0;
     for (int k = 1; k < cnt; ++k) ti += (int)blockIdx.x >= batch.first[k] ? 1 : 0;
     const int lb = (int)blockIdx.x - batch.first[ti];
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_flush_kernel(const OptDefBat
             for (int q = 0; q < NF; ++q) {
                 float4 pn = P[q], sn = S[q];
                 float sqn = sqr[q];
-                opt_four<ADA>(pn, sn, zero4, g2, nlr, eps, sqn);
+                opt_four<K>(pn, sn, zero4, g2, nlr, hyp, sqn);
                 const bool take = act[q] && st > old[q];
                 P[q].x = take ? pn.x : P[q].x; P[q].y = take ? pn.y : P[q].y; P[q].z = take ? pn.z : P[q].z; P[q].w = take ? pn.w : P[q].w;
                 if constexpr (ADA) { S[q].x = take ? sn.x : S[q].x; S[q].y = take ? sn.y : S[q].y; S[q].z = take ? sn.z : S[q].z; S[q].w = take ? sn.w : S[q].w; }
@@ -341,14 +344,16 @@ static void opt_def_grid(OptDefBatch& batch, int cnt, int bx) {
     }
 }
 
-template <bool ADA>
+template <int K>
 static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tensors, unsigned char* const* last, int T,
-                                  const xdfm_opt_clock* clk, double lr, const double* lr_dev, double eps, float* l2_ws,
+                                  const xdfm_opt_clock* clk, double lr, const double* lr_dev, double eps, double alpha, float* l2_ws,
                                   float* l2_value, void* stream) {
+    constexpr bool ADA = K != OPT_SGD;
     XDFM_REQUIRE(tensors && last, "%s: null pointer", what);
     XDFM_REQUIRE(T > 0 && T <= 65535, "%s: bad tensor count %d", what, T);
     if (int rc = opt_clock_ok(what, clk)) return rc;
     XDFM_REQUIRE(lr >= 0 && (!ADA || eps > 0), "%s: bad hyper-parameters", what);
+    XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "%s: bad hyper-parameters (alpha %g is outside [0, 1))", what, alpha);
     XDFM_REQUIRE(!l2_value || l2_ws, "%s: l2_value needs l2_ws", what);
     for (int t = 0; t < T; ++t)
         XDFM_REQUIRE(tensors[t].param && tensors[t].grad && tensors[t].numel >= 0 && tensors[t].l2 >= 0,
@@ -371,7 +376,7 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
     }
     hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, st, clk->clock, clk->rates, clk->cap, lr, lr_dev);
     if (!dense.empty()) {                               // stepped exactly as xdfm_sgd_step / xdfm_adagrad_step step them
-        if (int rc = xdfm_opt_step_dense(ADA, what, dense.data(), (int)dense.size(), lr, lr_dev, eps, l2_ws, l2_value, stream)) return rc;
+        if (int rc = xdfm_opt_step_dense(K, what, dense.data(), (int)dense.size(), lr, lr_dev, eps, alpha, l2_ws, l2_value, stream)) return rc;
     }
     const int n = (int)def.size();
     for (int l0 = 0; l0 < n; l0 += OPTD_CHUNK) {
@@ -379,20 +384,22 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
         const int cnt = n - l0 < OPTD_CHUNK ? n - l0 : OPTD_CHUNK;
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[def[l0 + k]], last[def[l0 + k]]);
         opt_def_grid(batch, cnt, OPTD_BX);
-        hipLaunchKernelGGL(opt_step_deferred_kernel<ADA>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock,
-                           clk->rates, (float)eps, clk->backlog, clk->cell);
+        hipLaunchKernelGGL(opt_step_deferred_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock,
+                           clk->rates, opt_hyper(K, eps, alpha), clk->backlog, clk->cell);
     }
     hipLaunchKernelGGL(opt_l2_cell_finish_kernel, dim3(1), dim3(64), 0, st, clk->cell, l2_value, dense.empty() ? 0 : 1);
     return xdfm_check_launch(what);
 }
 
-template <bool ADA>
+template <int K>
 static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double eps,
-                          void* stream) {
+                          double alpha, void* stream) {
+    constexpr bool ADA = K != OPT_SGD;
     XDFM_REQUIRE(tensors && last, "opt_flush: null pointer");
     XDFM_REQUIRE(T > 0 && T <= 65535, "opt_flush: bad tensor count %d", T);
     if (int rc = opt_clock_ok("opt_flush", clk)) return rc;
     XDFM_REQUIRE(!ADA || eps > 0, "opt_flush: bad hyper-parameters");
+    XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "opt_flush: bad hyper-parameters (alpha %g is outside [0, 1))", alpha);
     for (int t = 0; t < T; ++t) {
         XDFM_REQUIRE(tensors[t].param && tensors[t].numel >= 0 && tensors[t].l2 >= 0,
                      "opt_flush: tensor %d has a null pointer, a negative size or a negative l2", t);
@@ -407,54 +414,82 @@ static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* 
         const int cnt = T - l0 < OPTD_CHUNK ? T - l0 : OPTD_CHUNK;
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[l0 + k], last[l0 + k]);
         opt_def_grid(batch, cnt, OPTD_FLUSH_BX);
-        hipLaunchKernelGGL(opt_flush_kernel<ADA>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock, clk->rates,
-                           (float)eps, clk->backlog);
+        hipLaunchKernelGGL(opt_flush_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock, clk->rates,
+                           opt_hyper(K, eps, alpha), clk->backlog);
     }
     hipLaunchKernelGGL(opt_clock_reset_kernel, dim3(1), dim3(64), 0, st, clk->clock);
     return xdfm_check_launch("opt_flush");
 }
 
-template <bool ADA>
+template <int K>
 static int opt_catchup_impl(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D, const xdfm_opt_rows* emb,
-                            const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps, void* stream) {
+                            const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps, double alpha, void* stream) {
     const OptRowsDev e = {emb->param, emb->state, emb->last, emb->l2};
     const OptRowsDev l = lin ? OptRowsDev{lin->param, lin->state, lin->last, lin->l2} : e;
     const int QT = (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);
     const long threads = (long)B * m * QT;
-    hipLaunchKernelGGL(opt_catchup_rows_kernel<ADA>, dim3((unsigned)ceil_div(threads, (long)OPTD_THREADS)), dim3(OPTD_THREADS), 0,
-                       (hipStream_t)stream, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0, clk->clock, clk->rates, (float)eps,
-                       clk->backlog);
+    hipLaunchKernelGGL(opt_catchup_rows_kernel<K>, dim3((unsigned)ceil_div(threads, (long)OPTD_THREADS)), dim3(OPTD_THREADS), 0,
+                       (hipStream_t)stream, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0, clk->clock, clk->rates,
+                       opt_hyper(K, eps, alpha), clk->backlog);
     return xdfm_check_launch("opt_catchup_rows");
+}
+
+// what xdfm_opt_catchup_rows and xdfm_rmsprop_catchup_rows check before any device work
+static int opt_catchup_ok(int kind, const float* X, int B, const int* cols, const int* vocab, int m, int D, const xdfm_opt_rows* emb,
+                          const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps, double alpha) {
+    XDFM_REQUIRE(X && cols && vocab && emb, "opt_catchup_rows: null pointer");
+    if (int rc = opt_clock_ok("opt_catchup_rows", clk)) return rc;
+    XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "opt_catchup_rows: bad shape B=%d m=%d D=%d", B, m, D);
+    XDFM_REQUIRE(emb->param && emb->last && emb->l2 && (!lin || (lin->param && lin->last && lin->l2)),
+                 "opt_catchup_rows: a row table is missing");
+    XDFM_REQUIRE(kind != OPT_ADAGRAD || (eps > 0 && emb->state && (!lin || lin->state)), "opt_catchup_rows: Adagrad needs state and eps > 0");
+    XDFM_REQUIRE(kind != OPT_RMSPROP || (eps > 0 && emb->state && (!lin || lin->state)), "opt_catchup_rows: RMSprop needs state and eps > 0");
+    XDFM_REQUIRE(kind != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "opt_catchup_rows: bad hyper-parameters (alpha %g is outside [0, 1))", alpha);
+    return XDFM_OK;
 }
 
 extern "C" {
 
 int xdfm_sgd_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                            double lr, const double* lr_dev, float* l2_ws, float* l2_value, void* stream) {
-    return opt_step_deferred_impl<false>("sgd_step_deferred", tensors, last, T, clk, lr, lr_dev, 0.0, l2_ws, l2_value, stream);
+    return opt_step_deferred_impl<OPT_SGD>("sgd_step_deferred", tensors, last, T, clk, lr, lr_dev, 0.0, 0.0, l2_ws, l2_value, stream);
 }
 
 int xdfm_adagrad_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                                double lr, const double* lr_dev, double eps, float* l2_ws, float* l2_value, void* stream) {
-    return opt_step_deferred_impl<true>("adagrad_step_deferred", tensors, last, T, clk, lr, lr_dev, eps, l2_ws, l2_value, stream);
+    return opt_step_deferred_impl<OPT_ADAGRAD>("adagrad_step_deferred", tensors, last, T, clk, lr, lr_dev, eps, 0.0, l2_ws, l2_value, stream);
+}
+
+int xdfm_rmsprop_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
+                               double lr, const double* lr_dev, double alpha, double eps, float* l2_ws, float* l2_value,
+                               void* stream) {
+    return opt_step_deferred_impl<OPT_RMSPROP>("rmsprop_step_deferred", tensors, last, T, clk, lr, lr_dev, eps, alpha, l2_ws, l2_value, stream);
 }
 
 int xdfm_opt_catchup_rows(int adagrad, const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
                           const xdfm_opt_rows* emb, const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps,
                           void* stream) {
-    XDFM_REQUIRE(X && cols && vocab && emb, "opt_catchup_rows: null pointer");
-    if (int rc = opt_clock_ok("opt_catchup_rows", clk)) return rc;
-    XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "opt_catchup_rows: bad shape B=%d m=%d D=%d", B, m, D);
-    XDFM_REQUIRE(emb->param && emb->last && emb->l2 && (!lin || (lin->param && lin->last && lin->l2)),
-                 "opt_catchup_rows: a row table is missing");
-    XDFM_REQUIRE(!adagrad || (eps > 0 && emb->state && (!lin || lin->state)), "opt_catchup_rows: Adagrad needs state and eps > 0");
-    return adagrad ? opt_catchup_impl<true>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, eps, stream)
-                   : opt_catchup_impl<false>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, 0.0, stream);
+    if (int rc = opt_catchup_ok(adagrad ? OPT_ADAGRAD : OPT_SGD, X, B, cols, vocab, m, D, emb, lin, clk, eps, 0.0)) return rc;
+    return adagrad ? opt_catchup_impl<OPT_ADAGRAD>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, eps, 0.0, stream)
+                   : opt_catchup_impl<OPT_SGD>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, 0.0, 0.0, stream);
+}
+
+int xdfm_rmsprop_catchup_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
+                              const xdfm_opt_rows* emb, const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double alpha,
+                              double eps, void* stream) {
+    if (int rc = opt_catchup_ok(OPT_RMSPROP, X, B, cols, vocab, m, D, emb, lin, clk, eps, alpha)) return rc;
+    return opt_catchup_impl<OPT_RMSPROP>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, eps, alpha, stream);
 }
 
 int xdfm_opt_flush(int adagrad, const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                    double eps, void* stream) {
-    return adagrad ? opt_flush_impl<true>(tensors, last, T, clk, eps, stream) : opt_flush_impl<false>(tensors, last, T, clk, 0.0, stream);
+    return adagrad ? opt_flush_impl<OPT_ADAGRAD>(tensors, last, T, clk, eps, 0.0, stream)
+                   : opt_flush_impl<OPT_SGD>(tensors, last, T, clk, 0.0, 0.0, stream);
+}
+
+int xdfm_rmsprop_flush(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double alpha,
+                       double eps, void* stream) {
+    return opt_flush_impl<OPT_RMSPROP>(tensors, last, T, clk, eps, alpha, stream);
 }
 
 }  // extern "C"

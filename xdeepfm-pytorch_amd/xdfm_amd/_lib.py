@@ -83,6 +83,10 @@ SIGNATURES = {
     "xdfm_adagrad_step_deferred": (c_int, [P, P, c_int, P, c_double, P, c_double, P, P, P]),
     "xdfm_opt_catchup_rows": (c_int, [c_int, P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, P]),
     "xdfm_opt_flush": (c_int, [c_int, P, P, c_int, P, c_double, P]),
+    "xdfm_rmsprop_step": (c_int, [P, c_int, c_double, P, c_double, c_double, P, P, P]),
+    "xdfm_rmsprop_step_deferred": (c_int, [P, P, c_int, P, c_double, P, c_double, c_double, P, P, P]),
+    "xdfm_rmsprop_catchup_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, c_double, P]),
+    "xdfm_rmsprop_flush": (c_int, [P, P, c_int, P, c_double, c_double, P]),
     "xdfm_vocab_lse_update": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_softmax_grad": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_ce_x3_supported": (c_int, [c_int]),
@@ -118,13 +122,13 @@ class AdamTensor(ctypes.Structure):
 
 
 class OptTensor(ctypes.Structure):
-    """xdfm_opt_tensor of include/xdfm.h (SGD / Adagrad; `state` is Adagrad's accumulator)"""
+    """xdfm_opt_tensor of include/xdfm.h (SGD / Adagrad / RMSprop; `state` is the accumulator of the latter two)"""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("state", c_void_p), ("numel", c_long), ("l2", ctypes.c_float),
                 ("grad_marks", c_void_p)]
 
 
 class OptClock(ctypes.Structure):
-    """xdfm_opt_clock of include/xdfm.h (deferred SGD / Adagrad)"""
+    """xdfm_opt_clock of include/xdfm.h (deferred SGD / Adagrad / RMSprop)"""
     _fields_ = [("clock", c_void_p), ("rates", c_void_p), ("cap", c_int), ("backlog", c_void_p), ("cell", c_void_p)]
 
 

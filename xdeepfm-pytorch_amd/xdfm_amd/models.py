@@ -311,7 +311,7 @@ class BaseModel(nn.Module):
 
     def _l2_fusion(self):
         """(tensors, strengths) of the whole L2 term when the optimizer applies it itself while it streams the
-        weights (xdfm_amd.optim.TableAdam / TableSGD / TableAdagrad: K7, K7s, K7g), else None.  Only the model's own
+        weights (xdfm_amd.optim.TableAdam / TableSGD / TableAdagrad / TableRMSprop: K7, K7s, K7g, K7r), else None.  Only the model's own
         train step uses this."""
         opt = getattr(self, "optim", None)
         if not getattr(opt, "table_step", False):
@@ -549,7 +549,7 @@ class BaseModel(nn.Module):
         self._optim_capturable = False
         self._flush_optim()                # a previous optimizer may still owe table rows their latest steps
         self.optim = self._get_optim(optimizer)
-        # the table optimizers (optim.TableAdam / TableSGD / TableAdagrad), also when handed in as an object, e.g.
+        # the table optimizers (optim.TableAdam / TableSGD / TableAdagrad / TableRMSprop), also when handed in as an object, e.g.
         # TableAdam(..., lazy_rows=True); an object of a stock torch class keeps the stock path
         if getattr(self.optim, "table_step", False):
             self._optim_capturable = all(p.is_cuda for g in self.optim.param_groups for p in g["params"])
@@ -570,7 +570,7 @@ class BaseModel(nn.Module):
                 return TableAdam(params)
             return torch.optim.Adam(params)
         def native(table_cls, stock):
-            # SGD / Adagrad through K7s / K7g on a GPU (xdfm_amd.optim); on the CPU the stock class, as the reference
+            # SGD / Adagrad / RMSprop through K7s / K7g / K7r on a GPU (xdfm_amd.optim); on the CPU the stock class, as the reference
             def make(params):
                 params = list(params)
                 if len(params) > 0 and all(p.is_cuda for p in params):
@@ -579,7 +579,8 @@ class BaseModel(nn.Module):
                 return stock(params)
             return make
         table = {"sgd": native("TableSGD", lambda p: torch.optim.SGD(p, lr=0.01)), "adam": adam,
-                 "adagrad": native("TableAdagrad", torch.optim.Adagrad), "rmsprop": torch.optim.RMSprop}
+                 "adagrad": native("TableAdagrad", torch.optim.Adagrad),
+                 "rmsprop": native("TableRMSprop", torch.optim.RMSprop)}
         if optimizer not in table:
             raise NotImplementedError
         return table[optimizer](self.parameters())

@@ -14,10 +14,11 @@ passes over the parameters (basemodel.py:412-428) from the step.
 Gradients that are views of a kept gradient buffer (`ops.GradArena`, registered through `grad_sources`) are read by
 their chunk marks: K7 skips the untouched rows of the dense table gradients and re-zeroes the touched ones.
 
-`TableSGD` and `TableAdagrad` (K7s / K7g, `xdfm_sgd_step` / `xdfm_adagrad_step`) give the trainer's two other optimizers
-(`--optimizer sgd|adagrad`, basemodel.py:447-461) the same sweep, armed L2 term, marked gradients and device-resident
-learning rate; their state layout is that of torch.optim.SGD / torch.optim.Adagrad.  Tables with an L2 term may take the
-deferred (exact) form of those steps (K7sd / K7gd, `xdfm_sgd_step_deferred` / `xdfm_adagrad_step_deferred`), as TableAdam's do."""
+`TableSGD`, `TableAdagrad` and `TableRMSprop` (K7s / K7g / K7r, `xdfm_sgd_step` / `xdfm_adagrad_step` / `xdfm_rmsprop_step`)
+give the other optimizer strings of basemodel.py:447-461 (`--optimizer sgd|adagrad|rmsprop`) the same sweep, armed L2 term,
+marked gradients and device-resident learning rate; their state layout is that of torch.optim.SGD / Adagrad / RMSprop.
+Tables with an L2 term may take the deferred (exact) form of those steps (K7sd / K7gd / K7rd, `xdfm_sgd_step_deferred` /
+`xdfm_adagrad_step_deferred` / `xdfm_rmsprop_step_deferred`), as TableAdam's do."""
 import ctypes
 import os
 
@@ -475,11 +476,11 @@ class TableAdam(torch.optim.Adam):
 
 
 class _TableStep(object):
-    """What `TableSGD` and `TableAdagrad` share, and what the model's train step duck-types on (`table_step`): `arm_l2`,
+    """What `TableSGD`, `TableAdagrad` and `TableRMSprop` share, and what the model's train step duck-types on (`table_step`): `arm_l2`,
     `owns`, `l2_value`, `grad_sources`, `sync_lr`, `generation`, `note_replay`.  A mixin in front of the stock class;
     TableAdam keeps its own copies (its deferred update threads through all of them)."""
     table_step = True
-    _KERNEL = None               # "sgd" / "adagrad"
+    _KERNEL = None               # "sgd" / "adagrad" / "rmsprop"
 
     def _table_init(self, deferred=None, flush_every=64):
         # Deferred (exact) update of the tables, include/xdfm.h "K7sd / K7gd": same bits as the dense sweep, but a row with
@@ -630,11 +631,14 @@ class _TableStep(object):
         if e_struct is None:
             return                                      # tables this optimizer does not update by deferral
         cols, vocab, _, _ = plan.on(X.device)
-        ada = self._KERNEL == "adagrad"
-        _lib.check(_lib.load().xdfm_opt_catchup_rows(
-            1 if ada else 0, X.data_ptr(), X.stride(0), X.shape[0], cols.data_ptr(), vocab.data_ptr(), plan.m, plan.D,
-            ctypes.byref(e_struct), ctypes.byref(l_struct) if l_struct is not None else None, ctypes.byref(d["clk"]),
-            float(d["eps"] or 0.0), torch.cuda.current_stream(X.device).cuda_stream), "opt_catchup_rows")
+        head = (X.data_ptr(), X.stride(0), X.shape[0], cols.data_ptr(), vocab.data_ptr(), plan.m, plan.D, ctypes.byref(e_struct),
+                ctypes.byref(l_struct) if l_struct is not None else None, ctypes.byref(d["clk"]))
+        stream = torch.cuda.current_stream(X.device).cuda_stream
+        if self._KERNEL == "rmsprop":                   # d["eps"]: (alpha, eps) of the steps the replays stand for
+            rc = _lib.load().xdfm_rmsprop_catchup_rows(*(head + (float(d["eps"][0]), float(d["eps"][1]), stream)))
+        else:
+            rc = _lib.load().xdfm_opt_catchup_rows(1 if self._KERNEL == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
+        _lib.check(rc, "opt_catchup_rows")
 
     @torch.no_grad()
     def flush(self):
@@ -652,10 +656,13 @@ class _TableStep(object):
                 arr[k].param, arr[k].numel, arr[k].l2 = ptr, numel, l2
                 arr[k].state = state.data_ptr() if state is not None else None
                 last[k] = lb.data_ptr()
-            dev = d["clock"].device
-            _lib.check(_lib.load().xdfm_opt_flush(1 if self._KERNEL == "adagrad" else 0, ctypes.cast(arr, ctypes.c_void_p),
-                                                  ctypes.cast(last, ctypes.c_void_p), len(ent), ctypes.byref(d["clk"]),
-                                                  float(d["eps"] or 0.0), torch.cuda.current_stream(dev).cuda_stream), "opt_flush")
+            stream = torch.cuda.current_stream(d["clock"].device).cuda_stream
+            head = (ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(last, ctypes.c_void_p), len(ent), ctypes.byref(d["clk"]))
+            if self._KERNEL == "rmsprop":
+                rc = _lib.load().xdfm_rmsprop_flush(*(head + (float(d["eps"][0]), float(d["eps"][1]), stream)))
+            else:
+                rc = _lib.load().xdfm_opt_flush(1 if self._KERNEL == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
+            _lib.check(rc, "opt_flush")
         self._since = 0
 
     def take_backlog(self):
@@ -736,6 +743,9 @@ class _TableStep(object):
     def _state_of(self, group, p):              # (accumulator or None, host step counter or None)
         raise NotImplementedError
 
+    def _hyper(self, group):                    # what the replays of a deferred step assume beside the rate: a change flushes
+        return None
+
     def _native(self):
         """True when every group can take the kernel: plain hyper-parameters, dense contiguous fp32 CUDA tensors."""
         if getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
@@ -766,7 +776,7 @@ class _TableStep(object):
         lib = _lib.load()
         from . import ops                              # per-kernel timing hook of bench.py
         from . import dist as xdist
-        ada = self._KERNEL == "adagrad"
+        kind = self._KERNEL
         capturing = torch.cuda.is_current_stream_capturing()
         host_steps = []
         for gi, group in enumerate(self.param_groups):
@@ -834,12 +844,12 @@ class _TableStep(object):
                     deferred_now = []
                 else:
                     want = {params[k].data_ptr(): (states[k][0], float(l2[k]), params[k].numel()) for k in deferred_now}
-                    eps = float(group["eps"]) if ada else None
+                    eps = self._hyper(group)
                     same = d["eps"] == eps and len(want) == len(d["tensors"]) and all(
                         ptr in d["tensors"] and d["tensors"][ptr][0] is w[0] and d["tensors"][ptr][2] == w[1]
                         for ptr, w in want.items())
                     if not same:
-                        # the set of deferred tables, an L2 strength or eps changed: the replays assumed the old ones
+                        # the set of deferred tables, an L2 strength, eps or alpha changed: the replays assumed the old ones
                         if capturing:                  # (the `last` bytes are allocated and zeroed by an eager step)
                             raise RuntimeError("xdfm %s: the deferred tables changed inside a HIP-graph capture" % type(self).__name__)
                         self.flush()
@@ -853,9 +863,10 @@ class _TableStep(object):
                         last_arr[k] = d["tensors"][params[k].data_ptr()][1].data_ptr()
             nbytes = 0.0
             for k in range(T):
-                per = 16.0 if ada else 8.0             # the byte model of DESIGN.md (K7s / K7g)
+                per = 8.0 if kind == "sgd" else 16.0   # the byte model of DESIGN.md (K7s / K7g / K7r)
                 if arr[k].grad_marks:
-                    skip = arr[k].l2 == 0.0 or (last_arr is not None and last_arr[k])
+                    # (RMSprop's accumulator decays in every step: no shortcut for a tensor without an L2 term)
+                    skip = (arr[k].l2 == 0.0 and kind != "rmsprop") or (last_arr is not None and last_arr[k])
                     nbytes += params[k].numel() * (0.0625 if skip else per + 0.0625)
                 else:
                     nbytes += params[k].numel() * (per + 4.0)
@@ -869,7 +880,11 @@ class _TableStep(object):
             ws_ptr, val_ptr = (ws.data_ptr(), val.data_ptr()) if val is not None else (None, None)
             if last_arr is not None:
                 lasts, clk = ctypes.cast(last_arr, ctypes.c_void_p), ctypes.byref(d["clk"])
-                if ada:
+                if kind == "rmsprop":
+                    launch = lambda: lib.xdfm_rmsprop_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
+                                                                    float(group["lr"]), lr_ptr, float(group["alpha"]),
+                                                                    float(group["eps"]), ws_ptr, val_ptr, stream)
+                elif kind == "adagrad":
                     launch = lambda: lib.xdfm_adagrad_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
                                                                     float(group["lr"]), lr_ptr, float(group["eps"]), ws_ptr,
                                                                     val_ptr, stream)
@@ -879,7 +894,10 @@ class _TableStep(object):
                 self.path_counts["scan"] += 1
                 if not capturing:
                     self._since += 1
-            elif ada:
+            elif kind == "rmsprop":
+                launch = lambda: lib.xdfm_rmsprop_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
+                                                       float(group["alpha"]), float(group["eps"]), ws_ptr, val_ptr, stream)
+            elif kind == "adagrad":
                 launch = lambda: lib.xdfm_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                        float(group["eps"]), ws_ptr, val_ptr, stream)
             else:
@@ -938,3 +956,42 @@ class TableAdagrad(_TableStep, torch.optim.Adagrad):
         if not (acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous()):
             raise RuntimeError("xdfm TableAdagrad: the accumulator of a CUDA parameter must be a contiguous fp32 CUDA tensor")
         return acc, st["step"]
+
+    def _hyper(self, group):
+        return float(group["eps"])
+
+
+class TableRMSprop(_TableStep, torch.optim.RMSprop):
+    """torch.optim.RMSprop whose step is K7r (`xdfm_rmsprop_step`) for momentum 0, not centered (the reference's
+    `compile("rmsprop")`: lr 0.01, alpha 0.99, eps 1e-8); tables with an L2 term may take its deferred form (K7rd).  State is
+    torch's: `square_avg` per parameter and a host-resident `step` counter, which the update does not read but which counts
+    every step, replayed ones included (`note_replay`); it is created by the first eager step, as the stock class creates
+    it, never inside a capture.  Momentum, centered, weight decay, maximize, capturable, foreach, differentiable, tensor
+    learning rates, eps == 0, alpha == 1, sparse / non-fp32 / non-CUDA tensors and closures fall back to
+    torch.optim.RMSprop.step with the armed L2 term applied by hand."""
+    _KERNEL = "rmsprop"
+
+    def __init__(self, params, lr=0.01, alpha=0.99, eps=1e-8, weight_decay=0, momentum=0, centered=False, capturable=False,
+                 foreach=None, maximize=False, differentiable=False, *, deferred=None, flush_every=64):
+        super().__init__(params, lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=momentum, centered=centered,
+                         capturable=capturable, foreach=foreach, maximize=maximize, differentiable=differentiable)
+        self._table_init(deferred, flush_every)
+
+    def _plain(self, group):
+        return (group["momentum"] == 0 and not group["centered"] and not group["capturable"] and group["foreach"] is None and
+                isinstance(group["alpha"], float) and 0.0 <= group["alpha"] < 1.0 and group["eps"] > 0)
+
+    def _state_of(self, group, p):
+        st = self.state[p]
+        if len(st) == 0:                        # torch.optim.RMSprop._init_group's layout for these hyper-parameters
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("xdfm TableRMSprop: the state is created by an eager step, not inside a HIP-graph capture")
+            st["step"] = torch.zeros((), dtype=torch.float64 if torch.get_default_dtype() == torch.float64 else torch.float32)
+            st["square_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        acc = st["square_avg"]
+        if not (acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous()):
+            raise RuntimeError("xdfm TableRMSprop: the accumulator of a CUDA parameter must be a contiguous fp32 CUDA tensor")
+        return acc, st["step"]
+
+    def _hyper(self, group):
+        return (float(group["alpha"]), float(group["eps"]))

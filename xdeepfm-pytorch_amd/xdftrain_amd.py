@@ -79,7 +79,7 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--l2_reg_dnn", type=float, default=1e-5)
     p.add_argument("--dnn_dropout", type=float, default=0.0)
     p.add_argument("--learning_rate", type=float, default=0.001)
-    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adagrad", "sgd"])
+    p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adagrad", "sgd", "rmsprop"])
     p.add_argument("--epochs", type=int, default=None)
     p.add_argument("--batch_size", type=int, default=None)
     p.add_argument("--pred_batch_size", type=int, default=None)
