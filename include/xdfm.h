@@ -43,6 +43,10 @@
  * xdfm_sgd_step_deferred, xdfm_adagrad_step_deferred, xdfm_opt_catchup_rows, xdfm_opt_flush (K7sd / K7gd: their deferred form);
  * xdfm_rmsprop_step, xdfm_rmsprop_step_deferred, xdfm_rmsprop_catchup_rows, xdfm_rmsprop_flush (K7r / K7rd: RMSprop);
  * xdfm_autodis_supported, xdfm_autodis_ws_elems, xdfm_autodis_fwd, xdfm_autodis_bwd (K10: AutoDis of xdeepfm_pro).
+ * Further ABI 8 additions (no existing struct or signature changed, so the version stays: a caller built against the earlier
+ * ABI 8 header keeps working, and the binding checks every symbol it needs by name): xdfm_embed_gather_fwd_ld (K1 with a row pitch and a dense-column
+ * offset for dnn_in), xdfm_varlen_field, xdfm_varlen_pool_fwd, xdfm_varlen_pool_bwd_ws_elems, xdfm_varlen_pool_bwd
+ * (K1v / K2v: pooled variable-length fields).
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -134,6 +138,67 @@ int xdfm_embed_gather_fwd(const float* X, long ldx, int B,
                           const int* dense_cols, const float* dense_w, int nd,
                           float* emb_fm, float* dnn_in, float* lin_out,
                           int* err_flag, void* stream);
+
+/* Same, with the layout of dnn_in given by the caller: rows of ld_dnn floats, the m*D embedding columns first, the nd dense
+ * columns from column dense_off on (dense_off >= m*D, ld_dnn >= dense_off + nd).  The columns in between are left alone:
+ * xdfm_varlen_pool_fwd fills them with the pooled variable-length fields, and emb_fm may then have more than m field
+ * slots.  ld_dnn = m*D + nd, dense_off = m*D is xdfm_embed_gather_fwd. */
+int xdfm_embed_gather_fwd_ld(const float* X, long ldx, int B,
+                             const float* const* tables, const float* const* lin_tables,
+                             const int* cols, const int* vocab, int m, int D,
+                             const int* dense_cols, const float* dense_w, int nd,
+                             float* emb_fm, float* dnn_in, long ld_dnn, int dense_off, float* lin_out,
+                             int* err_flag, void* stream);
+
+/* ------------------------------------------------------------------ pooled variable-length fields (K1v / K2v, csrc/varlen.hip)
+ * replaces: varlen_embedding_lookup + get_varlen_pooling_list (deepctr/inputs.py:141-155, :213-227) with
+ *           SequencePoolingLayer (deepctr/layers/sequence.py:49-77) for every VarLenSparseFeat, in input_from_feature_columns
+ *           (deepctr/models/basemodel.py:372-377) and in Linear.forward (:72-77), and their autograd.
+ * Field f reads maxlen ids from the columns col .. col + maxlen - 1 of X (fp32, truncated as Tensor.long()).  Position t is
+ * valid when id != 0 (len_col < 0) or when t < long(X[b][len_col]).  With w_t the table row of position t:
+ *   XDFM_POOL_SUM   sum of the valid w_t;
+ *   XDFM_POOL_MEAN  that sum / (float(count of valid positions, or the length column's value) + 1e-8f);
+ *   XDFM_POOL_MAX   max over ALL t of (valid ? w_t : w_t - 1e9f) -- an empty sequence pools to the reference's value, not to 0.
+ * The [B, maxlen, D] rows exist in registers only.  Every position is looked up, padded ones too, as the reference does: an id
+ * outside [0, vocab) is clamped and raises err_flag (as K1).  1 <= maxlen <= 255. */
+enum { XDFM_POOL_SUM = 0, XDFM_POOL_MEAN = 1, XDFM_POOL_MAX = 2 };
+typedef struct {
+    const float* table;   /* [vocab][D]; may be NULL in a call without emb_fm and dnn_in */
+    const float* lin;     /* [vocab][1]; may be NULL in a call without lin_out */
+    int col;              /* first id column of X */
+    int maxlen;
+    int len_col;          /* column of X that holds the length, or -1: mask = id != 0 */
+    int combiner;         /* XDFM_POOL_* */
+    int vocab;
+    int reserved;
+} xdfm_varlen_field;
+/* ONE launch for all F fields.  fields: device array; fields_host: the same F descriptors in host memory (shapes are
+ * checked against ldx before anything is launched; the pointers in it are not dereferenced).
+ * emb_fm  FM layout [>= slot0 + F][B*D] or NULL: field f is written to slot slot0 + f (the sparse fields of K1 come first);
+ * dnn_in  [B][ld_dnn] or NULL: field f is written to columns dnn_off + f*D .. of every row;
+ * lin_out [B] or NULL: the pooled [vocab][1] rows of all fields are ADDED to it (K1 has written it before);
+ * argpos  [B][F][D + 1] bytes or NULL: position of the first maximum per (example, field, column), column D being the linear
+ *         table's -- what xdfm_varlen_pool_bwd needs for XDFM_POOL_MAX fields (0 for the other combiners). */
+int xdfm_varlen_pool_fwd(const float* X, long ldx, int B, const xdfm_varlen_field* fields,
+                         const xdfm_varlen_field* fields_host, int F, int D, int slot0,
+                         float* emb_fm, float* dnn_in, long ld_dnn, int dnn_off, float* lin_out,
+                         unsigned char* argpos, int* err_flag, void* stream);
+/* Backward: dense [vocab][D] and [vocab][1] gradients, no float atomics, bit-identical from run to run.  An expand kernel
+ * writes one row gradient per position for B * Tmax pseudo-examples (Tmax = largest maxlen; g for sum, g / (len + 1e-8f) for
+ * mean, g at the recorded position for max, zeros at masked and padded positions), then K2's exact segmented reduce
+ * (xdfm_embed_scatter_bwd_marked) adds them to d_flat in chunks of 4096 pseudo-examples, in ascending order.
+ * d_emb_fm / d_dnn_in / d_lin: the gradients of the three outputs of the forward (same layouts; each may be NULL; ld_lin = row
+ * stride of d_lin, 0 = 1); the pooled row's gradient is d_emb_fm + d_dnn_in (one fp32 add).
+ * d_flat: caller-initialised (zeros) gradient buffer, 16-byte aligned; table f's gradient starts at d_flat + tab_off[f], its
+ * linear table's at d_flat + lin_off[f] (device long[F]; either array may be NULL: those gradients are not computed).
+ * cols: device int[F] = 0 .. F-1;  vocab: device int[F];  ws: xdfm_varlen_pool_bwd_ws_elems floats. */
+size_t xdfm_varlen_pool_bwd_ws_elems(long B, int F, int D, int Tmax);
+int xdfm_varlen_pool_bwd(const float* X, long ldx, int B, const xdfm_varlen_field* fields,
+                         const xdfm_varlen_field* fields_host, int F, int D, int slot0,
+                         const float* d_emb_fm, const float* d_dnn_in, long ld_dnn, int dnn_off,
+                         const float* d_lin, long ld_lin, const unsigned char* argpos,
+                         const int* cols, const int* vocab, float* d_flat, const long* tab_off, const long* lin_off,
+                         float* ws, void* stream);
 
 /* ------------------------------------------------------------------ embedding scatter (K2)
  * replaces: autograd of the above (aten::embedding_dense_backward x52, sparse=False,

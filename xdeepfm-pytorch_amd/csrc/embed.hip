@@ -23,7 +23,8 @@ __global__ __launch_bounds__(EMB_THREADS) void embed_gather_kernel(
     const float* __restrict__ X, long ldx, int B, const float* const* __restrict__ tables,
     const float* const* __restrict__ lin_tables, const int* __restrict__ cols, const int* __restrict__ vocab,
     int m, int D, const int* __restrict__ dense_cols, const float* __restrict__ dense_w, int nd, int EB,
-    float* __restrict__ emb_fm, float* __restrict__ dnn_in, float* __restrict__ lin_out, int* __restrict__ err_flag) {
+    float* __restrict__ emb_fm, float* __restrict__ dnn_in, long ldd, int dense_off, float* __restrict__ lin_out,
+    int* __restrict__ err_flag) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* tile = smem;                                                    // [EB][m][D]
     float* linv = smem + (size_t)EB * m * D;                               // [EB][m]
@@ -127,13 +128,12 @@ __global__ __launch_bounds__(EMB_THREADS) void embed_gather_kernel(
 
     // phase 2a: dnn_in rows (sparse part is the tile verbatim, dense part from the staged values)
     if (dnn_in) {
-        const int ldd = m * D + nd;
         const int per = m * D;
         for (int bl = 0; bl < nb; ++bl) {
             float* drow = dnn_in + (long)(b0 + bl) * ldd;
             const float* trow = tile + (size_t)bl * per;
             for (int k = tid; k < per; k += EMB_THREADS) drow[k] = trow[k];
-            for (int k = tid; k < nd; k += EMB_THREADS) drow[per + k] = densev[bl * nd + k];
+            for (int k = tid; k < nd; k += EMB_THREADS) drow[dense_off + k] = densev[bl * nd + k];
         }
     }
     // phase 2b: FM layout, field-major: for field j the nb*D floats of this block are contiguous
@@ -654,11 +654,21 @@ int xdfm_embed_gather_fwd(const float* X, long ldx, int B, const float* const* t
                           const float* const* lin_tables, const int* cols, const int* vocab, int m, int D,
                           const int* dense_cols, const float* dense_w, int nd, float* emb_fm, float* dnn_in,
                           float* lin_out, int* err_flag, void* stream) {
+    return xdfm_embed_gather_fwd_ld(X, ldx, B, tables, lin_tables, cols, vocab, m, D, dense_cols, dense_w, nd, emb_fm, dnn_in,
+                                    (long)m * D + nd, m * D, lin_out, err_flag, stream);
+}
+
+int xdfm_embed_gather_fwd_ld(const float* X, long ldx, int B, const float* const* tables,
+                             const float* const* lin_tables, const int* cols, const int* vocab, int m, int D,
+                             const int* dense_cols, const float* dense_w, int nd, float* emb_fm, float* dnn_in,
+                             long ld_dnn, int dense_off, float* lin_out, int* err_flag, void* stream) {
     XDFM_REQUIRE(X && tables && cols && vocab && emb_fm, "embed_gather_fwd: null pointer");
     XDFM_REQUIRE(B > 0 && m > 0 && D > 0 && nd >= 0 && ldx >= m + nd, "embed_gather_fwd: bad shape B=%d m=%d D=%d nd=%d ldx=%ld",
                  B, m, D, nd, ldx);
     XDFM_REQUIRE(nd == 0 || dense_cols, "embed_gather_fwd: dense_cols missing");
     XDFM_REQUIRE(!(lin_out && nd > 0) || dense_w, "embed_gather_fwd: dense_w missing");
+    XDFM_REQUIRE(!dnn_in || (dense_off >= (long)m * D && ld_dnn >= (long)dense_off + nd),
+                 "embed_gather_fwd: bad dnn_in layout ld_dnn=%ld dense_off=%d (m*D=%ld, nd=%d)", ld_dnn, dense_off, (long)m * D, nd);
     // examples per block: tile <= 32 KiB, at most 16, at least 1
     int EB = (int)(8192 / ((long)m * D));
     if (EB > 16) EB = 16;
@@ -677,7 +687,7 @@ int xdfm_embed_gather_fwd(const float* X, long ldx, int B, const float* const* t
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCH(V)                                                                                              \
     hipLaunchKernelGGL((embed_gather_kernel<V>), grid, dim3(EMB_THREADS), lds, st, X, ldx, B, tables, lin_tables, \
-                       cols, vocab, m, D, dense_cols, dense_w, nd, EB, emb_fm, dnn_in, lin_out, err_flag)
+                       cols, vocab, m, D, dense_cols, dense_w, nd, EB, emb_fm, dnn_in, ld_dnn, dense_off, lin_out, err_flag)
     if (D % 4 == 0) LAUNCH(4);
     else if (D % 2 == 0) LAUNCH(2);
     else LAUNCH(1);

@@ -26,6 +26,11 @@ SIGNATURES = {
     "xdfm_graph_node_census": (c_int, [P, P, P, P]),
     "xdfm_set_ticket_board": (c_int, [P, c_int]),
     "xdfm_embed_gather_fwd": (c_int, [P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, c_int, P, P, P, P, P]),
+    "xdfm_embed_gather_fwd_ld": (c_int, [P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, c_int, P, P, c_long, c_int, P, P, P]),
+    "xdfm_varlen_pool_fwd": (c_int, [P, c_long, c_int, P, P, c_int, c_int, c_int, P, P, c_long, c_int, P, P, P, P]),
+    "xdfm_varlen_pool_bwd_ws_elems": (c_size_t, [c_long, c_int, c_int, c_int]),
+    "xdfm_varlen_pool_bwd": (c_int, [P, c_long, c_int, P, P, c_int, c_int, c_int, P, P, c_long, c_int, P, c_long, P, P, P, P, P, P,
+                                     P, P]),
     "xdfm_embed_scatter_bwd": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P]),
     "xdfm_embed_scatter_bwd_marked": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, c_int, P, P, c_long, P, c_long,
                                               P, P, P, P, P, P]),
@@ -112,6 +117,12 @@ SIGNATURES = {
 class PackJob(ctypes.Structure):
     """xdfm_cin_pack_job of include/xdfm.h"""
     _fields_ = [("W", c_void_p), ("H", c_int), ("Hp", c_int), ("m", c_int), ("fwd_pack", c_void_p), ("bwd_pack", c_void_p)]
+
+
+class VarLenField(ctypes.Structure):
+    """xdfm_varlen_field of include/xdfm.h"""
+    _fields_ = [("table", c_void_p), ("lin", c_void_p), ("col", c_int), ("maxlen", c_int), ("len_col", c_int), ("combiner", c_int),
+                ("vocab", c_int), ("reserved", c_int)]
 
 
 class AdamTensor(ctypes.Structure):

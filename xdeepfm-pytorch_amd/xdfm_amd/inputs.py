@@ -49,8 +49,9 @@ class DenseFeat(_DenseBase):
 
 
 class VarLenSparseFeat(_VarLenBase):
-    """Descriptor kept for API compatibility; the xDeepFM hot path has no variable-length fields
-    (no config of the reference's scripts creates one) and the models reject it."""
+    """One multi-valued field: `maxlen` id columns of X looked up in one table and pooled (combiner sum / mean / max)
+    into one embedding row; positions are masked by id != 0 or, with `length_name`, by a length column.  xDeepFM,
+    xDeepFMAttention and xDeepFMAttentionV2 take it (one more CIN field per column, pooled by K1v); 1 <= maxlen <= 255."""
     __slots__ = ()
 
     def __new__(cls, sparsefeat, maxlen, combiner="mean", length_name=None):

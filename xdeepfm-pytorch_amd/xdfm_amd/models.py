@@ -57,9 +57,31 @@ def epoch_order(n, shuffle):
 RESIDENT_LIMIT_BYTES = 64 << 30     # keep the packed fp32 input matrix on the device up to this size
 
 
-def _reject_varlen(cols):
-    if any(isinstance(c, VarLenSparseFeat) for c in cols):
-        raise NotImplementedError("VarLenSparseFeat is outside the xDeepFM hot path (no reference script uses it)")
+def _check_varlen(cols):
+    """Limits of the pooled variable-length fields (K1v): refused here, on the host, before anything is built."""
+    sparse, _, varlen = split_columns(cols)
+    if not varlen:
+        return
+    for fc in varlen:
+        if not isinstance(fc.maxlen, (int, np.integer)) or not 1 <= fc.maxlen <= 255:
+            raise ValueError("VarLenSparseFeat %r: maxlen must be an integer in 1..255, got %r" % (fc.name, fc.maxlen))
+        if fc.combiner not in ops.POOL_CODES:
+            raise ValueError("VarLenSparseFeat %r: combiner must be one of sum, mean, max, got %r" % (fc.name, fc.combiner))
+    dims = {fc.embedding_dim for fc in sparse + varlen}
+    if len(dims) > 1:
+        raise ValueError("embedding_dim of SparseFeat and VarlenSparseFeat must be same in this model!")
+    owner = {}
+    for fc in sparse + varlen:
+        # the reference counts CIN fields by tables (len(embedding_dict)) and breaks when two columns share one
+        if owner.setdefault(fc.embedding_name, fc.name) != fc.name:
+            raise ValueError("VarLenSparseFeat: columns %r and %r share embedding_name %r; every column needs a table of its own"
+                             % (owner[fc.embedding_name], fc.name, fc.embedding_name))
+
+
+def _varlen_plan(varlen, feature_index, emb_dim, slot0=0, dnn_off=0):
+    return ops.VarLenPlan([feature_index[fc.name][0] for fc in varlen], [fc.maxlen for fc in varlen],
+                          [None if fc.length_name is None else feature_index[fc.length_name][0] for fc in varlen],
+                          [fc.combiner for fc in varlen], [fc.vocabulary_size for fc in varlen], emb_dim, slot0, dnn_off)
 
 
 class Linear(nn.Module):
@@ -73,7 +95,7 @@ class Linear(nn.Module):
         self.device = device
         self.sparse_feature_columns, self.dense_feature_columns, self.varlen_sparse_feature_columns = \
             split_columns(feature_columns)
-        _reject_varlen(self.varlen_sparse_feature_columns)
+        _check_varlen(feature_columns)
         # All draws happen on the CPU generator and the module moves afterwards, so a seed gives the
         # same initial weights on every device (= the reference's CPU path; on a CUDA device the
         # reference itself would take these two draws from the device generator, basemodel.py:47-61).
@@ -85,15 +107,18 @@ class Linear(nn.Module):
         if n_dense > 0:
             self.weight = nn.Parameter(torch.Tensor(n_dense, 1))
             nn.init.normal_(self.weight, mean=0, std=init_std)
-        self._plan = None
+        self._plan = self._vplan = None
         self.to(device)
 
     def tables(self):
         return [self.embedding_dict[fc.embedding_name].weight for fc in self.sparse_feature_columns]
 
+    def varlen_tables(self):
+        return [self.embedding_dict[fc.embedding_name].weight for fc in self.varlen_sparse_feature_columns]
+
     def __getstate__(self):
         state = self.__dict__.copy()
-        state["_plan"] = None
+        state["_plan"] = state["_vplan"] = None
         return state
 
     def forward(self, X, sparse_feat_refine_weight=None):
@@ -103,6 +128,10 @@ class Linear(nn.Module):
             dense_cols = [c for fc in self.dense_feature_columns for c in range(*self.feature_index[fc.name])]
             self._plan = ops.EmbedPlan([self.feature_index[fc.name][0] for fc in self.sparse_feature_columns],
                                        [fc.vocabulary_size for fc in self.sparse_feature_columns], dense_cols, 1)
+            if self.varlen_sparse_feature_columns:
+                self._vplan = _varlen_plan(self.varlen_sparse_feature_columns, self.feature_index, 1)
+        if self.varlen_sparse_feature_columns and not self.sparse_feature_columns:
+            raise NotImplementedError("the linear part needs at least one SparseFeat beside its VarLenSparseFeat columns")
         if not self.sparse_feature_columns:
             out = torch.zeros([X.shape[0], 1], device=X.device)
             if self.dense_feature_columns:
@@ -112,10 +141,14 @@ class Linear(nn.Module):
         tabs = self.tables()
         w = self.weight if self.dense_feature_columns else None
         _, _, lin = ops.EmbedGather.apply(X, w, self._plan, True, *tabs, *tabs)
+        if self.__dict__.get("_vplan") is not None:        # pooled [V, 1] rows of the variable-length fields, added in place
+            _, _, lin = ops.VarLenPool.apply(X, None, None, lin, self._vplan, 0, *self.varlen_tables())
         return lin
 
 
 class BaseModel(nn.Module):
+    _VARLEN = True      # the model's input stage pools VarLenSparseFeat columns (K1v); xDeepFMPro's does not
+
     def __init__(self, linear_feature_columns, dnn_feature_columns, l2_reg_linear=1e-5, l2_reg_embedding=1e-5,
                  init_std=0.0001, seed=1024, task='binary', device='cpu', gpus=None):
         super().__init__()
@@ -130,7 +163,11 @@ class BaseModel(nn.Module):
         self.reg_loss = torch.zeros((1,), device=device)
         self.aux_loss = torch.zeros((1,), device=device)
         self._aux_unset = True              # aux_loss is still the initial zero: the train step need not add it
-        _reject_varlen(list(linear_feature_columns) + list(dnn_feature_columns))
+        _check_varlen(linear_feature_columns)
+        _check_varlen(dnn_feature_columns)
+        if not self._VARLEN and split_columns(list(linear_feature_columns) + list(dnn_feature_columns))[2]:
+            raise NotImplementedError("%s does not take VarLenSparseFeat columns (xDeepFM, xDeepFMAttention and "
+                                      "xDeepFMAttentionV2 do)" % type(self).__name__)
         self.feature_index = build_input_features(list(linear_feature_columns) + list(dnn_feature_columns))
         self.embedding_dict = create_embedding_matrix(dnn_feature_columns, init_std, sparse=False, device=device)
         self.linear_model = Linear(linear_feature_columns, self.feature_index, device=device)
@@ -148,7 +185,7 @@ class BaseModel(nn.Module):
     # ------------------------------------------------------------------ pickling (ModelCheckpoint with
     # save_weights_only=False calls torch.save(model), deepctr/callbacks.py:41-73)
     _UNPICKLED = ("_graphed_step", "_plan", "_l2_cache", "_unit_grad_cache", "_sparse_cols", "_fused_linear", "_own_step",
-                  "_row_weight")
+                  "_row_weight", "_vplan", "_varlen_cols")
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -182,10 +219,13 @@ class BaseModel(nn.Module):
         self.__dict__.setdefault("_plan", None)
         lm = self.__dict__.get("_modules", {}).get("linear_model")
         if lm is not None:
-            lm._plan = None
+            lm._plan = lm._vplan = None
 
     def _plans(self):
         plans = [self._plan, getattr(self.linear_model, "_plan", None)]
+        if self._plan is not None:
+            plans.append(self.__dict__.get("_vplan"))
+        plans.append(self.linear_model.__dict__.get("_vplan"))
         return [p for p in plans if p is not None]
 
     def _raise_on_bad_ids(self):
@@ -222,19 +262,26 @@ class BaseModel(nn.Module):
     # ------------------------------------------------------------------ fused input stage
     def _gather_plan(self):
         if self._plan is None:
-            sparse, dense, _ = split_columns(self.dnn_feature_columns)
-            dims = {fc.embedding_dim for fc in sparse}
+            sparse, dense, varlen = split_columns(self.dnn_feature_columns)
+            dims = {fc.embedding_dim for fc in sparse + varlen}
             if len(dims) > 1:
                 raise ValueError("embedding_dim of SparseFeat and VarlenSparseFeat must be same in this model!")
+            dp = xdist.current()
+            if dp is not None and (varlen or self.linear_model.varlen_sparse_feature_columns):
+                raise NotImplementedError("row-parallel training does not take VarLenSparseFeat columns")
             lin_sparse = self.linear_model.sparse_feature_columns
             self._fused_linear = [fc.name for fc in lin_sparse] == [fc.name for fc in sparse] and \
-                [fc.name for fc in self.linear_model.dense_feature_columns] == [fc.name for fc in dense]
+                [fc.name for fc in self.linear_model.dense_feature_columns] == [fc.name for fc in dense] and \
+                [fc.name for fc in self.linear_model.varlen_sparse_feature_columns] == [fc.name for fc in varlen]
             dense_cols = [c for fc in dense for c in range(*self.feature_index[fc.name])]
+            D = dims.pop() if dims else 1
+            # the pooled variable-length fields follow the sparse ones: field slots m .. m+F-1 of the CIN input,
+            # columns m*D .. of the DNN input (sparse_embedding_list + varlen_sparse_embedding_list, basemodel.py:377)
             self._plan = ops.EmbedPlan([self.feature_index[fc.name][0] for fc in sparse],
-                                       [fc.vocabulary_size for fc in sparse], dense_cols,
-                                       dims.pop() if dims else 1)
+                                       [fc.vocabulary_size for fc in sparse], dense_cols, D, extra_fields=len(varlen))
+            self._vplan = _varlen_plan(varlen, self.feature_index, D, len(sparse), len(sparse) * D) if varlen else None
             self._sparse_cols = sparse
-            dp = xdist.current()
+            self._varlen_cols = varlen
             if dp is not None and self._fused_linear:
                 # these gradients are built from the all-gathered rows and are identical on every rank
                 self._plan.dp = dp
@@ -244,32 +291,47 @@ class BaseModel(nn.Module):
 
     def fused_inputs(self, X):
         """(emb_fm [m, B*D], dnn_in [B, m*D+nd], linear_logit [B,1]) from ONE gather launch
-        (input_from_feature_columns + linear_model + both concatenations of the reference forward)."""
+        (input_from_feature_columns + linear_model + both concatenations of the reference forward).  With F
+        variable-length columns m counts them too: a second launch pools them into their slots of the same tensors."""
         plan = self._gather_plan()
         self._use_grad_arena(plan)
         if not self._sparse_cols:
             raise NotImplementedError("the xDeepFM path needs at least one SparseFeat")
         tabs = [self.embedding_dict[fc.embedding_name].weight for fc in self._sparse_cols]
+        vplan = self._vplan
+        vtabs = [self.embedding_dict[fc.embedding_name].weight for fc in self._varlen_cols]
         if self._fused_linear:
             w = getattr(self.linear_model, "weight", None)
-            return ops.EmbedGather.apply(X, w, plan, True, *tabs, *self.linear_model.tables())
+            out = ops.EmbedGather.apply(X, w, plan, True, *tabs, *self.linear_model.tables())
+            if vplan is None:
+                return out
+            return ops.VarLenPool.apply(X, out[0], out[1], out[2], vplan, vplan.F, *vtabs, *self.linear_model.varlen_tables())
         emb_fm, dnn_in, _ = ops.EmbedGather.apply(X, None, plan, False, *tabs)
+        if vplan is not None:
+            emb_fm, dnn_in, _ = ops.VarLenPool.apply(X, emb_fm, dnn_in, None, vplan, vplan.F, *vtabs)
         return emb_fm, dnn_in, self.linear_model(X)
 
     def input_from_feature_columns(self, X, feature_columns, embedding_dict, support_dense=True):
-        """API of basemodel.py:354-380: ([B,1,D] per sparse field, [B,k] per dense field)."""
+        """API of basemodel.py:354-380: ([B,1,D] per sparse field, then per pooled variable-length field; [B,k] per
+        dense field)."""
         sparse, dense, varlen = split_columns(feature_columns)
-        _reject_varlen(varlen)
+        _check_varlen(feature_columns)
         if not support_dense and len(dense) > 0:
             raise ValueError("DenseFeat is not supported in dnn_feature_columns")
+        if varlen and not sparse:
+            raise NotImplementedError("the xDeepFM path needs at least one SparseFeat")
         emb_list = []
         if sparse:
             plan = ops.EmbedPlan([self.feature_index[fc.name][0] for fc in sparse],
-                                 [fc.vocabulary_size for fc in sparse], [], sparse[0].embedding_dim)
+                                 [fc.vocabulary_size for fc in sparse], [], sparse[0].embedding_dim, extra_fields=len(varlen))
             tabs = [embedding_dict[fc.embedding_name].weight for fc in sparse]
             emb_fm, _, _ = ops.EmbedGather.apply(X, None, plan, False, *tabs)
+            if varlen:
+                vplan = _varlen_plan(varlen, self.feature_index, plan.D, plan.m, plan.m * plan.D)
+                emb_fm, _, _ = ops.VarLenPool.apply(X, emb_fm, None, None, vplan, vplan.F,
+                                                    *[embedding_dict[fc.embedding_name].weight for fc in varlen])
             B = X.shape[0]
-            emb_list = [emb_fm[j].view(B, 1, plan.D) for j in range(plan.m)]
+            emb_list = [emb_fm[j].view(B, 1, plan.D) for j in range(plan.m + len(varlen))]
         dense_list = [X[:, self.feature_index[fc.name][0]:self.feature_index[fc.name][1]] for fc in dense]
         return emb_list, dense_list
 

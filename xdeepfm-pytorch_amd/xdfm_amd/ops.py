@@ -64,8 +64,10 @@ def activation_code(name) -> int:
 class EmbedPlan:
     """Device-side metadata of one gather: which column of X feeds which table."""
 
-    def __init__(self, sparse_cols: Sequence[int], vocab: Sequence[int], dense_cols: Sequence[int], emb_dim: int):
+    def __init__(self, sparse_cols: Sequence[int], vocab: Sequence[int], dense_cols: Sequence[int], emb_dim: int,
+                 extra_fields: int = 0):
         self.m = len(sparse_cols)
+        self.extra = int(extra_fields)     # field slots behind the sparse ones, filled by VarLenPool (0: K1's own layout)
         self.nd = len(dense_cols)
         self.D = int(emb_dim)
         self.sparse_cols = [int(c) for c in sparse_cols]
@@ -199,8 +201,9 @@ class EmbedGather(torch.autograd.Function):
         X = X.contiguous()
         B = X.shape[0]
         cols, vocab, dcols, flag = plan.on(X.device)
-        emb_fm = torch.empty((m, B * D), dtype=torch.float32, device=X.device)
-        dnn_in = torch.empty((B, m * D + nd), dtype=torch.float32, device=X.device)
+        mx = m + plan.extra                # with pooled variable-length fields behind the sparse ones (VarLenPool fills them)
+        emb_fm = torch.empty((mx, B * D), dtype=torch.float32, device=X.device)
+        dnn_in = torch.empty((B, mx * D + nd), dtype=torch.float32, device=X.device)
         lin = torch.empty((B, 1), dtype=torch.float32, device=X.device)
         plan.last_gather = (X, tuple(emb_tables), tuple(lin_tables))
         if plan.catchup is not None:
@@ -210,10 +213,16 @@ class EmbedGather(torch.autograd.Function):
         dw = dense_w.contiguous() if (dense_w is not None and nd > 0) else None
         # algorithmic bytes: X row + table rows (+ linear rows) + both outputs + logit
         nbytes = B * (4 * (m + nd) + m * (4 * D + (4 if has_lin else 0)) + 4 * m * D + 4 * (m * D + nd) + 4)
-        _lib.check(_run("embed_gather_fwd[bytes]", nbytes, lambda: lib.xdfm_embed_gather_fwd(
-            _ptr(X), X.stride(0), B, _ptr(tp), _ptr(lp), _ptr(cols), _ptr(vocab), m, D,
-            _ptr(dcols) if nd else None, _ptr(dw), nd, _ptr(emb_fm), _ptr(dnn_in), _ptr(lin), _ptr(flag),
-            _stream())), "embed_gather_fwd")
+        if plan.extra == 0:
+            _lib.check(_run("embed_gather_fwd[bytes]", nbytes, lambda: lib.xdfm_embed_gather_fwd(
+                _ptr(X), X.stride(0), B, _ptr(tp), _ptr(lp), _ptr(cols), _ptr(vocab), m, D,
+                _ptr(dcols) if nd else None, _ptr(dw), nd, _ptr(emb_fm), _ptr(dnn_in), _ptr(lin), _ptr(flag),
+                _stream())), "embed_gather_fwd")
+        else:
+            _lib.check(_run("embed_gather_fwd[bytes]", nbytes, lambda: lib.xdfm_embed_gather_fwd_ld(
+                _ptr(X), X.stride(0), B, _ptr(tp), _ptr(lp), _ptr(cols), _ptr(vocab), m, D,
+                _ptr(dcols) if nd else None, _ptr(dw), nd, _ptr(emb_fm), _ptr(dnn_in), mx * D + nd, mx * D, _ptr(lin),
+                _ptr(flag), _stream())), "embed_gather_fwd")
         plan.reg_defer = None      # a deferral is only valid between this forward and its backward
         ctx.plan, ctx.has_lin = plan, has_lin
         ctx.shapes = [tuple(t.shape) for t in tables]
@@ -284,6 +293,171 @@ class EmbedGather(torch.autograd.Function):
                 _ptr(de), _ptr(dd), ld_dnn, _ptr(dl), ld_lin, _ptr(flat), _ptr(tab_off), _ptr(lin_off), _ptr(d_w),
                 _ptr(marks), _stream())), "embed_scatter_bwd")
         return grads, d_w
+
+
+# --------------------------------------------------------------------------------------------- #
+# pooled variable-length fields                                                                  #
+# --------------------------------------------------------------------------------------------- #
+POOL_CODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+class VarLenPlan:
+    """Metadata of the pooled variable-length fields of one model: per field the first id column of X, maxlen, the
+    length column (None: mask = id != 0), the combiner and the vocabulary size.  The device descriptors
+    (xdfm_varlen_field) are built once per set of table addresses, never per step."""
+
+    def __init__(self, cols: Sequence[int], maxlens: Sequence[int], len_cols, combiners: Sequence[str], vocab: Sequence[int],
+                 emb_dim: int, slot0: int = 0, dnn_off: int = 0):
+        self.F = len(cols)
+        self.D = int(emb_dim)
+        self.slot0, self.dnn_off = int(slot0), int(dnn_off)
+        self.cols = [int(c) for c in cols]
+        self.maxlens = [int(t) for t in maxlens]
+        self.len_cols = [-1 if c is None else int(c) for c in len_cols]
+        self.vocab = [int(v) for v in vocab]
+        for t in self.maxlens:
+            if not 1 <= t <= 255:
+                raise ValueError("VarLenSparseFeat: maxlen must lie in 1..255, got %d" % t)
+        for c in combiners:
+            if c not in POOL_CODES:
+                raise ValueError("VarLenSparseFeat: combiner must be one of sum, mean, max, got %r" % (c,))
+        self.combiners = [POOL_CODES[c] for c in combiners]
+        self.Tmax = max(self.maxlens)
+        self.min_cols = max([c + t for c, t in zip(self.cols, self.maxlens)] + [c + 1 for c in self.len_cols])
+        self._dev = {}
+        self._desc = {}
+        self._off_cache = {}
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._dev:
+            i32 = dict(dtype=torch.int32, device=device)
+            self._dev[key] = (torch.arange(self.F, **i32), torch.tensor(self.vocab, **i32), torch.zeros(1, **i32))
+        return self._dev[key]
+
+    def descriptors(self, emb_tables, lin_tables, device):
+        """(host array, device copy) of the field descriptors; re-uploaded only when a table address changed."""
+        key = (tuple(t.data_ptr() for t in emb_tables), tuple(t.data_ptr() for t in lin_tables), str(device))
+        hit = self._desc.get(key)
+        if hit is None:
+            host = (_lib.VarLenField * self.F)()
+            for f in range(self.F):
+                host[f].table = emb_tables[f].data_ptr() if emb_tables else None
+                host[f].lin = lin_tables[f].data_ptr() if lin_tables else None
+                host[f].col, host[f].maxlen, host[f].len_col = self.cols[f], self.maxlens[f], self.len_cols[f]
+                host[f].combiner, host[f].vocab = self.combiners[f], self.vocab[f]
+            dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device)
+            self._desc.clear()                 # one live set of addresses per plan
+            hit = self._desc[key] = (host, dev)
+        return hit
+
+    def grad_layout(self, shapes, device):
+        """Element offsets of every table gradient inside one flat buffer, each on a 16-byte boundary (device int64)."""
+        key = (tuple(shapes), str(device))
+        hit = self._off_cache.get(key)
+        if hit is None:
+            sizes = [sh[0] * sh[1] for sh in shapes]
+            offs, off = [], 0
+            for n in sizes:
+                offs.append(off)
+                off += (n + 3) // 4 * 4
+            hit = self._off_cache[key] = (sizes, offs, off, torch.tensor(offs if offs else [0], dtype=torch.int64, device=device))
+        return hit
+
+    def check_ids(self, device) -> bool:
+        """True when a pooled lookup since the last call saw an id outside [0, vocab) (syncs the stream)."""
+        flag = self.on(device)[2]
+        bad = bool(flag.item())
+        flag.zero_()
+        return bad
+
+
+class VarLenPool(torch.autograd.Function):
+    """Pools the variable-length fields of X into the outputs of EmbedGather, in place: field f goes to slot
+    plan.slot0 + f of emb_fm, to columns plan.dnn_off + f*D of dnn_in, and its pooled [V, 1] row is added to lin (any of
+    the three may be None).  `tables` = the F [V, D] tables (n_emb == F, or none with n_emb == 0), then the F [V, 1]
+    tables when lin is given.  The table gradients are ordinary dense tensors (views of one zero-filled buffer).
+
+    replaces deepctr/inputs.py:141-155 + :213-227 + deepctr/layers/sequence.py:49-77."""
+
+    @staticmethod
+    def forward(ctx, X, emb_fm, dnn_in, lin, plan: VarLenPlan, n_emb: int, *tables):
+        _need_cuda(X, "X")
+        lib = _lib.load()
+        F, D = plan.F, plan.D
+        emb_tables = tables[:n_emb]
+        lin_tables = tables[n_emb:]
+        if n_emb not in (0, F) or len(lin_tables) not in (0, F) or (lin is not None) != (len(lin_tables) == F) or \
+                ((emb_fm is not None or dnn_in is not None) != (n_emb == F)):
+            raise ValueError("xdfm: VarLenPool needs one [V, D] table per field for emb_fm / dnn_in and one [V, 1] table per field for lin")
+        for t in tables:
+            _need_cuda(t, "embedding table")
+            if not t.is_contiguous():
+                raise ValueError("xdfm: embedding tables must be contiguous")
+        for t, d in zip(emb_tables, [D] * F):
+            if t.shape[1] != d:
+                raise ValueError("xdfm: embedding_dim of a VarLenSparseFeat table is %d, the plan's is %d" % (t.shape[1], d))
+        X = X.contiguous()
+        B = X.shape[0]
+        if X.shape[1] < plan.min_cols:
+            raise ValueError("xdfm: X has %d columns, the variable-length fields need %d" % (X.shape[1], plan.min_cols))
+        N = B * D
+        if emb_fm is not None and not (emb_fm.is_contiguous() and emb_fm.shape[0] >= plan.slot0 + F and emb_fm.shape[1] == N):
+            raise ValueError("xdfm: VarLenPool: emb_fm must be contiguous [>= slot0 + F, B*D]")
+        if dnn_in is not None and not (dnn_in.stride(1) == 1 and dnn_in.shape[0] == B and dnn_in.shape[1] >= plan.dnn_off + F * D):
+            raise ValueError("xdfm: VarLenPool: dnn_in must be [B, >= dnn_off + F*D] with unit column stride")
+        if lin is not None and not (lin.is_contiguous() and lin.numel() == B):
+            raise ValueError("xdfm: VarLenPool: lin must be contiguous [B, 1]")
+        _, _, flag = plan.on(X.device)
+        host, dev = plan.descriptors(emb_tables, lin_tables, X.device)
+        argpos = torch.empty((B, F, D + 1), dtype=torch.uint8, device=X.device)
+        # algorithmic bytes: ids + the looked-up rows (+ linear rows) + the pooled rows to both consumers
+        T = sum(plan.maxlens)
+        nbytes = B * (4 * T + T * ((4 * D if n_emb else 0) + (4 if lin_tables else 0)) + 2 * 4 * F * D)
+        _lib.check(_run("varlen_pool_fwd[bytes]", nbytes, lambda: lib.xdfm_varlen_pool_fwd(
+            _ptr(X), X.stride(0), B, _ptr(dev), ctypes.cast(host, ctypes.c_void_p), F, D, plan.slot0, _ptr(emb_fm), _ptr(dnn_in),
+            dnn_in.stride(0) if dnn_in is not None else 0, plan.dnn_off, _ptr(lin), _ptr(argpos), _ptr(flag), _stream())),
+            "varlen_pool_fwd")
+        dirty = [t for t in (emb_fm, dnn_in, lin) if t is not None]
+        ctx.mark_dirty(*dirty)
+        ctx.plan, ctx.n_emb, ctx.n_lin = plan, n_emb, len(lin_tables)
+        ctx.shapes = [tuple(t.shape) for t in tables]
+        ctx.desc = (host, dev)
+        ctx.save_for_backward(X, argpos)
+        return emb_fm, dnn_in, lin
+
+    @staticmethod
+    def backward(ctx, d_emb, d_dnn, d_lin):
+        X, argpos = ctx.saved_tensors
+        plan = ctx.plan
+        lib = _lib.load()
+        F, D = plan.F, plan.D
+        need = ctx.needs_input_grad[6:]
+        grads = [None] * len(ctx.shapes)
+        if any(need):
+            dev = X.device
+            B = X.shape[0]
+            sizes, offs, total, off_dev = plan.grad_layout(ctx.shapes, dev)
+            flat = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+            grads = [flat[o:o + n].view(sh) for o, n, sh in zip(offs, sizes, ctx.shapes)]
+            cols, vocab, _ = plan.on(dev)
+            host, desc = ctx.desc
+            de = d_emb.contiguous() if d_emb is not None else None
+            dd = d_dnn if (d_dnn is None or d_dnn.stride(1) == 1) else d_dnn.contiguous()
+            dl = d_lin.reshape(B) if d_lin is not None else None
+            ld_lin = dl.stride(0) if dl is not None and B > 1 else 1
+            ws = torch.empty(lib.xdfm_varlen_pool_bwd_ws_elems(B, F, D, plan.Tmax), dtype=torch.float32, device=dev)
+            tab_off = off_dev[:F] if ctx.n_emb else None
+            lin_off = off_dev[ctx.n_emb:ctx.n_emb + F] if ctx.n_lin else None
+            P = B * plan.Tmax
+            nbytes = 4 * P * F * ((D if ctx.n_emb else 0) + (1 if ctx.n_lin else 0) + 1) * 2
+            _lib.check(_run("varlen_pool_bwd[bytes]", nbytes, lambda: lib.xdfm_varlen_pool_bwd(
+                _ptr(X), X.stride(0), B, _ptr(desc), ctypes.cast(host, ctypes.c_void_p), F, D, plan.slot0, _ptr(de), _ptr(dd),
+                dd.stride(0) if dd is not None else 0, plan.dnn_off, _ptr(dl), ld_lin, _ptr(argpos), _ptr(cols), _ptr(vocab),
+                _ptr(flat), _ptr(tab_off), _ptr(lin_off), _ptr(ws), _stream())), "varlen_pool_bwd")
+            grads = [g if n else None for g, n in zip(grads, need)]
+        # the gradients of the three outputs go on to the gather unchanged: K2 reads its own fields' part of them
+        return (None, d_emb, d_dnn, d_lin, None, None) + tuple(grads)
 
 
 def apply_stashed_scatter(stash, dense_w, params=None):

@@ -242,6 +242,7 @@ class DenseFeatureEncoder(nn.Module):
 
 # ------------------------------------------------------------------------------------------------- #
 class BaseModelSFG(BaseModel):
+    _VARLEN = False     # the SFG decoder and AutoDis are built on one id per field
     """BaseModel + SFG decoder / loss and the `sfg_loss` History entry (deepctr/xdeepfm_pro/basemodel_sfg.py:96-476).
     The training loop is BaseModel.fit: the step adds `sfg_weight * sfg_loss` to the total (basemodel_sfg.py:343) and
     the epoch logs gain `sfg_loss` = sum of the steps' values / sample_num (:365-366)."""
