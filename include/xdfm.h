@@ -67,7 +67,10 @@ enum {
     XDFM_ERR_NO_DEVICE = 3
 };
 
-enum { XDFM_ACT_LINEAR = 0, XDFM_ACT_RELU = 1 };
+/* `act` of the CIN entry points.  XDFM_ACT_RELU: max(v, 0); levels may keep 1 sign bit per element instead of the output
+ * (the `mask` arguments).  XDFM_ACT_SIGMOID: 1 / (1 + exp(-v)) in fp32 (accurate exp, true division); its backward
+ * y (1 - y) needs the stored fp32 output, so `mask` must be NULL with it.  Any other value: XDFM_ERR_INVALID. */
+enum { XDFM_ACT_LINEAR = 0, XDFM_ACT_RELU = 1, XDFM_ACT_SIGMOID = 2 };
 
 int xdfm_abi_version(void);
 const char* xdfm_last_error(void);          /* [host] thread-local, never NULL */

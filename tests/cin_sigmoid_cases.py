@@ -1,0 +1,142 @@
+"""The fixed backward cases behind tests/test_gpu_cin_sigmoid.py: xdfm_cin_dout_det and the fused xdfm_cin_bwd_prep
+(+ xdfm_cin_level_bwd_w_prepared) with act = 2 (sigmoid), every call twice.
+
+make_case(name) builds the inputs on the CPU from a seed; run_cases(dev) runs every case and returns the outputs as numpy
+arrays.  As a program (python cin_sigmoid_cases.py OUT.npz, started by the test with XDFM_TICKETS=1 in a fresh process) it
+registers the ticket board first and writes the arrays to OUT.npz: the board is registered once per process and changes
+every later launch, so the ticketed half never runs inside the pytest process (as tests/ticket_child.py)."""
+import ctypes
+import os
+import sys
+
+import numpy as np
+
+if __name__ == "__main__":          # as a program: the paths conftest.py sets for the tests
+    _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    for _p in (_ROOT, os.path.join(_ROOT, "xdeepfm-pytorch_amd")):
+        if _p not in sys.path:
+            sys.path.insert(0, _p)
+
+SIGMOID = 2
+# name: (H, B, D, split, dir_mode, cin_math, Hp, m)   Hp = 0: xdfm_cin_dout_det alone; otherwise the fused pass with the dW
+#                                                      operands of a level (Hp, m) -- shapes of tests/test_gpu_cin_instances.py
+CASES = {
+    "dout_split_pooled": (37, 300, 4, True, 0, 1, 0, 0),         # float4 path, hidden and direct-connect halves, gradient of the pooled sum
+    "dout_nosplit_scalar": (12, 77, 5, False, 0, 1, 0, 0),       # D = 5: the scalar path; every row has both gradient sources
+    "dout_nosplit_fm": (20, 1100, 4, False, 1, 1, 0, 0),         # N = 4400: two blocks per row; feature-map layout of dDirect
+    "prep_f16x3_split_pooled": (100, 512, 4, True, 0, 1, 13, 8),
+    "prep_bf16_nosplit_fm": (65, 750, 4, False, 1, 2, 21, 8),
+}
+
+
+def make_case(name):
+    """fp32 inputs: A in [0, 1] with exact 0.0 and 1.0 and the fp32 neighbours of both within 2^-24; dHid / dDirect of both
+    signs with exact zeros."""
+    H, B, D, split, dir_mode, math, Hp, m = CASES[name]
+    rng = np.random.default_rng(sorted(CASES).index(name) + 41)
+    N = B * D
+    A = (1.0 / (1.0 + np.exp(-2.5 * rng.standard_normal((H, N))))).astype(np.float32)
+    special = np.array([0.0, 1.0, 2.0 ** -24, 2.0 ** -25, 0.25, 1.0 - 2.0 ** -24, 1.0 - 2.0 ** -23, 0.5], dtype=np.float32)
+    pos = rng.choice(H * N, size=8 * special.size, replace=False)
+    A.reshape(-1)[pos] = np.tile(special, 8)
+    hid_rows = H // 2 if split else H
+    dir0, dir_rows = (hid_rows, H - hid_rows) if split else (0, H)
+    dhid = rng.standard_normal((hid_rows, N)).astype(np.float32)
+    dhid[rng.random(dhid.shape) < 0.05] = 0.0
+    dir_off = 3
+    if dir_mode == 0:
+        ddir = rng.standard_normal((B, dir_off + dir_rows + 2)).astype(np.float32)          # [example][pooled feature map]
+    else:
+        ddir = rng.standard_normal((dir_off + dir_rows, N)).astype(np.float32)              # feature-map layout
+    ddir[rng.random(ddir.shape) < 0.05] = 0.0
+    c = dict(name=name, H=H, B=B, D=D, N=N, math=math, Hp=Hp, m=m, A=A, dhid=dhid, ddir=ddir, hid_rows=hid_rows, dir0=dir0,
+             dir_rows=dir_rows, dir_off=dir_off, dir_mode=dir_mode)
+    if Hp:
+        c["xp"] = rng.standard_normal((Hp, N)).astype(np.float32)
+        c["x0"] = rng.standard_normal((m, N)).astype(np.float32)
+    return c
+
+
+def sources64(c):
+    """float64 (dHid, dDirect) spread over [H, N]: zero where a row has no such source"""
+    H, N, D = c["H"], c["N"], c["D"]
+    gh, gd = np.zeros((H, N)), np.zeros((H, N))
+    gh[:c["hid_rows"]] = c["dhid"]
+    rows = slice(c["dir0"], c["dir0"] + c["dir_rows"])
+    if c["dir_mode"] == 0:
+        gd[rows] = np.repeat(c["ddir"][:, c["dir_off"]:c["dir_off"] + c["dir_rows"]].T.astype(np.float64), D, axis=1)
+    else:
+        gd[rows] = c["ddir"][c["dir_off"]:c["dir_off"] + c["dir_rows"]]
+    return gh, gd
+
+
+def _run(c, dev):
+    import torch
+    from xdfm_amd import _lib
+    lib = _lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    H, B, D, N, Hp, m = c["H"], c["B"], c["D"], c["N"], c["Hp"], c["m"]
+    A, dhid, ddir = (torch.from_numpy(c[k]).to(dev) for k in ("A", "dhid", "ddir"))
+    lddir = ddir.shape[1]
+    p = lambda t: t.data_ptr()
+    out = {}
+    old = _lib.get_option("cin_math")
+    _lib.set_option("cin_math", c["math"])
+    try:
+        for rep in (0, 1):
+            dOut = torch.full((H, N), 7.0, device=dev)
+            dbias = torch.zeros(H, device=dev)
+            if not Hp:
+                ws = torch.empty(lib.xdfm_cin_dout_ws_elems(H, B, D), dtype=torch.float32, device=dev)
+                _lib.check(lib.xdfm_cin_dout_det(p(A), H, B, D, SIGMOID, p(dhid), 0, c["hid_rows"], p(ddir), c["dir_mode"], lddir,
+                                                 c["dir_off"], c["dir0"], c["dir_rows"], p(dOut), p(dbias), p(ws), st), "cin_dout_det")
+            else:
+                xp, x0 = torch.from_numpy(c["xp"]).to(dev), torch.from_numpy(c["x0"]).to(dev)
+                dws = torch.empty(lib.xdfm_cin_bwd_prep_ws_elems(H, Hp, m, B, D), dtype=torch.float32, device=dev)
+                ws = torch.empty(lib.xdfm_cin_bwd_w_ws_elems(H, Hp, m, N), dtype=torch.float32, device=dev)
+                flag = ctypes.c_int(0)
+                _lib.check(lib.xdfm_cin_bwd_prep(p(A), None, 0, H, B, D, SIGMOID, p(dhid), 0, c["hid_rows"], p(ddir), c["dir_mode"], lddir,
+                                                 c["dir_off"], c["dir0"], c["dir_rows"], p(dOut), p(dbias), p(dws), p(xp), p(x0), Hp, m,
+                                                 p(ws), ctypes.byref(flag), st), "cin_bwd_prep")
+                assert flag.value == 1, "%s: the fused pass did not prepare the dW operands" % c["name"]
+                dW = torch.full((H, Hp * m), 7.0, device=dev)
+                _lib.set_option("last_bww_inst", -1)
+                _lib.check(lib.xdfm_cin_level_bwd_w_prepared(p(dOut), p(xp), p(x0), H, Hp, m, N, p(ws), p(dW), st),
+                           "cin_level_bwd_w_prepared")
+                out["%s/%d/dW" % (c["name"], rep)] = dW.cpu().numpy()
+                out["%s/%d/bww_inst" % (c["name"], rep)] = np.array(_lib.get_option("last_bww_inst"))
+            torch.cuda.synchronize()
+            out["%s/%d/dOut" % (c["name"], rep)] = dOut.cpu().numpy()
+            out["%s/%d/dbias" % (c["name"], rep)] = dbias.cpu().numpy()
+    finally:
+        _lib.set_option("cin_math", old)
+    return out
+
+
+def run_cases(dev):
+    import torch
+    from xdfm_amd import _lib
+    out = {}
+    for name in CASES:
+        out.update(_run(make_case(name), dev))
+        torch.cuda.synchronize()
+        if 0 in _lib._BOARDS:
+            out["board/" + name] = _lib._BOARDS[0].cpu().numpy().copy()
+    out["meta/board_registered"] = np.array(int(0 in _lib._BOARDS))
+    return out
+
+
+def main(path):
+    import torch
+    from xdfm_amd import _lib
+    assert os.environ.get("XDFM_TICKETS") == "1", "start this program with XDFM_TICKETS=1"
+    dev = torch.device("cuda:0")
+    _lib.ticket_board(dev)
+    assert 0 in _lib._BOARDS, "no ticket board was registered"
+    out = run_cases(dev)
+    np.savez(path, **out)
+    print("cin_sigmoid_cases: %d arrays" % len(out))
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])

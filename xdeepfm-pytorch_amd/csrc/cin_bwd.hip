@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void cin_dout_kernel(
             }
 #pragma unroll
             for (int e = 0; e < VEC; ++e) {
-                if (act == XDFM_ACT_RELU && !(a[e] > 0.f)) g[e] = 0.f;
+                g[e] = xdfm_act_bwd(act, a[e], g[e]);
                 part += g[e];
             }
             if constexpr (VEC == 4) *reinterpret_cast<float4*>(orow + n) = make_float4(g[0], g[1], g[2], g[3]);
@@ -785,7 +785,8 @@ static int cin_dout_impl(const float* A, const unsigned* mask, long mask_ld, int
                          float* dOut, float* dbias, float* ws, void* stream) {
     XDFM_REQUIRE((A || mask) && dOut && dbias, "cin_dout: null pointer");
     XDFM_REQUIRE(H > 0 && B > 0 && D > 0, "cin_dout: bad shape H=%d B=%d D=%d", H, B, D);
-    XDFM_REQUIRE(act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU, "cin_dout: unsupported activation %d", act);
+    XDFM_REQUIRE(xdfm_act_known(act), "cin_dout: unsupported activation %d", act);
+    XDFM_REQUIRE(!mask || act != XDFM_ACT_SIGMOID, "cin_dout: sign bits do not describe a sigmoid level (mask must be NULL)");
     XDFM_REQUIRE(hid_rows >= 0 && dir_rows >= 0 && hid0 >= 0 && dir0 >= 0 && hid0 + hid_rows <= H &&
                      dir0 + dir_rows <= H, "cin_dout: row ranges outside [0,%d)", H);
     XDFM_REQUIRE(dir_mode == 0 || dir_mode == 1, "cin_dout: dir_mode %d", dir_mode);
@@ -915,7 +916,8 @@ int xdfm_cin_bwd_prep(const float* A, const unsigned* mask, long mask_ld, int H,
         return cin_dout_impl(A, mask, mask_ld, H, B, D, act, dHid, hid0, hid_rows, dDir, dir_mode, lddir, dir_off, dir0, dir_rows, dOut,
                              dbias, dout_ws, stream);
     XDFM_REQUIRE(dbias, "cin_bwd_prep: null pointer");
-    XDFM_REQUIRE(act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU, "cin_bwd_prep: unsupported activation %d", act);
+    XDFM_REQUIRE(xdfm_act_known(act), "cin_bwd_prep: unsupported activation %d", act);
+    XDFM_REQUIRE(!mask || act != XDFM_ACT_SIGMOID, "cin_bwd_prep: sign bits do not describe a sigmoid level (mask must be NULL)");
     XDFM_REQUIRE(hid_rows >= 0 && dir_rows >= 0 && hid0 >= 0 && dir0 >= 0 && hid0 + hid_rows <= H && dir0 + dir_rows <= H,
                  "cin_bwd_prep: row ranges outside [0,%d)", H);
     XDFM_REQUIRE(dir_mode == 0 || dir_mode == 1, "cin_bwd_prep: dir_mode %d", dir_mode);

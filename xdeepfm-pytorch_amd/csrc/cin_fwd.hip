@@ -162,6 +162,7 @@ __global__ __launch_bounds__(256, 2) void cin_fwd_kernel(
                     if (n < N) {
                         float v = acc[mt][f][r] + bv;
                         if (act == XDFM_ACT_RELU) v = fmaxf(v, 0.f);
+                        else if (act == XDFM_ACT_SIGMOID) v = xdfm_sigmoid(v);
                         out[(long)row * N + n] = v;
                     }
                 }
@@ -316,6 +317,7 @@ __global__ __launch_bounds__(256, 2) void cin_fwd_mp_kernel(
                     if (n < N) {
                         float v = acc[mt][f][r] + bv;
                         if (act == XDFM_ACT_RELU) v = fmaxf(v, 0.f);
+                        else if (act == XDFM_ACT_SIGMOID) v = xdfm_sigmoid(v);
                         out[(long)row * N + n] = v;
                     }
                 }
@@ -453,7 +455,7 @@ int xdfm_cin_level_fwd(const float* xp, const float* x0, const float* Wf, const 
                        int m, long N, int act, float* out, void* stream) {
     XDFM_REQUIRE(xp && x0 && Wf && bias && out, "cin_level_fwd: null pointer");
     XDFM_REQUIRE(H > 0 && Hp > 0 && m > 0 && N > 0, "cin_level_fwd: bad shape H=%d Hp=%d m=%d N=%ld", H, Hp, m, N);
-    XDFM_REQUIRE(act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU, "cin_level_fwd: unsupported activation %d", act);
+    XDFM_REQUIRE(xdfm_act_known(act), "cin_level_fwd: unsupported activation %d", act);
     hipStream_t st = (hipStream_t)stream;
     if (x3_fwd_usable(H, Hp, m)) { xdfm_opt_note(OPT_LAST_FWD, xdfm_opt(OPT_CIN_MATH)); return x3_level_fwd(xp, x0, Wf, bias, H, Hp, m, N, act, out, x3_fwd_epi_plain(H), st); }
     xdfm_opt_note(OPT_LAST_FWD, 0);
@@ -479,13 +481,14 @@ int xdfm_cin_level_fwd_ex(const float* xp, const float* x0, const float* Wf, con
                           unsigned* mask, long mask_ld, void* stream) {
     XDFM_REQUIRE(xp && x0 && Wf && bias, "cin_level_fwd_ex: null pointer");
     XDFM_REQUIRE(H > 0 && Hp > 0 && m > 0 && N > 0, "cin_level_fwd_ex: bad shape H=%d Hp=%d m=%d N=%ld", H, Hp, m, N);
-    XDFM_REQUIRE(act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU, "cin_level_fwd_ex: unsupported activation %d", act);
+    XDFM_REQUIRE(xdfm_act_known(act), "cin_level_fwd_ex: unsupported activation %d", act);
     XDFM_REQUIRE(xdfm_cin_level_fwd_ex_supported(H, Hp, m, D), "cin_level_fwd_ex: no f16x3 / bf16 forward kernel with this epilogue "
                  "for H=%d Hp=%d m=%d D=%d (xdfm_cin_level_fwd_ex_supported)", H, Hp, m, D);
     XDFM_REQUIRE(keep_rows >= 0 && keep_rows <= H && (keep_rows == 0 || out), "cin_level_fwd_ex: keep_rows %d of %d", keep_rows, H);
     XDFM_REQUIRE(!res || (dir0 >= 0 && dir0 <= H && ldres >= res_off + (H - dir0) && res_off >= 0 && N % D == 0),
                  "cin_level_fwd_ex: bad direct-sum arguments");
     XDFM_REQUIRE(!mask || (mask_ld >= H && mask_ld % 4 == 0), "cin_level_fwd_ex: mask pitch %ld", mask_ld);
+    XDFM_REQUIRE(!mask || act != XDFM_ACT_SIGMOID, "cin_level_fwd_ex: sign bits do not describe a sigmoid level (mask must be NULL)");
     int logD = 0;
     while ((1 << logD) < D) ++logD;
     const X3FwdEpi epi = {keep_rows, res, ldres, res_off, res ? dir0 : H, logD, mask, mask_ld};

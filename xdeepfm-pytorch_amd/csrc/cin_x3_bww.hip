@@ -619,6 +619,21 @@ __global__ __launch_bounds__(256) void x3_bwd_prep_kernel(
         const unsigned w = mrow[((c0 + o) >> 5) * mask_ld] >> ((c0 + o) & 31);
         return make_float4((w & 1u) ? 1.f : 0.f, (w & 2u) ? 1.f : 0.f, (w & 4u) ? 1.f : 0.f, (w & 8u) ? 1.f : 0.f);
     };
+    // g *= act'(output): ReLU keeps g where the output (or its sign bit) was > 0, sigmoid multiplies by y (1 - y) of the
+    // stored output; `act` is launch-uniform
+    auto act_bwd = [&](float4& g, const float4& av) {
+        if (act == XDFM_ACT_RELU) {
+            if (!(av.x > 0.f)) g.x = 0.f;
+            if (!(av.y > 0.f)) g.y = 0.f;
+            if (!(av.z > 0.f)) g.z = 0.f;
+            if (!(av.w > 0.f)) g.w = 0.f;
+        } else if (act == XDFM_ACT_SIGMOID) {
+            g.x *= xdfm_sigmoid_slope(av.x);
+            g.y *= xdfm_sigmoid_slope(av.y);
+            g.z *= xdfm_sigmoid_slope(av.z);
+            g.w *= xdfm_sigmoid_slope(av.w);
+        }
+    };
     auto value = [&](int o) -> float4 {
         const float4 av = use_mask ? keep4(o) : *reinterpret_cast<const float4*>(src + o);
         if (!is_d) return av;
@@ -626,26 +641,13 @@ __global__ __launch_bounds__(256) void x3_bwd_prep_kernel(
         if (hrow) g = *reinterpret_cast<const float4*>(hrow + o);
         if (drow) { const float4 dv = *reinterpret_cast<const float4*>(drow + o); g.x += dv.x; g.y += dv.y; g.z += dv.z; g.w += dv.w; }
         if (dres) { const float rr = dres[(long)x3_div((unsigned)(c0 + o), divD) * lddir]; g.x += rr; g.y += rr; g.z += rr; g.w += rr; }   // one example
-        if (act == XDFM_ACT_RELU) {
-            if (!(av.x > 0.f)) g.x = 0.f;
-            if (!(av.y > 0.f)) g.y = 0.f;
-            if (!(av.z > 0.f)) g.z = 0.f;
-            if (!(av.w > 0.f)) g.w = 0.f;
-        }
+        act_bwd(g, av);
         return g;
     };
     // a thread owns 8 consecutive columns per iteration (two float4): 16-byte stores into the hi and the lo half of a plane block
     float4 gv[2][2];
     float part = 0.f;
     const int iters = (span + 2047) / 2048;
-    auto relu_mask = [&](float4& g, const float4& av) {
-        if (act == XDFM_ACT_RELU) {
-            if (!(av.x > 0.f)) g.x = 0.f;
-            if (!(av.y > 0.f)) g.y = 0.f;
-            if (!(av.z > 0.f)) g.z = 0.f;
-            if (!(av.w > 0.f)) g.w = 0.f;
-        }
-    };
     // dbias share and split maximum of 8 columns; the dOut store too when the values do not stay in registers (otherwise it
     // waits until the block has drawn its ticket: a block's ticket waits for its outstanding stores, see `finish`)
     auto account = [&](int o, const float4& g0, const float4& g1) {
@@ -732,7 +734,7 @@ __global__ __launch_bounds__(256) void x3_bwd_prep_kernel(
             for (int it = 0; it < 2; ++it) {
 #pragma unroll
                 for (int q = 0; q < 2; ++q) {
-                    if (is_d) relu_mask(g[it][q], av[it][q]);
+                    if (is_d) act_bwd(g[it][q], av[it][q]);
                     else g[it][q] = av[it][q];
                     g[it][q].x *= msk[it][q]; g[it][q].y *= msk[it][q]; g[it][q].z *= msk[it][q]; g[it][q].w *= msk[it][q];
                     gv[it][q] = g[it][q];

@@ -466,6 +466,19 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void cin_fwd_x3_kernel(
     const unsigned res_lane = (unsigned)((nc >> E.logD) * E.ldres) + (unsigned)(4 * hh);     // example's row of res + the half's 4 rows
     const bool res_vec = E.res && ((E.ldres | (long)E.res_off | (long)E.dir0) & 3) == 0 && (((size_t)E.res) & 15) == 0;
     const int keep_rows = E.keep_rows < H ? E.keep_rows : H;
+    // XDFM_ACT_SIGMOID: a pass of its own over the accumulators, which then hold the outputs; the loop below takes them as
+    // they are through its own arithmetic (scale 1, bias x 0; relu / linear: bias x 1, exact).  With the sigmoid, or a
+    // select on `act`, inside that loop hipcc stops unrolling it at MT = 8, and the accumulators of a loop that is not
+    // unrolled live in scratch memory (576 B per lane, every instance with 8 row tiles, relu included).
+    float sc_e = sc, bias_e = 1.f;
+    if (act == XDFM_ACT_SIGMOID) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][r] = xdfm_sigmoid(acc[mt][r] * sc + bias_s[mt * 32 + frag_row(r, hh)]);
+        sc_e = 1.f;
+        bias_e = 0.f;
+    }
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
         __builtin_amdgcn_sched_barrier(0);          // one row tile at a time: 16 store addresses live, not 16 * MT
@@ -473,7 +486,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void cin_fwd_x3_kernel(
         float v[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            v[r] = acc[mt][r] * sc + bias_s[mt * 32 + frag_row(r, hh)];
+            v[r] = acc[mt][r] * sc_e + bias_s[mt * 32 + frag_row(r, hh)] * bias_e;
             if (act == XDFM_ACT_RELU) v[r] = fmaxf(v[r], 0.f);
         }
         // ---- the rows that are kept (all of them, or the hidden half): one lane mask for the whole tile when it is inside

@@ -74,7 +74,19 @@ __device__ __forceinline__ bool xdfm_last_block_done(unsigned* __restrict__ tick
     if (last) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");      // the other blocks' published partials, past this XCD's cache
     return last;
 }
+// XDFM_ACT_SIGMOID, forward: 1 / (1 + exp(-v)) with the accurate expf and an IEEE division (three roundings; exp(-v) = inf
+// for v < -88.7 gives the correct 0).  Backward, from the stored output y: y (1 - y) = fma(-y, y, y), one rounding, exactly 0
+// at y = 0 and y = 1.
+__device__ __forceinline__ float xdfm_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
+__device__ __forceinline__ float xdfm_sigmoid_slope(float y) { return fmaf(-y, y, y); }
+// dOut = act'(A) * g in place, A the level's stored output (or 1.0 / 0.0 from the ReLU sign bits)
+__device__ __forceinline__ float xdfm_act_bwd(int act, float a, float g) {
+    if (act == XDFM_ACT_RELU) return a > 0.f ? g : 0.f;
+    if (act == XDFM_ACT_SIGMOID) return g * xdfm_sigmoid_slope(a);
+    return g;
+}
 #endif
+static inline bool xdfm_act_known(int act) { return act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU || act == XDFM_ACT_SIGMOID; }
 
 #define XDFM_REQUIRE(cond, ...) \
     do { if (!(cond)) return xdfm_fail(XDFM_ERR_INVALID, __VA_ARGS__); } while (0)

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 
-ACT_CODES = {"linear": 0, "relu": 1}
+ACT_CODES = {"linear": 0, "relu": 1, "sigmoid": 2}      # XDFM_ACT_* of include/xdfm.h
 
 # bench.py sets this to a list to collect (name, algorithmic work, start event, end event) for each
 # heavy launch; the events are recorded on torch's current stream, the one the kernels run on.
@@ -54,7 +54,7 @@ def _need_cuda(t: torch.Tensor, name: str):
 def activation_code(name) -> int:
     key = name.lower() if isinstance(name, str) else name
     if key not in ACT_CODES:
-        raise NotImplementedError("xdfm CIN kernels implement activation 'relu' and 'linear', got %r" % (name,))
+        raise NotImplementedError("xdfm CIN kernels implement activation 'relu', 'linear' and 'sigmoid', got %r" % (name,))
     return ACT_CODES[key]
 
 
@@ -516,6 +516,14 @@ def _warn_if_fp32_fallback(what, probe, H, Hp, m):
                   % (what, H, Hp, m, "f16x3" if want == 1 else "bf16"), RuntimeWarning, stacklevel=3)
 
 
+def cin_lean_allowed(act: int) -> bool:
+    """Whether a CIN stack with this activation may run the lean levels (and with them the dX path that forms dOut from the
+    sign bits): both keep 1 bit per element, the sign of a ReLU output (for `linear` the bits are written and never read).
+    The sigmoid's derivative y (1 - y) needs the output itself, so its levels store full fp32 outputs and materialise
+    dOut -- the path XDFM_CIN_LEAN=0 selects for the others."""
+    return act != ACT_CODES["sigmoid"]
+
+
 class CINStack(torch.autograd.Function):
     """All CIN levels.  x0 is FM layout [m, B*D].
 
@@ -561,7 +569,7 @@ class CINStack(torch.autograd.Function):
         # rows into `result` and leaves the ReLU sign bits, so only the hidden rows (the next level's x_prev) are ever
         # written -- no direct_sum launches, no direct-connect half in memory, and the backward reads 1 bit per element
         # instead of the saved output (xdfm_cin_level_fwd_ex / xdfm_cin_bwd_prep)
-        lean = pool == "sum" and os.environ.get("XDFM_CIN_LEAN", "1") != "0" and \
+        lean = cin_lean_allowed(act) and pool == "sum" and os.environ.get("XDFM_CIN_LEAN", "1") != "0" and \
             all(lib.xdfm_cin_level_fwd_ex_supported(H, Hp, m, D) for (H, Hp, *_r) in levels)
         need_bwd = any(ctx.needs_input_grad)
         masks = []
