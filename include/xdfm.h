@@ -449,12 +449,14 @@ int xdfm_head_bwd(const float* pred, const float* y, const float* gloss, const f
  * replaces: torch.optim.Adam.step() (deepctr/models/basemodel.py:452).  The embedding / linear tables carry
  * dense gradients (deepctr/inputs.py:168), so the step streams every parameter: 28 B per parameter, arithmetic
  * of ATen's fused Adam in fp32.  `tensors` is a HOST array of T descriptors (device pointers inside; they travel
- * by value in the kernel arguments, 52 per launch); `step` points to the fp32 step counter torch keeps per
+ * by value in the kernel arguments, 64 per launch); `step` points to the fp32 step counter torch keeps per
  * parameter, already incremented for this step.
  * l2 > 0 in a descriptor: the kernel uses g + 2*l2*w as the gradient (the term l2 * sum(w^2) of
  * basemodel.py:412-428 with unit upstream gradient); with l2_value != NULL it also returns
  * sum_t l2_t * sum(w_t^2) of the weights BEFORE the update (l2_ws: xdfm_adam_step_ws_elems(T) floats).
- * ABI 3 added grad_marks. */
+ * ABI 3 added grad_marks.  Errors (NULL `tensors`, T <= 0 or T > 65535, a NULL member pointer, lr < 0, a beta outside
+ * [0, 1), eps < 0, l2_value without l2_ws, XDFM_ADAM_LAZY without grad_marks, XDFM_ADAM_DEFERRED without a clock, grad_marks
+ * or last, grad_marks with a pointer that is not 16-byte aligned) are reported before any device work. */
 typedef struct {
     float* param;
     float* grad;
@@ -544,10 +546,14 @@ int xdfm_rmsprop_step(const xdfm_opt_tensor* tensors, int T, double lr, const do
 typedef struct {
     int* clock;
     float* consts;
-    int cap;            /* steps the table holds: flush before clock[0] reaches it */
+    int cap;            /* steps the table holds, 3 .. 256 (`last` is one byte per chunk): flush before clock[0] reaches it */
 } xdfm_adam_clock;
 /* xdfm_adam_step_lr with a clock: advances it, records the step's constants, and treats XDFM_ADAM_DEFERRED tensors by
- * their marks only (replaying, for a marked chunk, whatever steps it still misses, then this one). */
+ * their marks only (replaying, for a marked chunk, whatever steps it still misses, then this one).  A tensor whose `step`
+ * counter is not the clock's clock[0] + clock[1] takes THIS step with constants of its own counter; the steps a chunk
+ * missed are always replayed with the clock's table (here, in the catch-up and in the flush), so a deferred tensor gives
+ * the sweep's bits only while its counter is the clock's or none of its chunks falls behind.  Errors (those of
+ * xdfm_adam_step_lr; a NULL clock or member, cap <= 2, cap > 256) are reported before any device work. */
 int xdfm_adam_step_deferred(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double lr,
                             const double* lr_dev, double beta1, double beta2, double eps, float* l2_ws, float* l2_value,
                             void* stream);
@@ -563,7 +569,9 @@ typedef struct {
 } xdfm_adam_rows;
 /* Brings the rows a batch is about to gather (X, cols, vocab as in xdfm_embed_gather_fwd; lin may be NULL) up to the
  * clock.  backlog: one 64-bit device cell (8-byte aligned, zeroed once by the caller); the L2 value of the replayed
- * steps is ADDED to it in 2^-40 fixed point (integer adds: the total does not depend on the order of the threads). */
+ * steps is ADDED to it in 2^-40 fixed point (integer adds: the total does not depend on the order of the threads).
+ * Errors (a NULL argument other than `lin`, a NULL clock member, cap outside 3 .. 256, B, m or D <= 0, an unaligned
+ * backlog) are reported before any device work. */
 int xdfm_adam_catchup_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
                            const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                            double beta1, double beta2, double eps, float* backlog, void* stream);
@@ -571,12 +579,14 @@ int xdfm_adam_catchup_rows(const float* X, long ldx, int B, const int* cols, con
  * (the batch whose gradients the scatter just wrote: single process), apply step clock[0] -- to be called after
  * xdfm_adam_step_deferred over the OTHER tensors, which advances the clock.  Reads the rows' gradient chunks, zeroes
  * them and their marks, updates the numel % 4 tail elements of every table densely.  l2_cell: 8-byte device scratch
- * (zero before the first call); l2_value[0] += the L2 value of the touched rows (may be NULL). */
+ * (zero before the first call); l2_value[0] += the L2 value of the touched rows (may be NULL).  Errors (as the catch-up's;
+ * emb or lin without grad, marks or last; an unaligned l2_cell) are reported before any device work. */
 int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
                          const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                          double beta1, double beta2, double eps, float* l2_cell, float* l2_value, void* stream);
 /* Brings every chunk of the XDFM_ADAM_DEFERRED tensors up to the clock, then resets the clock (clock[1] += clock[0],
- * clock[0] = 0, every `last` byte 0). */
+ * clock[0] = 0, every `last` byte 0).  Errors (NULL tensors / clock / backlog, a NULL clock member, cap outside 3 .. 256,
+ * T <= 0 or T > 65535, a deferred tensor with a NULL pointer, an unaligned backlog) are reported before any device work. */
 int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double beta1, double beta2,
                     double eps, float* backlog, void* stream);
 
@@ -596,7 +606,7 @@ int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_cloc
 typedef struct {
     int* clock;
     float* rates;
-    int cap;            /* steps the table holds: flush before clock[0] reaches it */
+    int cap;            /* steps the table holds, 3 .. 256: flush before clock[0] reaches it */
     unsigned long long* backlog;
     unsigned long long* cell;
 } xdfm_opt_clock;
@@ -607,7 +617,7 @@ typedef struct {
  * replays the steps it still misses with g = 0, takes this step with its gradient, gets zeros written back to the
  * gradient, its mark cleared and last = clock[0].  The numel % 4 tail elements are updated every step.  l2_value: the
  * term's value for the chunks this step touched plus the tensors without `last`.  Errors (NULL descriptors, T <= 0, a bad
- * clock, cap <= 2 (hence cap <= 0), a deferred tensor without grad_marks or with l2 == 0, Adagrad without state, eps <= 0) are reported
+ * clock, cap <= 2 (hence cap <= 0), cap > 256 (`last` is one byte per chunk), a deferred tensor without grad_marks or with l2 == 0, Adagrad without state, eps <= 0) are reported
  * before any device work. */
 int xdfm_sgd_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                            double lr, const double* lr_dev, float* l2_ws, float* l2_value, void* stream);

@@ -240,11 +240,17 @@ def test_ticketed_finishes_match_two_launch_path_bit_for_bit(tmp_path):
     assert int(ticketed["meta/board_registered"]) == 1 and int(plain["meta/board_registered"]) == 0
     assert int(ticketed["meta/replays"]) >= 3 and int(plain["meta/replays"]) >= 3
     boards = [k for k in ticketed if k.startswith("board/")]
-    assert len(boards) >= 5
+    assert len(boards) >= 5 and "board/adam70" in boards
     for k in boards:
         assert ticketed[k].size == 2048 and not ticketed[k].any(), "%s: tickets %s left non-zero" % (k, np.nonzero(ticketed[k])[0][:8])
     keys = sorted(k for k in ticketed if not k.startswith(("board/", "meta/")))
     assert keys == sorted(k for k in plain if not k.startswith(("board/", "meta/"))) and len(keys) > 40
+    adam = [k for k in keys if k.startswith("adam70/")]
+    assert len(adam) == 10 and all(np.isfinite(ticketed[k]).all() for k in adam)       # 2 runs x (2 L2 values + p, m, v)
+    for k in adam:
+        if k.startswith("adam70/0/"):          # the second run in a row gives the first one's bits (a ticket left behind would not)
+            assert ticketed[k].tobytes() == ticketed[k.replace("adam70/0/", "adam70/1/")].tobytes(), k
+            assert float(np.abs(ticketed[k]).max()) > 0
     diff = [k for k in keys if not (ticketed[k].dtype == plain[k].dtype and ticketed[k].shape == plain[k].shape
                                     and ticketed[k].tobytes() == plain[k].tobytes())]
     assert not diff, "ticketed and two-launch results differ in %s" % diff[:12]

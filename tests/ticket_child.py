@@ -1,6 +1,7 @@
 """The fixed list of cases behind test_gpu_head_reg.py::test_ticketed_finishes_match_two_launch_path_bit_for_bit.
 
-run_cases(dev) runs every kernel family that has a ticketed finish twice in a row and returns all outputs as numpy
+run_cases(dev) runs every kernel family that has a ticketed finish (the Adam step over 70 tensors, the head, the column
+sums, a train step) twice in a row and returns all outputs as numpy
 arrays, plus the ticket board (when one is registered) read after every family.  As a program (python ticket_child.py
 OUT.npz, started by the test with XDFM_TICKETS=1 in a fresh process) it registers the board first and writes the arrays
 to OUT.npz; imported by the test, the same function runs on the two-launch path.  The board is registered once per
@@ -16,6 +17,7 @@ if __name__ == "__main__":          # as a program: the paths conftest.py sets f
         if _p not in sys.path:
             sys.path.insert(0, _p)
 
+import adam_ref as A  # noqa: E402
 import head_reg_drivers as D  # noqa: E402
 import head_reg_ref as R  # noqa: E402
 
@@ -56,9 +58,24 @@ def _train(dev, out):
     return model.__dict__["_graphed_step"].replays
 
 
+def _adam70(dev, out):
+    """The 70-tensor Adam step of test_gpu_adam.py (two launches; the L2 partials of both are summed by the last launch's
+    ticket or by the finish launch), with l2_value, twice in a row."""
+    state = A.make_state_70()
+    for rep in (0, 1):
+        snap, values = A.run_70(dev, True, state=state)
+        for s, v in enumerate(values):
+            out["adam70/%d/l2_step%d" % (rep, s + 1)] = v
+        small = [t for t, n in enumerate(A.SIZES_70) if n <= 40989]
+        for k, name in enumerate("pmv"):
+            out["adam70/%d/%s" % (rep, name)] = np.concatenate([snap[t][k] for t in small])
+    _board(out, "adam70")
+
+
 def run_cases(dev):
     from xdfm_amd import _lib
     out = {}
+    _adam70(dev, out)
     for name in HEAD:
         c = R.make_head_case(name)
         for rep in (0, 1):

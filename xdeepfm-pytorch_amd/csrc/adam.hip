@@ -1,4 +1,4 @@
-// K7: Adam step over all parameters (one launch per 52 tensors, a 1-D grid shared out by tensor size; the embedding
+// K7: Adam step over all parameters (one launch per 64 tensors, a 1-D grid shared out by tensor size; the embedding
 // tables are 98 % of the bytes).
 //
 // replaces torch.optim.Adam.step() for the [vocab, D] / [vocab, 1] tables (deepctr/models/basemodel.py:452
@@ -54,9 +54,9 @@ __device__ __forceinline__ void adam_st(float4* a, const float4& x) {
 // first[k] = first block of tensor k in the launch's 1-D grid (first[cnt] = grid size): a tensor's share of the grid
 // follows its size, so a launch that holds four 10 M-row tables and thirty small tensors is 16 000 blocks of table
 // sweep, not 128 per tensor
-// the descriptor as the kernels see it: 72 bytes, so that 52 of them (the criteo-card step holds 51 tensors outside the
-// by-rows tables: one launch instead of two 35-us launches of small, latency-bound tensors) and the other arguments stay
-// inside the 4 KB a kernel's argument block may take
+// the descriptor as the kernels see it: 72 bytes, so that ADAM_CHUNK = 64 of them (the criteo-card step holds 51 tensors
+// outside the by-rows tables: one launch instead of two 35-us launches of small, latency-bound tensors) and the other
+// arguments stay inside the 8 KB the static_assert below allows for a kernel's argument block
 struct AdamDev {
     float* param; float* grad; float* exp_avg; float* exp_avg_sq; const float* step; unsigned char* grad_marks; unsigned char* last;
     long numel; float l2; int flags;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
     // the learning rate as a kernel argument, or read from device memory (a captured HIP graph then follows a
     // learning-rate schedule without being captured again)
     const double lr = lr_dev ? *lr_dev : lr_arg;
-    int ti = 0;                                        // wave-uniform search over <= 40 entries
+    int ti = 0;                                        // wave-uniform search over <= ADAM_CHUNK (64) entries
     for (int k = 1; k < cnt; ++k) ti += (int)blockIdx.x >= batch.first[k] ? 1 : 0;
     const int lb = (int)blockIdx.x - batch.first[ti];  // this block among the tensor's nb blocks
     const int nb = batch.first[ti + 1] - batch.first[ti];
@@ -314,9 +314,13 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
         // order), in slot order -- what adam_l2_finish_kernel does in a launch of its own
         if (ticket && xdfm_last_block_done(ticket, gridDim.x)) {
             __shared__ float acc[ADAM_THREADS];
-            float v = 0.f;
-            for (int k = threadIdx.x; k < l2_total; k += ADAM_THREADS) v += xdfm_peer(l2_part + k);
-            acc[threadIdx.x] = v;
+            // in that kernel's ORDER: its 1024 threads stride by 1024 and its tree's first two levels add thread t + 512,
+            // then t + 256 -- with more than 256 partials a stride of 256 would round differently (70 tensors: 1480 partials)
+            float vq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                for (int k = threadIdx.x + q * ADAM_THREADS; k < l2_total; k += 4 * ADAM_THREADS) vq[q] += xdfm_peer(l2_part + k);
+            acc[threadIdx.x] = (vq[0] + vq[2]) + (vq[1] + vq[3]);
             __syncthreads();
             for (int o = ADAM_THREADS / 2; o > 0; o >>= 1) {
                 if ((int)threadIdx.x < o) acc[threadIdx.x] += acc[threadIdx.x + o];
@@ -717,6 +721,8 @@ int xdfm_adam_step_deferred(const xdfm_adam_tensor* tensors, int T, const xdfm_a
                             const double* lr_dev, double beta1, double beta2, double eps, float* l2_ws, float* l2_value,
                             void* stream) {
     XDFM_REQUIRE(clk && clk->clock && clk->consts && clk->cap > 2, "adam_step_deferred: bad clock");
+    // `last` holds the step in one byte per chunk: a table of more than 256 steps would let it wrap
+    XDFM_REQUIRE(clk->cap <= 256, "adam_step_deferred: bad clock (cap %d > 256)", clk->cap);
     return adam_step_impl(tensors, T, clk, lr, lr_dev, beta1, beta2, eps, l2_ws, l2_value, stream);
 }
 
@@ -784,6 +790,7 @@ int xdfm_adam_catchup_rows(const float* X, long ldx, int B, const int* cols, con
                            const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                            double beta1, double beta2, double eps, float* backlog, void* stream) {
     XDFM_REQUIRE(X && cols && vocab && emb && clk && backlog, "adam_catchup_rows: null pointer");
+    XDFM_REQUIRE(clk->clock && clk->consts && clk->cap > 2 && clk->cap <= 256, "adam_catchup_rows: bad clock");
     XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "adam_catchup_rows: bad shape B=%d m=%d D=%d", B, m, D);
     XDFM_REQUIRE((((size_t)backlog) & 7) == 0, "adam_catchup_rows: backlog must be 8-byte aligned");
     const AdamRowsDev e = {emb->param, emb->exp_avg, emb->exp_avg_sq, emb->last, emb->l2, nullptr, nullptr};
@@ -800,6 +807,8 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
                          const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                          double beta1, double beta2, double eps, float* l2_cell, float* l2_value, void* stream) {
     XDFM_REQUIRE(X && cols && vocab && emb && clk && l2_cell, "adam_apply_rows: null pointer");
+    XDFM_REQUIRE(clk->clock && clk->consts && clk->cap > 2 && clk->cap <= 256, "adam_apply_rows: bad clock");
+    XDFM_REQUIRE(emb->last && (!lin || lin->last), "adam_apply_rows: `last` tables missing");
     XDFM_REQUIRE(emb->grad && emb->marks && (!lin || (lin->grad && lin->marks)), "adam_apply_rows: gradient / mark tables missing");
     XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "adam_apply_rows: bad shape B=%d m=%d D=%d", B, m, D);
     XDFM_REQUIRE((((size_t)l2_cell) & 7) == 0, "adam_apply_rows: l2_cell must be 8-byte aligned");
@@ -819,7 +828,9 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
 
 int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double beta1, double beta2,
                     double eps, float* backlog, void* stream) {
-    XDFM_REQUIRE(tensors && clk && clk->clock && clk->consts && backlog, "adam_flush: null pointer");
+    XDFM_REQUIRE(tensors && clk && backlog, "adam_flush: null pointer");
+    XDFM_REQUIRE(clk->clock && clk->consts && clk->cap > 2 && clk->cap <= 256, "adam_flush: bad clock");
+    XDFM_REQUIRE(T > 0 && T <= 65535, "adam_flush: bad tensor count %d", T);
     XDFM_REQUIRE((((size_t)backlog) & 7) == 0, "adam_flush: backlog must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     std::vector<int> order;

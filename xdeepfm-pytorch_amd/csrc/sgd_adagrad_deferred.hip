@@ -323,7 +323,7 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_flush_kernel(const OptDefBat
 // ---------------------------------------------------------------------------------------------
 static int opt_clock_ok(const char* what, const xdfm_opt_clock* clk) {
     XDFM_REQUIRE(clk && clk->clock && clk->rates && clk->backlog && clk->cell, "%s: bad clock (a null pointer)", what);
-    XDFM_REQUIRE(clk->cap > 2, "%s: bad clock (cap %d)", what, clk->cap);
+    XDFM_REQUIRE(clk->cap > 2 && clk->cap <= 256, "%s: bad clock (cap %d)", what, clk->cap);     // `last`: one byte per chunk
     XDFM_REQUIRE(((((size_t)clk->backlog) | ((size_t)clk->cell)) & 7) == 0, "%s: backlog and cell must be 8-byte aligned", what);
     return XDFM_OK;
 }

@@ -25,7 +25,7 @@ enum {
     OPT_X3_BWX_ROWS,     // 0 = auto (256); rows of the contraction per f16x3 dX launch (host side reads it)
     OPT_X3_WAVES,        // 0 = auto (8 waves per workgroup share a weight ring where the piece count allows); 4 = force 4
     OPT_BWW_PHASE,       // 0 = whole dW call; 1 / 2 / 3 = only the pre-passes / the MFMA kernel / the slab sum (f16x3; timing)
-    OPT_ADAM_BX,         // 0 = default (128); blocks per tensor of the Adam kernel
+    OPT_ADAM_BX,         // 0 = default (512, ADAM_BX); most blocks one tensor gets in the Adam kernel
     OPT_LAST_FWD,        // read-only probes: arithmetic of the kernel the last xdfm_cin_level_fwd / _bwd_x / _bwd_w call
     OPT_LAST_BWX,        //   launched: 0 = v_mfma_f32_32x32x2_f32, 1 = f16x3, 2 = bf16 (tests assert which kernel ran)
     OPT_LAST_BWW,
