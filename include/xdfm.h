@@ -46,7 +46,8 @@
  * Further ABI 8 additions (no existing struct or signature changed, so the version stays: a caller built against the earlier
  * ABI 8 header keeps working, and the binding checks every symbol it needs by name): xdfm_embed_gather_fwd_ld (K1 with a row pitch and a dense-column
  * offset for dnn_in), xdfm_varlen_field, xdfm_varlen_pool_fwd, xdfm_varlen_pool_bwd_ws_elems, xdfm_varlen_pool_bwd
- * (K1v / K2v: pooled variable-length fields).
+ * (K1v / K2v: pooled variable-length fields); XDFM_LINK_*, XDFM_LOSS_*, xdfm_head_fwd_ex, xdfm_head_bwd_ex (K8 with a
+ * compile-time link and loss: the regression task and the mse / mae losses).
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -62,7 +63,7 @@ extern "C" {
 
 enum {
     XDFM_OK = 0,
-    XDFM_ERR_INVALID = 1,   /* bad shape / null pointer / unsupported option */
+    XDFM_ERR_INVALID = 1,   /* bad shape / null pointer / unsupported option / unknown link, loss or (identity, bce) */
     XDFM_ERR_LAUNCH = 2,    /* HIP reported an error at launch */
     XDFM_ERR_NO_DEVICE = 3
 };
@@ -429,21 +430,36 @@ int xdfm_colsum(const float* g, long rows, int cols, long ld, float* ws, float* 
 int xdfm_relu_bwd_colsum(const float* g, const float* y, long rows, int cols, long ldg, long ldy, float* ws, float* gz,
                          float* out, void* stream);
 
-/* ------------------------------------------------------------------ output head of the binary task (K8)
- * z_b = lin_b + <u_b, wu> + <v_b, wv> + bias,  pred = sigmoid(z),  loss = sum_b BCE(pred_b, y_b).
+/* ------------------------------------------------------------------ output head: link + loss (K8)
+ * z_b = lin_b + <u_b, wu> + <v_b, wv> + bias,  pred = LINK(z),  loss = sum_b LOSS(pred_b, y_b).
  * replaces: cin_linear / dnn_linear (the two [B,K]x[K,1] products of deepctr/models/xdeepfm.py:95-105), the
- * logit sum, PredictionLayer (deepctr/layers/core.py:150-160) and F.binary_cross_entropy(reduction='sum')
- * (basemodel.py:254) with their autograd -- 2 GEMV + ~10 small launches forward, 4 skinny GEMMs + ~6 small
- * launches backward -- by two launches each way; fixed summation order.
+ * logit sum, PredictionLayer (deepctr/layers/core.py:150-160) and the summed loss of the batch loop
+ * (basemodel.py:254: F.binary_cross_entropy / F.mse_loss / F.l1_loss with reduction='sum') with their autograd
+ * -- 2 GEMV + ~10 small launches forward, 4 skinny GEMMs + ~6 small launches backward -- by two launches each
+ * way; fixed summation order.
  * lin [B] or NULL; u [B][Ku], wu [Ku] (or NULL); v [B][Kv], wv [Kv] (or NULL); bias [1] or NULL; y [B];
  * ws: xdfm_head_ws_elems(Ku, Kv) floats.  Backward: gloss [1]; dlin [B] or NULL; du [B][Ku]; dv [B][Kv];
- * grads [Ku + Kv + 1] = d wu | d wv | d bias. */
+ * grads [Ku + Kv + 1] = d wu | d wv | d bias.
+ * link: XDFM_LINK_SIGMOID (task "binary", pred = 1 / (1 + exp(-z))) or XDFM_LINK_IDENTITY (task "regression",
+ * pred = z).  loss: XDFM_LOSS_BCE (logs clamped at -100, as ATen), XDFM_LOSS_MSE ((pred - y)^2) or XDFM_LOSS_MAE
+ * (|pred - y|, gradient sign with sgn(0) = 0, as torch.sign).  The backward reads pred and y only.  The _ex entry
+ * points return XDFM_ERR_INVALID, before any device call and with both values in the message, for a link outside
+ * {0, 1}, a loss outside {0, 1, 2} and for (identity, bce), which does not exist.  xdfm_head_fwd / xdfm_head_bwd
+ * are the _ex calls with (XDFM_LINK_SIGMOID, XDFM_LOSS_BCE). */
+enum { XDFM_LINK_SIGMOID = 0, XDFM_LINK_IDENTITY = 1 };
+enum { XDFM_LOSS_BCE = 0, XDFM_LOSS_MSE = 1, XDFM_LOSS_MAE = 2 };
 size_t xdfm_head_ws_elems(int Ku, int Kv);
 int xdfm_head_fwd(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
                   const float* bias, const float* y, int B, float* pred, float* loss, float* ws, void* stream);
 int xdfm_head_bwd(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
                   const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
                   float* ws, void* stream);
+int xdfm_head_fwd_ex(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
+                     const float* bias, const float* y, int B, float* pred, float* loss_out, float* ws, int link, int loss,
+                     void* stream);
+int xdfm_head_bwd_ex(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
+                     const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
+                     float* ws, int link, int loss, void* stream);
 
 /* ------------------------------------------------------------------ Adam (K7)
  * replaces: torch.optim.Adam.step() (deepctr/models/basemodel.py:452).  The embedding / linear tables carry

@@ -254,8 +254,54 @@ int xdfm_relu_bwd_colsum(const float* g, const float* y, long rows, int cols, lo
 // launches backward, each a few microseconds of launch floor -- by two launches each way.
 // BCE as ATen evaluates it: log terms clamped at -100; backward (p - y) * p(1-p) / max(p(1-p), 1e-12).
 // All sums in a fixed order (per-block partials + a finish kernel): deterministic.
+//
+// The row tail is a compile-time choice of a link (pred = LINK(z)) and a loss; the dot products, the partials and both
+// finish paths are shared by all instantiations.  (sigmoid, bce) is the head above, spelled as it always was.  The
+// others -- the regression task and the "mse" / "mae" losses of basemodel.py's compile(), F.mse_loss / F.l1_loss with
+// reduction='sum' -- in the order the tests' bounds are derived from (tests/head_ex_ref.py), d = fl(p - t):
+//   link      pred p               loss   term                 g = d loss / d z   (gl = gloss[0])
+//   sigmoid   1 / (1 + expf(-z))   mse    fl(d * d)            fl(fl(gl * fl(2 d)) * pq),   pq = fl(fl(1 - p) * p)
+//   sigmoid   same                 mae    |d|                  fl(fl(gl * sgn(d)) * pq)
+//   identity  z                    mse    fl(d * d)            fl(gl * fl(2 d))
+//   identity  z                    mae    |d|                  fl(gl * sgn(d))
+// fl(2 d), sgn(d) (sgn(0) = 0, as torch.sign; a rounded difference keeps the exact one's sign) and gl * sgn(d) are
+// exact, so g costs 5 / 3 / 2 / 0 roundings: d and gl * s for mse, the two of pq and the last product for the sigmoid
+// link.  The term is added to the running sum; the compiler may fuse d * d into that add (one rounding fewer).  The
+// backward reads pred and y only: for the identity link pred IS z.
 #define HEAD_BLOCKS 128
 #define HEAD_THREADS 256
+enum { HEAD_SIGMOID = XDFM_LINK_SIGMOID, HEAD_IDENTITY = XDFM_LINK_IDENTITY };
+enum { HEAD_BCE = XDFM_LOSS_BCE, HEAD_MSE = XDFM_LOSS_MSE, HEAD_MAE = XDFM_LOSS_MAE };
+
+template <int LINK>
+__device__ __forceinline__ float head_link(float z) {
+    if constexpr (LINK == HEAD_SIGMOID) return 1.f / (1.f + expf(-z));
+    else return z;
+}
+
+template <int LOSS>
+__device__ __forceinline__ float head_term(float p, float t) {
+    if constexpr (LOSS == HEAD_BCE) {
+        return -(t * fmaxf(logf(p), -100.f) + (1.f - t) * fmaxf(logf(1.f - p), -100.f));
+    } else {
+        const float d = p - t;
+        if constexpr (LOSS == HEAD_MSE) return d * d;
+        else return fabsf(d);
+    }
+}
+
+template <int LINK, int LOSS>
+__device__ __forceinline__ float head_g(float gl, float p, float t) {
+    if constexpr (LOSS == HEAD_BCE) {
+        const float pq = (1.f - p) * p;
+        return gl * (p - t) / fmaxf(pq, 1e-12f) * pq;
+    } else {
+        const float d = p - t;
+        const float s = LOSS == HEAD_MSE ? 2.f * d : (float)(d > 0.f) - (float)(d < 0.f);
+        if constexpr (LINK == HEAD_SIGMOID) return (gl * s) * ((1.f - p) * p);
+        else return gl * s;
+    }
+}
 
 __device__ __forceinline__ float head_row_dot(const float* __restrict__ x, const float* __restrict__ w, int K, int lane) {
     float s = 0.f;
@@ -284,7 +330,7 @@ __device__ __forceinline__ float head_row_dot_vec(const float* __restrict__ x, c
 }
 
 // rows strided over all 16-lane groups of the grid; per-block partial loss -> part[blockIdx.x]
-template <bool VEC>
+template <bool VEC, int LINK, int LOSS>
 __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(
     const float* __restrict__ lin, const float* __restrict__ u, const float* __restrict__ wu, int Ku,
     const float* __restrict__ v, const float* __restrict__ wv, int Kv, const float* __restrict__ bias,
@@ -299,11 +345,11 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(
             float z = (lin ? lin[b] : 0.f) + bv;
             if (u) z += head_row_dot_vec<8>(u + (long)b * Ku, wu, Ku >> 2, sub);       // K <= 512
             if (v) z += head_row_dot_vec<8>(v + (long)b * Kv, wv, Kv >> 2, sub);
-            const float p = 1.f / (1.f + expf(-z));
+            const float p = head_link<LINK>(z);
             const float t = y[b];
             if (sub == 0) {
                 pred[b] = p;
-                acc += -(t * fmaxf(logf(p), -100.f) + (1.f - t) * fmaxf(logf(1.f - p), -100.f));
+                acc += head_term<LOSS>(p, t);
             }
         }
         acc += __shfl_xor(acc, 16);
@@ -313,11 +359,11 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(
             float z = (lin ? lin[b] : 0.f) + bv;
             if (u) z += head_row_dot(u + (long)b * Ku, wu, Ku, lane);
             if (v) z += head_row_dot(v + (long)b * Kv, wv, Kv, lane);
-            const float p = 1.f / (1.f + expf(-z));
+            const float p = head_link<LINK>(z);
             const float t = y[b];
             if (lane == 0) {
                 pred[b] = p;
-                acc += -(t * fmaxf(logf(p), -100.f) + (1.f - t) * fmaxf(logf(1.f - p), -100.f));
+                acc += head_term<LOSS>(p, t);
             }
         }
     }
@@ -348,8 +394,9 @@ __global__ __launch_bounds__(HEAD_BLOCKS) void head_fwd_finish_kernel(const floa
     if (threadIdx.x == 0) loss[0] = red[0];
 }
 
-// g_b = gloss * dBCE/dz;  dlin_b = g_b;  du[b][k] = g_b wu[k];  dv likewise;
+// g_b = gloss * dLOSS/dz (head_g);  dlin_b = g_b;  du[b][k] = g_b wu[k];  dv likewise;
 // per-block partials of dwu[k] = sum_b g_b u[b][k], dwv[k], dbias = sum_b g_b  -> part[blk][Ku + Kv + 1]
+template <int LINK, int LOSS>
 __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(
     const float* __restrict__ pred, const float* __restrict__ y, const float* __restrict__ gloss,
     const float* __restrict__ u, const float* __restrict__ wu, int Ku, const float* __restrict__ v,
@@ -364,8 +411,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(
     float gsum = 0.f;
     for (int b = blockIdx.x * 4 + wave; b < B; b += HEAD_BLOCKS * 4) {
         const float p = pred[b], t = y[b];
-        const float pq = (1.f - p) * p;
-        const float g = gl * (p - t) / fmaxf(pq, 1e-12f) * pq;
+        const float g = head_g<LINK, LOSS>(gl, p, t);
         if (lane == 0 && dlin) dlin[b] = g;
         gsum += g;
         if (u) {
@@ -395,6 +441,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(
 // loads / stores issued back to back; every lane keeps the partial column sums of its own columns in registers
 // (reduced over the wave's 4 row groups by shuffles at the end, over the 4 waves through LDS) -- the scalar
 // kernel above walks its rows one after the other with an LDS read-modify-write per element
+template <int LINK, int LOSS>
 __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_vec_kernel(
     const float* __restrict__ pred, const float* __restrict__ y, const float* __restrict__ gloss,
     const float* __restrict__ u, const float* __restrict__ wu, int Ku, const float* __restrict__ v,
@@ -417,8 +464,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_vec_kernel(
     float gsum = 0.f;
     for (int b = (blockIdx.x * 4 + wave) * 4 + grp; b < B; b += HEAD_BLOCKS * 16) {
         const float p = pred[b], t = y[b];
-        const float pq = (1.f - p) * p;
-        const float g = gl * (p - t) / fmaxf(pq, 1e-12f) * pq;
+        const float g = head_g<LINK, LOSS>(gl, p, t);
         if (sub == 0) { if (dlin) dlin[b] = g; gsum += g; }
         float4 xu[8], xv[8];
 #pragma unroll
@@ -481,46 +527,84 @@ extern "C" {
 
 size_t xdfm_head_ws_elems(int Ku, int Kv) { return (size_t)HEAD_BLOCKS * (size_t)(Ku + Kv + 1) + HEAD_BLOCKS; }
 
-int xdfm_head_fwd(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
-                  const float* bias, const float* y, int B, float* pred, float* loss, float* ws, void* stream) {
-    XDFM_REQUIRE(y && pred && loss && ws && B > 0, "head_fwd: bad arguments");
+// the five (link, loss) pairs; anything else is refused before any device call
+static int head_mode_check(const char* what, int link, int loss) {
+    XDFM_REQUIRE(link == XDFM_LINK_SIGMOID || link == XDFM_LINK_IDENTITY, "%s: link=%d (0 sigmoid, 1 identity), loss=%d", what, link, loss);
+    XDFM_REQUIRE(loss == XDFM_LOSS_BCE || loss == XDFM_LOSS_MSE || loss == XDFM_LOSS_MAE, "%s: link=%d, loss=%d (0 bce, 1 mse, 2 mae)", what, link, loss);
+    XDFM_REQUIRE(!(link == XDFM_LINK_IDENTITY && loss == XDFM_LOSS_BCE), "%s: link=%d (identity) with loss=%d (bce) does not exist", what, link, loss);
+    return XDFM_OK;
+}
+
+#define HEAD_DISPATCH(CALL)                                                              \
+    switch (link * 3 + loss) {                                                           \
+        case 0: CALL(HEAD_SIGMOID, HEAD_BCE); break;                                     \
+        case 1: CALL(HEAD_SIGMOID, HEAD_MSE); break;                                     \
+        case 2: CALL(HEAD_SIGMOID, HEAD_MAE); break;                                     \
+        case 4: CALL(HEAD_IDENTITY, HEAD_MSE); break;                                    \
+        default: CALL(HEAD_IDENTITY, HEAD_MAE); break;                                   \
+    }
+
+int xdfm_head_fwd_ex(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
+                     const float* bias, const float* y, int B, float* pred, float* loss_out, float* ws, int link, int loss,
+                     void* stream) {
+    XDFM_REQUIRE(y && pred && loss_out && ws && B > 0, "head_fwd: bad arguments");
     XDFM_REQUIRE((!u || (wu && Ku > 0)) && (!v || (wv && Kv > 0)) && Ku >= 0 && Kv >= 0, "head_fwd: bad operand shapes");
+    if (int rc = head_mode_check("head_fwd", link, loss)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int ku = u ? Ku : 0, kv = v ? Kv : 0;
     const bool vec = ku % 4 == 0 && kv % 4 == 0 && ku <= 512 && kv <= 512 &&
                      ((((size_t)u) | ((size_t)v) | ((size_t)wu) | ((size_t)wv)) & 15) == 0;
     unsigned* ticket = xdfm_ticket(TK_HEAD_FWD);
-    if (vec)
-        hipLaunchKernelGGL(head_fwd_kernel<true>, dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), 0, st, lin, u, wu, ku, v, wv, kv,
-                           bias, y, B, pred, ws, loss, ticket);
-    else
-        hipLaunchKernelGGL(head_fwd_kernel<false>, dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), 0, st, lin, u, wu, ku, v, wv, kv,
-                           bias, y, B, pred, ws, loss, ticket);
-    if (!ticket) hipLaunchKernelGGL(head_fwd_finish_kernel, dim3(1), dim3(HEAD_BLOCKS), 0, st, ws, loss);
+#define HEAD_FWD_LAUNCH(LINK, LOSS)                                                                                          \
+    if (vec)                                                                                                                 \
+        hipLaunchKernelGGL((head_fwd_kernel<true, LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), 0, st, lin, u, wu, ku, \
+                           v, wv, kv, bias, y, B, pred, ws, loss_out, ticket);                                               \
+    else                                                                                                                     \
+        hipLaunchKernelGGL((head_fwd_kernel<false, LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), 0, st, lin, u, wu,   \
+                           ku, v, wv, kv, bias, y, B, pred, ws, loss_out, ticket)
+    HEAD_DISPATCH(HEAD_FWD_LAUNCH)
+#undef HEAD_FWD_LAUNCH
+    if (!ticket) hipLaunchKernelGGL(head_fwd_finish_kernel, dim3(1), dim3(HEAD_BLOCKS), 0, st, ws, loss_out);
     return xdfm_check_launch("head_fwd");
 }
 
+int xdfm_head_fwd(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
+                  const float* bias, const float* y, int B, float* pred, float* loss, float* ws, void* stream) {
+    return xdfm_head_fwd_ex(lin, u, wu, Ku, v, wv, Kv, bias, y, B, pred, loss, ws, XDFM_LINK_SIGMOID, XDFM_LOSS_BCE, stream);
+}
+
 /* grads: [Ku + Kv + 1] = dwu | dwv | dbias */
-int xdfm_head_bwd(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
-                  const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
-                  float* ws, void* stream) {
+int xdfm_head_bwd_ex(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
+                     const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
+                     float* ws, int link, int loss, void* stream) {
     XDFM_REQUIRE(pred && y && gloss && grads && ws && B > 0, "head_bwd: bad arguments");
     XDFM_REQUIRE((!u || (wu && du && Ku > 0)) && (!v || (wv && dv && Kv > 0)), "head_bwd: bad operand shapes");
     const int ku = u ? Ku : 0, kv = v ? Kv : 0, KT = ku + kv + 1;
     const size_t lds = (size_t)4 * KT * sizeof(float);
     XDFM_REQUIRE(lds <= 64 * 1024, "head_bwd: Ku + Kv = %d too large", ku + kv);
+    if (int rc = head_mode_check("head_bwd", link, loss)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const bool vec = ku % 4 == 0 && kv % 4 == 0 && ku <= 512 && kv <= 512 &&
                      ((((size_t)u) | ((size_t)v) | ((size_t)wu) | ((size_t)wv) | ((size_t)du) | ((size_t)dv)) & 15) == 0;
     unsigned* ticket = xdfm_ticket(TK_HEAD_BWD);
-    if (vec)
-        hipLaunchKernelGGL(head_bwd_vec_kernel, dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), lds, st, pred, y, gloss, u, wu, ku, v,
-                           wv, kv, B, dlin, du, dv, ws, grads, ticket);
-    else
-        hipLaunchKernelGGL(head_bwd_kernel, dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), lds, st, pred, y, gloss, u, wu, ku, v, wv,
-                           kv, B, dlin, du, dv, ws, grads, ticket);
+#define HEAD_BWD_LAUNCH(LINK, LOSS)                                                                                          \
+    if (vec)                                                                                                                 \
+        hipLaunchKernelGGL((head_bwd_vec_kernel<LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), lds, st, pred, y, gloss, \
+                           u, wu, ku, v, wv, kv, B, dlin, du, dv, ws, grads, ticket);                                        \
+    else                                                                                                                     \
+        hipLaunchKernelGGL((head_bwd_kernel<LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), lds, st, pred, y, gloss, u,  \
+                           wu, ku, v, wv, kv, B, dlin, du, dv, ws, grads, ticket)
+    HEAD_DISPATCH(HEAD_BWD_LAUNCH)
+#undef HEAD_BWD_LAUNCH
     if (!ticket) hipLaunchKernelGGL(head_bwd_finish_kernel, dim3(ceil_div(KT, 256)), dim3(256), 0, st, ws, KT, grads);
     return xdfm_check_launch("head_bwd");
+}
+
+int xdfm_head_bwd(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
+                  const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
+                  float* ws, void* stream) {
+    return xdfm_head_bwd_ex(pred, y, gloss, u, wu, Ku, v, wv, Kv, B, dlin, du, dv, grads, ws, XDFM_LINK_SIGMOID, XDFM_LOSS_BCE,
+                            stream);
 }
 
 }  // extern "C"

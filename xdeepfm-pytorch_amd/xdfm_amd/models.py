@@ -441,17 +441,19 @@ class BaseModel(nn.Module):
         return step(x, y)
 
     def _fused_head(self, x, y):
-        """(y_pred, loss) through one launch (ops.Head) when the model is the binary-task xDeepFM family with the
-        stock F.binary_cross_entropy loss; None otherwise."""
-        if self.loss_func is not F.binary_cross_entropy or not hasattr(self, "head_inputs") or not x.is_cuda:
+        """(y_pred, summed data loss) through one launch (ops.Head) when the model is of the xDeepFM family (it has
+        `head_inputs`) and its task and compiled loss have a native head (ops.head_mode: binary / regression with
+        binary_crossentropy / mse / mae, except regression + binary_crossentropy); None otherwise."""
+        if not hasattr(self, "head_inputs") or not x.is_cuda:
             return None
         out = self.out
-        if getattr(out, "task", None) != "binary" or y.numel() != x.shape[0]:
+        mode = ops.head_mode(getattr(out, "task", None), self.loss_func)
+        if mode is None or y.numel() != x.shape[0]:
             return None
         lin, cin_out, dnn_out = self.head_inputs(x)
         return ops.Head.apply(y, out.bias if out.use_bias else None, lin,
                               cin_out, self.cin_linear.weight if cin_out is not None else None,
-                              dnn_out, self.dnn_linear.weight if dnn_out is not None else None)
+                              dnn_out, self.dnn_linear.weight if dnn_out is not None else None, *mode)
 
     def _loss_forward(self, x, y):
         """(y_pred, data loss): forward + loss of the reference's batch loop (basemodel.py:250-254)."""

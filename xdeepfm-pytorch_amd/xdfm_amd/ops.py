@@ -889,15 +889,36 @@ def dense(x, W, b):
 # --------------------------------------------------------------------------------------------- #
 # output head                                                                                    #
 # --------------------------------------------------------------------------------------------- #
+LINK_SIGMOID, LINK_IDENTITY = 0, 1          # XDFM_LINK_* of include/xdfm.h
+LOSS_BCE, LOSS_MSE, LOSS_MAE = 0, 1, 2      # XDFM_LOSS_*
+
+
+def head_mode(task, loss_func):
+    """(link, loss) of the native head (K8) for a model's task and compiled loss, or None when the stock tail has to
+    run: 'binary' -> sigmoid, 'regression' -> identity (PredictionLayer, core.py:150-160); F.binary_cross_entropy /
+    F.mse_loss / F.l1_loss -> bce / mse / mae, matched by identity (what compile() stores for "binary_crossentropy",
+    "mse", "mae"; basemodel.py:463-480).  None for 'multiclass', a list of losses, any other callable and
+    (regression, bce), which has no kernel.  Pure: needs no device."""
+    link = {"binary": LINK_SIGMOID, "regression": LINK_IDENTITY}.get(task) if isinstance(task, str) else None
+    if link is None or isinstance(loss_func, (list, tuple)):
+        return None
+    F = torch.nn.functional
+    for fn, loss in ((F.binary_cross_entropy, LOSS_BCE), (F.mse_loss, LOSS_MSE), (F.l1_loss, LOSS_MAE)):
+        if loss_func is fn:
+            return None if (link == LINK_IDENTITY and loss == LOSS_BCE) else (link, loss)
+    return None
+
+
 class Head(torch.autograd.Function):
-    """(y [B,1], bias [1]|None, lin [B,1]|None, u [B,Ku]|None, wu [1,Ku]|None, v [B,Kv]|None, wv [1,Kv]|None) ->
-    (pred [B], loss [1]) with pred = sigmoid(lin + u wu^T + v wv^T + bias), loss = sum BCE(pred, y): cin_linear /
-    dnn_linear + logit sum (deepctr/models/xdeepfm.py:95-105) + PredictionLayer (core.py:150-160) +
-    F.binary_cross_entropy(reduction='sum') (basemodel.py:254), two launches each way (K8).  `pred` is returned
-    for metrics and is not differentiable here (the model's train step differentiates the loss only)."""
+    """(y [B,1], bias [1]|None, lin [B,1]|None, u [B,Ku]|None, wu [1,Ku]|None, v [B,Kv]|None, wv [1,Kv]|None,
+    link = sigmoid, loss = bce) -> (pred [B], loss [1]) with pred = LINK(lin + u wu^T + v wv^T + bias), loss = sum
+    LOSS(pred, y): cin_linear / dnn_linear + logit sum (deepctr/models/xdeepfm.py:95-105) + PredictionLayer
+    (core.py:150-160) + the summed loss of the batch loop (basemodel.py:254; F.binary_cross_entropy, F.mse_loss or
+    F.l1_loss with reduction='sum'), two launches each way (K8).  `link` / `loss` are the pairs of head_mode().  `pred`
+    is returned for metrics and is not differentiable here (the model's train step differentiates the loss only)."""
 
     @staticmethod
-    def forward(ctx, y, bias, lin, u, wu, v, wv):
+    def forward(ctx, y, bias, lin, u, wu, v, wv, link=LINK_SIGMOID, loss=LOSS_BCE):
         lib = _lib.load()
         yv = y.reshape(-1).contiguous()
         B = yv.numel()
@@ -913,20 +934,21 @@ class Head(torch.autograd.Function):
             if t is not None and (t.dim() != 2 or t.shape[0] != B):
                 raise ValueError("xdfm head: operands must be [B, K]")
         pred = torch.empty(B, dtype=torch.float32, device=dev)
-        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.xdfm_head_ws_elems(Ku, Kv), dtype=torch.float32, device=dev)
-        _lib.check(lib.xdfm_head_fwd(_ptr(linv), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, _ptr(bias), _ptr(yv), B,
-                                     _ptr(pred), _ptr(loss), _ptr(ws), _stream()), "head_fwd")
+        _lib.check(lib.xdfm_head_fwd_ex(_ptr(linv), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, _ptr(bias), _ptr(yv), B,
+                                        _ptr(pred), _ptr(out), _ptr(ws), int(link), int(loss), _stream()), "head_fwd")
         ctx.save_for_backward(pred, yv, u, wu, v, wv)
         ctx.cfg = (bias is not None, lin is not None, tuple(lin.shape) if lin is not None else None, Ku, Kv)
+        ctx.mode = (int(link), int(loss))
         ctx.mark_non_differentiable(pred)
         ctx.set_materialize_grads(False)          # no [B] zero fill for pred's (unused) gradient slot
-        return pred, loss
+        return pred, out
 
     @staticmethod
     def backward(ctx, _gpred, gloss):
         if gloss is None:
-            return (None,) * 7
+            return (None,) * 9
         lib = _lib.load()
         pred, yv, u, wu, v, wv = ctx.saved_tensors
         has_bias, has_lin, lin_shape, Ku, Kv = ctx.cfg
@@ -939,12 +961,13 @@ class Head(torch.autograd.Function):
         grads = torch.empty(Ku + Kv + 1, **f32)
         ws = torch.empty(lib.xdfm_head_ws_elems(Ku, Kv), **f32)
         gl = gloss.reshape(1).contiguous()
-        _lib.check(lib.xdfm_head_bwd(_ptr(pred), _ptr(yv), _ptr(gl), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, B,
-                                     _ptr(dlin), _ptr(du), _ptr(dv), _ptr(grads), _ptr(ws), _stream()), "head_bwd")
+        _lib.check(lib.xdfm_head_bwd_ex(_ptr(pred), _ptr(yv), _ptr(gl), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, B,
+                                        _ptr(dlin), _ptr(du), _ptr(dv), _ptr(grads), _ptr(ws), ctx.mode[0], ctx.mode[1],
+                                        _stream()), "head_bwd")
         return (None, grads[Ku + Kv:Ku + Kv + 1] if has_bias else None,
                 dlin.view(lin_shape) if has_lin else None,
                 du, grads[:Ku].view(1, Ku) if u is not None else None,
-                dv, grads[Ku:Ku + Kv].view(1, Kv) if v is not None else None)
+                dv, grads[Ku:Ku + Kv].view(1, Kv) if v is not None else None, None, None)
 
 
 # --------------------------------------------------------------------------------------------- #
