@@ -30,8 +30,8 @@ def _dev():
 
 
 def _cls(kind):
-    from xdfm_amd.optim import TableAdagrad, TableSGD
-    return TableSGD if kind == "sgd" else TableAdagrad
+    from xdfm_amd import optim
+    return {"sgd": optim.TableSGD, "adagrad": optim.TableAdagrad, "rmsprop": optim.TableRMSprop, "adam": optim.TableAdam}[kind]
 
 
 def _big_vocab_model(dev, kind, deferred, use_graph, flush_every=5, emb_dim=D, vocab=VOCAB, seed=4, metrics=(), **kw):

@@ -101,3 +101,20 @@ def test_cpu_model_compiles_the_stock_classes():
         model.compile(name, "binary_crossentropy")
         assert type(model.optim) is cls and model.optim.param_groups[0]["lr"] == lr
         assert not model._optim_capturable and model._l2_fusion() is None
+
+
+def test_launch_order_and_grid_composer_under_the_host_sanitizers(tmp_path):
+    """csrc/table_step.h's host side (the size-sorted round-robin launch order and the first[] grid composer that the Adam,
+    SGD / Adagrad / RMSprop and deferred launchers share) in a stand-alone program, tests/table_step_host.hip, built with
+    AddressSanitizer and UndefinedBehaviorSanitizer on the host side and run on the CPU: T = 1, 63, 64, 65, 130 tensors of
+    0, 1, 8191, 8192, 8193 and 10^9 elements; first[] monotone, 1 <= blocks <= cap per tensor, and everything equal to the
+    loops the launchers spelled out before.  Nothing loaded into Python is sanitized."""
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "table_step_host")
+    subprocess.run([hipcc, "--offload-arch=gfx950", "-std=c++17", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined",
+                    "-Xarch_host", "-fno-sanitize-recover=all", os.path.join(ROOT, "tests", "table_step_host.hip"), "-o", exe],
+                   check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0 and "table_step_host ok: 270 cases" in run.stdout, (run.returncode, run.stdout, run.stderr)
+    assert "Sanitizer" not in run.stderr and "runtime error" not in run.stderr, run.stderr

@@ -127,6 +127,72 @@ def test_constructor_arguments_and_environment(monkeypatch):
         assert cls(ps).flush_every == 12
 
 
+SHARED = ("sync_lr", "load_state_dict", "add_param_group", "_invalidate", "_last_bytes", "take_backlog", "note_replay", "owns",
+          "arm_l2", "_l2_by_hand", "__getstate__", "__setstate__", "_drop_deferred", "_table_init", "flush")
+
+
+def test_table_adam_host_contract_and_the_one_scaffold_of_the_four_classes(monkeypatch):
+    """TableAdam's counterpart of the two tests around it, on two CPU parameters (no compute on a device): constructor
+    arguments and environment, the hooks the model calls without deferred state, `generation`, the stock state layout, a
+    pickle round trip, and the refusal of CPU parameters by the native step.  Then the structure: the host scaffold has one
+    definition, `_TableStep`'s, for all four classes."""
+    import pickle
+    from xdfm_amd import optim
+    from xdfm_amd.optim import TableAdagrad, TableAdam, TableRMSprop, TableSGD, _TableStep
+    for env in ("XDFM_ADAM_DEFERRED", "XDFM_ADAM_FLUSH_EVERY"):
+        monkeypatch.delenv(env, raising=False)
+    ps = [torch.nn.Parameter(torch.randn(5, 3)), torch.nn.Parameter(torch.randn(4))]
+    o = TableAdam(ps)
+    assert o.deferred == "auto" and o.flush_every == 64 and o.lazy_rows is False and o.table_step is True
+    assert o.path_counts == {"rows": 0, "scan": 0} and o._def is None and o._since == 0
+    assert TableAdam(ps, deferred=True).deferred is True and TableAdam(ps, deferred=False).deferred is False
+    assert TableAdam(ps, flush_every=7).flush_every == 7 and TableAdam(ps, flush_every=10 ** 6).flush_every == 248
+    monkeypatch.setenv("XDFM_ADAM_FLUSH_EVERY", "12")
+    assert TableAdam(ps).flush_every == 12
+    monkeypatch.setenv("XDFM_OPT_FLUSH_EVERY", "9")              # the other family's variable is not Adam's
+    assert TableAdam(ps).flush_every == 12 and TableSGD(ps).flush_every == 9
+    monkeypatch.delenv("XDFM_ADAM_FLUSH_EVERY")
+    monkeypatch.setenv("XDFM_ADAM_DEFERRED", "1")
+    assert TableAdam(ps).deferred is True and TableAdam(ps, deferred=False).deferred is False and TableSGD(ps).deferred == "auto"
+    monkeypatch.setenv("XDFM_ADAM_DEFERRED", "0")
+    assert TableAdam(ps).deferred is False
+    monkeypatch.delenv("XDFM_ADAM_DEFERRED")
+
+    mine = TableAdam(ps, lazy_rows=True, deferred=True, flush_every=3)
+    assert mine.owns(ps) and not mine.owns([torch.nn.Parameter(torch.zeros(2))])
+    mine.arm_l2([ps[0], ps[1], ps[0]], [0.25, 0.5, 0.125])       # a tensor named twice: its coefficients add
+    assert mine._armed == {id(ps[0]): 0.375, id(ps[1]): 0.5}
+    mine._armed = None
+    mine.flush()                                                 # no deferred state: the model's hooks are no-ops
+    assert mine.take_backlog() == 0.0
+    mine.note_replay()
+    assert mine._def is None and mine._since == 0 and mine.path_counts == {"rows": 0, "scan": 0}
+    stock = torch.optim.Adam([torch.nn.Parameter(p.detach().clone()) for p in ps], fused=True, capturable=True)
+    sd = mine.state_dict()
+    assert sorted(sd.keys()) == sorted(stock.state_dict().keys())
+    assert [sorted(g.keys()) for g in sd["param_groups"]] == [sorted(g.keys()) for g in stock.state_dict()["param_groups"]]
+    gen = mine.generation
+    mine.load_state_dict(sd)
+    assert mine.generation > gen
+    gen = mine.generation
+    extra = torch.nn.Parameter(torch.randn(2, 2))
+    mine.add_param_group({"params": [extra]})
+    assert mine.generation > gen and mine.owns([extra]) and len(mine.param_groups) == 2
+    twin = pickle.loads(pickle.dumps(mine))
+    assert twin.deferred is True and twin.flush_every == 3 and twin.lazy_rows is True
+    assert twin._def is None and twin._since == 0 and twin._desc == {} and twin.grad_sources == []
+    for p in ps:                                                 # native-eligible hyper-parameters, CPU tensors: an error, no fall-back
+        p.grad = torch.ones_like(p)
+    with pytest.raises(RuntimeError, match="xdfm TableAdam: parameters and gradients must be contiguous fp32 CUDA tensors"):
+        mine.step()
+
+    for cls in (TableAdam, TableSGD, TableAdagrad, TableRMSprop):
+        assert cls.__mro__[1] is _TableStep
+        for name in SHARED:
+            assert getattr(cls, name) is getattr(_TableStep, name), "%s.%s is not _TableStep's" % (cls.__name__, name)
+    assert [n for n in SHARED if n in vars(optim.TableAdam)] == []
+
+
 def test_deferred_classes_take_the_stock_update_on_cpu_parameters():
     """`deferred=True` changes nothing where the native step does not run: bit for bit the stock classes, and the hooks
     the model calls (`flush`, `take_backlog`, `note_replay`) are harmless no-ops; the state layout stays the stock one."""

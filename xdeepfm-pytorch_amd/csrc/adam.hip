@@ -17,43 +17,22 @@
 // two table-sized passes per step (sum of squares; gradient initialisation) from the train step.
 #include "xdfm_internal.h"
 #include "adam_math.h"
-
-#include <algorithm>
-#include <vector>
+#include "table_step.h"    // the streaming accesses, the chunk claim, the launch order and the grid composer
 
 #define ADAM_THREADS 256
 #define ADAM_BX 512             // most blocks one tensor gets (tools/adam_probe.py: 128 .. 4096 are within 5 % of each other, 512 best)
 #define ADAM_BLOCK_ELEMS 8192   // a tensor gets one block per this many elements: 8 float4 per thread and array
+#define ADAM_FLUSH_BX 4096      // ... and in the flush, which wants every SIMD busy
 
-// Streaming accesses: p, m, v (and the touched gradients) are read once and written once per step, 14 GB of them at
-// Criteo-card vocabularies -- non-temporal, four chunks per array and thread in flight.  tools/ubench/stream.hip is the
-// bare read-modify-write stream of the same shape: 6.4-7.3 TB/s while the three arrays total 1.9 GB, 4.4-5.5 TB/s at
-// the 7.7 GB this step sweeps -- K7 runs at 5.0-5.5 TB/s (tools/adam_probe.py), the rate the memory system gives
-// this footprint.
-typedef float adam_v4f __attribute__((ext_vector_type(4)));
-// wave-uniform chunk pointer + this lane's byte offset (32-bit: the access becomes scalar base + vector offset)
-__device__ __forceinline__ float4* at4(float4* base, unsigned byte_off) {
-    return reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off);
-}
-template <bool NT>
-__device__ __forceinline__ float4 adam_ld(const float4* a) {
-    if constexpr (!NT) return *a;
-    const adam_v4f t = __builtin_nontemporal_load(reinterpret_cast<const adam_v4f*>(a));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-template <bool NT>
-__device__ __forceinline__ void adam_st(float4* a, const float4& x) {
-    if constexpr (!NT) { *a = x; return; }
-    const adam_v4f t = {x.x, x.y, x.z, x.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<adam_v4f*>(a));
-}
+// Streaming accesses (table_step.h: tbl_ld / tbl_st, non-temporal, four chunks per array and thread in flight).
+// tools/ubench/stream.hip is the bare read-modify-write stream of the same shape: 6.4-7.3 TB/s while the three arrays total
+// 1.9 GB, 4.4-5.5 TB/s at the 7.7 GB this step sweeps -- K7 runs at 5.0-5.5 TB/s (tools/adam_probe.py), the rate the
+// memory system gives this footprint.
 
 #define ADAM_FIX 1099511627776.0          // 2^40: fixed-point scale of the L2 backlog (integer adds: order-independent)
 
 #define ADAM_CHUNK 64
-// first[k] = first block of tensor k in the launch's 1-D grid (first[cnt] = grid size): a tensor's share of the grid
-// follows its size, so a launch that holds four 10 M-row tables and thirty small tensors is 16 000 blocks of table
-// sweep, not 128 per tensor
+// first[k] = first block of tensor k in the launch's 1-D grid (first[cnt] = grid size), see tbl_grid (table_step.h)
 // the descriptor as the kernels see it: 72 bytes, so that ADAM_CHUNK = 64 of them (the criteo-card step holds 51 tensors
 // outside the by-rows tables: one launch instead of two 35-us launches of small, latency-bound tensors) and the other
 // arguments stay inside the 8 KB the static_assert below allows for a kernel's argument block
@@ -231,8 +210,8 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
             for (int q = 0; q < 4; ++q) k[q] = (marks + (iu + q * stride))[tx];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                P[q] = adam_ld<NT>(at4(p4 + (iu + q * stride), tx16)); M[q] = adam_ld<NT>(at4(m4 + (iu + q * stride), tx16));
-                V[q] = adam_ld<NT>(at4(v4 + (iu + q * stride), tx16));
+                P[q] = tbl_ld<NT>(at4(p4 + (iu + q * stride), tx16)); M[q] = tbl_ld<NT>(at4(m4 + (iu + q * stride), tx16));
+                V[q] = tbl_ld<NT>(at4(v4 + (iu + q * stride), tx16));
                 G[q] = zero4;
             }
             if (k[0] | k[1] | k[2] | k[3]) {
@@ -247,22 +226,22 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
                 ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
                 adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
                 adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
-                adam_st<NT>(at4(p4 + (iu + q * stride), tx16), pa); adam_st<NT>(at4(m4 + (iu + q * stride), tx16), ma);
-                adam_st<NT>(at4(v4 + (iu + q * stride), tx16), va);
+                tbl_st<NT>(at4(p4 + (iu + q * stride), tx16), pa); tbl_st<NT>(at4(m4 + (iu + q * stride), tx16), ma);
+                tbl_st<NT>(at4(v4 + (iu + q * stride), tx16), va);
                 __builtin_amdgcn_sched_barrier(0);       // one chunk's arithmetic at a time: its temporaries die before the next
             }
         }
         i = iu + tx;
         for (; i < n4; i += stride) {
             const unsigned char ka = marks[i];
-            float4 pa = adam_ld<NT>(p4 + i), ma = adam_ld<NT>(m4 + i), va = adam_ld<NT>(v4 + i);
+            float4 pa = tbl_ld<NT>(p4 + i), ma = tbl_ld<NT>(m4 + i), va = tbl_ld<NT>(v4 + i);
             float4 ga = zero4;
             if (ka) { ga = g4[i]; g4[i] = zero4; marks[i] = 0; }
             sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
             ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
             adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
             adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
-            adam_st<NT>(p4 + i, pa); adam_st<NT>(m4 + i, ma); adam_st<NT>(v4 + i, va);
+            tbl_st<NT>(p4 + i, pa); tbl_st<NT>(m4 + i, ma); tbl_st<NT>(v4 + i, va);
         }
     }
     long iu = i - threadIdx.x;                            // dense gradient: four float4 per array in flight
@@ -271,8 +250,8 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
         float4 P[4], M[4], V[4], G[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            P[q] = adam_ld<NT>(at4(p4 + (iu + q * stride), tx16)); G[q] = adam_ld<NT>(at4(g4 + (iu + q * stride), tx16));
-            M[q] = adam_ld<NT>(at4(m4 + (iu + q * stride), tx16)); V[q] = adam_ld<NT>(at4(v4 + (iu + q * stride), tx16));
+            P[q] = tbl_ld<NT>(at4(p4 + (iu + q * stride), tx16)); G[q] = tbl_ld<NT>(at4(g4 + (iu + q * stride), tx16));
+            M[q] = tbl_ld<NT>(at4(m4 + (iu + q * stride), tx16)); V[q] = tbl_ld<NT>(at4(v4 + (iu + q * stride), tx16));
         }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -281,19 +260,19 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
             ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
             adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
             adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
-            adam_st<NT>(at4(p4 + (iu + q * stride), tx16), pa); adam_st<NT>(at4(m4 + (iu + q * stride), tx16), ma);
-            adam_st<NT>(at4(v4 + (iu + q * stride), tx16), va);
+            tbl_st<NT>(at4(p4 + (iu + q * stride), tx16), pa); tbl_st<NT>(at4(m4 + (iu + q * stride), tx16), ma);
+            tbl_st<NT>(at4(v4 + (iu + q * stride), tx16), va);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
     i = iu + tx;
     for (; i < n4; i += stride) {
-        float4 pa = adam_ld<NT>(p4 + i), ga = adam_ld<NT>(g4 + i), ma = adam_ld<NT>(m4 + i), va = adam_ld<NT>(v4 + i);
+        float4 pa = tbl_ld<NT>(p4 + i), ga = tbl_ld<NT>(g4 + i), ma = tbl_ld<NT>(m4 + i), va = tbl_ld<NT>(v4 + i);
         sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
         ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
         adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
         adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
-        adam_st<NT>(p4 + i, pa); adam_st<NT>(m4 + i, ma); adam_st<NT>(v4 + i, va);
+        tbl_st<NT>(p4 + i, pa); tbl_st<NT>(m4 + i, ma); tbl_st<NT>(v4 + i, va);
     }
     for (long k = 4 * n4 + tid; k < n; k += stride) {
         float pa = p[k], ma = m[k], va = v[k];
@@ -422,20 +401,8 @@ __device__ __forceinline__ AdamClaim adam_claim_chunk(long idx, const float* __r
     k.cc = c0 + (k.is_lin ? 0 : q);
     const long n4 = (long)V * w / 4;                    // whole chunks; the tail elements are updated densely every step
     k.old = -1;
-    if (k.cc <= c1 && k.cc < n4 && (!need_table || R.p[k.f] != nullptr)) {      // a null table: left to the step's mark scan (small tables)
-        unsigned char* last = R.last[k.f];
-        unsigned* word = reinterpret_cast<unsigned*>(last + (k.cc & ~3L));
-        const int sh = (int)(k.cc & 3) * 8;
-        unsigned seen = *word;          // a plain (cached) read: stale at worst, and then the CAS below returns the current word
-        while (true) {
-            const int ob = (int)((seen >> sh) & 255u);
-            if (ob >= t) break;
-            const unsigned want = (seen & ~(255u << sh)) | ((unsigned)t << sh);
-            const unsigned got = atomicCAS(word, seen, want);
-            if (got == seen) { k.old = ob; break; }
-            seen = got;
-        }
-    }
+    if (k.cc <= c1 && k.cc < n4 && (!need_table || R.p[k.f] != nullptr))       // a null table: left to the step's mark scan (small tables)
+        k.old = tbl_claim(R.last[k.f], k.cc, t);
     return k;
 }
 
@@ -592,9 +559,9 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_flush_kernel(const AdamBatc
         const int old = in ? (int)last[i] : 0;
         const bool act = in && old < t;
         float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), ma = pa, va = pa;
-        if (act) { pa = adam_ld<true>(p4 + i); ma = adam_ld<true>(m4 + i); va = adam_ld<true>(v4 + i); }
+        if (act) { pa = tbl_ld<true>(p4 + i); ma = tbl_ld<true>(m4 + i); va = tbl_ld<true>(v4 + i); }
         adam_replay_span(pa, ma, va, act, old, t, consts, g2, zf, c, sq2, eps_ok);
-        if (act) { adam_st<true>(p4 + i, pa); adam_st<true>(m4 + i, ma); adam_st<true>(v4 + i, va); }
+        if (act) { tbl_st<true>(p4 + i, pa); tbl_st<true>(m4 + i, ma); tbl_st<true>(v4 + i, va); }
         if (in && old) last[i] = 0;
     }
     adam_backlog_add(l2c * (sq2.x + sq2.y), backlog);
@@ -700,6 +667,12 @@ __global__ __launch_bounds__(256) void adam_selftest_kernel(int mode, unsigned l
     if (bad) { atomicAdd(&out[1], 1ull); atomicMax(&out[2], what); }
 }
 
+// `last` holds the step in one byte per chunk: a table of more than 256 steps would let it wrap
+static int adam_clock_ok(const char* what, const xdfm_adam_clock* clk) {
+    XDFM_REQUIRE(clk && clk->clock && clk->consts && clk->cap > 2 && clk->cap <= 256, "%s: bad clock", what);
+    return XDFM_OK;
+}
+
 extern "C" {
 
 size_t xdfm_adam_step_ws_elems(int T) { return T > 0 ? (size_t)T * ADAM_BX : 0; }
@@ -720,9 +693,9 @@ int xdfm_adam_step_lr(const xdfm_adam_tensor* tensors, int T, double lr, const d
 int xdfm_adam_step_deferred(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double lr,
                             const double* lr_dev, double beta1, double beta2, double eps, float* l2_ws, float* l2_value,
                             void* stream) {
-    XDFM_REQUIRE(clk && clk->clock && clk->consts && clk->cap > 2, "adam_step_deferred: bad clock");
-    // `last` holds the step in one byte per chunk: a table of more than 256 steps would let it wrap
-    XDFM_REQUIRE(clk->cap <= 256, "adam_step_deferred: bad clock (cap %d > 256)", clk->cap);
+    // an otherwise good clock whose table is too long gets a message of its own
+    XDFM_REQUIRE(!(clk && clk->clock && clk->consts && clk->cap > 256), "adam_step_deferred: bad clock (cap %d > 256)", clk->cap);
+    if (int rc = adam_clock_ok("adam_step_deferred", clk)) return rc;
     return adam_step_impl(tensors, T, clk, lr, lr_dev, beta1, beta2, eps, l2_ws, l2_value, stream);
 }
 
@@ -748,30 +721,19 @@ static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_ada
     const int* clock = clk ? clk->clock : nullptr;
     const float* consts = clk ? clk->consts : nullptr;
     if (clk) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, clk->clock, clk->consts, clk->cap, lr, lr_dev, beta1, beta2);
-    // Launch composition: tensors sorted by size and dealt round-robin to the launches, so that every launch streams
-    // its share of the big tables and the small tensors' latency-bound blocks run underneath (a launch of small
-    // tensors alone took 25 us for 30 MB).  The order is a pure function of the sizes: deterministic.
+    // Launch composition: tensors sorted by size and dealt round-robin to the launches (tbl_launch_order)
     const int nlaunch = ceil_div(T, ADAM_CHUNK);
     unsigned* ticket = xdfm_ticket(TK_ADAM_L2);
-    std::vector<int> order(T);
-    for (int t = 0; t < T; ++t) order[t] = t;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tensors[a].numel > tensors[b].numel; });
+    const std::vector<int> order = tbl_launch_order(tensors, T);
     int slot0 = 0;
     for (int l = 0; l < nlaunch; ++l) {
         AdamBatch batch;
         int cnt = 0;
         for (int k = l; k < T; k += nlaunch) batch.t[cnt++] = adam_dev(tensors[order[k]]);
-        for (int k = cnt; k < ADAM_CHUNK; ++k) batch.t[k] = batch.t[0];
         // blocks per tensor by size (option "adam_bx" caps them: a small footprint for experiments)
         int cap = xdfm_opt(OPT_ADAM_BX);
         if (cap <= 0 || cap > ADAM_BX) cap = ADAM_BX;
-        batch.first[0] = 0;
-        for (int k = 0; k < ADAM_CHUNK; ++k) {
-            long nb = k < cnt ? ceil_div(batch.t[k].numel, (long)ADAM_BLOCK_ELEMS) : 0;
-            if (k < cnt && nb < 1) nb = 1;
-            if (nb > cap) nb = cap;
-            batch.first[k + 1] = batch.first[k] + (int)nb;
-        }
+        tbl_grid(batch, cnt, ADAM_BLOCK_ELEMS, cap);
         unsigned* tk = (l2_value && l == nlaunch - 1) ? ticket : nullptr;
         const int l2_total = slot0 + batch.first[cnt];
         if (xdfm_opt(OPT_DBG) & (1 << 17))              // experiment: ordinary (cached) loads and stores
@@ -790,7 +752,7 @@ int xdfm_adam_catchup_rows(const float* X, long ldx, int B, const int* cols, con
                            const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                            double beta1, double beta2, double eps, float* backlog, void* stream) {
     XDFM_REQUIRE(X && cols && vocab && emb && clk && backlog, "adam_catchup_rows: null pointer");
-    XDFM_REQUIRE(clk->clock && clk->consts && clk->cap > 2 && clk->cap <= 256, "adam_catchup_rows: bad clock");
+    if (int rc = adam_clock_ok("adam_catchup_rows", clk)) return rc;
     XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "adam_catchup_rows: bad shape B=%d m=%d D=%d", B, m, D);
     XDFM_REQUIRE((((size_t)backlog) & 7) == 0, "adam_catchup_rows: backlog must be 8-byte aligned");
     const AdamRowsDev e = {emb->param, emb->exp_avg, emb->exp_avg_sq, emb->last, emb->l2, nullptr, nullptr};
@@ -807,7 +769,7 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
                          const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                          double beta1, double beta2, double eps, float* l2_cell, float* l2_value, void* stream) {
     XDFM_REQUIRE(X && cols && vocab && emb && clk && l2_cell, "adam_apply_rows: null pointer");
-    XDFM_REQUIRE(clk->clock && clk->consts && clk->cap > 2 && clk->cap <= 256, "adam_apply_rows: bad clock");
+    if (int rc = adam_clock_ok("adam_apply_rows", clk)) return rc;
     XDFM_REQUIRE(emb->last && (!lin || lin->last), "adam_apply_rows: `last` tables missing");
     XDFM_REQUIRE(emb->grad && emb->marks && (!lin || (lin->grad && lin->marks)), "adam_apply_rows: gradient / mark tables missing");
     XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "adam_apply_rows: bad shape B=%d m=%d D=%d", B, m, D);
@@ -829,7 +791,7 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
 int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double beta1, double beta2,
                     double eps, float* backlog, void* stream) {
     XDFM_REQUIRE(tensors && clk && backlog, "adam_flush: null pointer");
-    XDFM_REQUIRE(clk->clock && clk->consts && clk->cap > 2 && clk->cap <= 256, "adam_flush: bad clock");
+    if (int rc = adam_clock_ok("adam_flush", clk)) return rc;
     XDFM_REQUIRE(T > 0 && T <= 65535, "adam_flush: bad tensor count %d", T);
     XDFM_REQUIRE((((size_t)backlog) & 7) == 0, "adam_flush: backlog must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
@@ -844,14 +806,8 @@ int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_cloc
     for (int l0 = 0; l0 < n; l0 += ADAM_CHUNK) {
         AdamBatch batch;
         const int cnt = n - l0 < ADAM_CHUNK ? n - l0 : ADAM_CHUNK;
-        for (int k = 0; k < ADAM_CHUNK; ++k) batch.t[k] = adam_dev(tensors[order[l0 + (k < cnt ? k : 0)]]);
-        batch.first[0] = 0;
-        for (int k = 0; k < ADAM_CHUNK; ++k) {
-            long nb = k < cnt ? ceil_div(batch.t[k].numel, (long)ADAM_BLOCK_ELEMS) : 0;
-            if (k < cnt && nb < 1) nb = 1;
-            if (nb > 4096) nb = 4096;
-            batch.first[k + 1] = batch.first[k] + (int)nb;
-        }
+        for (int k = 0; k < cnt; ++k) batch.t[k] = adam_dev(tensors[order[l0 + k]]);
+        tbl_grid(batch, cnt, ADAM_BLOCK_ELEMS, ADAM_FLUSH_BX);
         hipLaunchKernelGGL(adam_flush_kernel, dim3(batch.first[cnt]), dim3(ADAM_THREADS), 0, st, batch, cnt, clk->clock, clk->consts,
                            beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog));
     }

@@ -6,20 +6,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-typedef float opt_v4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4* opt_at4(float4* base, unsigned byte_off) {
-    return reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off);
-}
-// p and the accumulator are read once and written once per pass: non-temporal
-__device__ __forceinline__ float4 opt_ld(const float4* a) {
-    const opt_v4f t = __builtin_nontemporal_load(reinterpret_cast<const opt_v4f*>(a));
-    return make_float4(t.x, t.y, t.z, t.w);
-}
-__device__ __forceinline__ void opt_st(float4* a, const float4& x) {
-    const opt_v4f t = {x.x, x.y, x.z, x.w};
-    __builtin_nontemporal_store(t, reinterpret_cast<opt_v4f*>(a));
-}
-
 // The optimizer a kernel instance is for.  SGD has no state; Adagrad's and RMSprop's `s` is the accumulator.
 enum OptKind { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_RMSPROP = 2 };
 // `eps` and RMSprop's decay, as floats (1 - alpha is taken in double on the host, as Python takes it)

@@ -22,9 +22,7 @@
 // or from one device double, per-block L2 partials summed in a fixed order by a finish kernel: all as K7.
 #include "xdfm_internal.h"
 #include "opt_math.h"      // opt_one / opt_four: the element update, shared with the deferred kernels
-
-#include <algorithm>
-#include <vector>
+#include "table_step.h"    // the streaming accesses, the launch order and the grid composer, shared with K7
 
 #define OPT_THREADS 256
 #define OPT_BX 512              // most blocks one tensor gets (K7's ADAM_BX)
@@ -123,35 +121,35 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
             for (int q = 0; q < NF; ++q) { k[q] = (marks + (iu + q * stride))[tx]; any |= k[q]; }
 #pragma unroll
             for (int q = 0; q < NF; ++q) {
-                P[q] = opt_ld(opt_at4(p4 + (iu + q * stride), tx16));
-                S[q] = ADA ? opt_ld(opt_at4(s4 + (iu + q * stride), tx16)) : zero4;
+                P[q] = tbl_ld<true>(at4(p4 + (iu + q * stride), tx16));
+                S[q] = ADA ? tbl_ld<true>(at4(s4 + (iu + q * stride), tx16)) : zero4;
                 G[q] = zero4;
             }
             if (any) {
 #pragma unroll
                 for (int q = 0; q < NF; ++q)
                     if (k[q]) {
-                        G[q] = *opt_at4(g4 + (iu + q * stride), tx16);
-                        *opt_at4(g4 + (iu + q * stride), tx16) = zero4;
+                        G[q] = *at4(g4 + (iu + q * stride), tx16);
+                        *at4(g4 + (iu + q * stride), tx16) = zero4;
                         (marks + (iu + q * stride))[tx] = 0;
                     }
             }
 #pragma unroll
             for (int q = 0; q < NF; ++q) {
                 opt_four<K>(P[q], S[q], G[q], g2, nlr, hyp, sq);
-                opt_st(opt_at4(p4 + (iu + q * stride), tx16), P[q]);
-                if constexpr (ADA) opt_st(opt_at4(s4 + (iu + q * stride), tx16), S[q]);
+                tbl_st<true>(at4(p4 + (iu + q * stride), tx16), P[q]);
+                if constexpr (ADA) tbl_st<true>(at4(s4 + (iu + q * stride), tx16), S[q]);
             }
         }
         i = iu + tx;
         for (; i < n4; i += stride) {
             const unsigned char ka = marks[i];
-            float4 pa = opt_ld(p4 + i), sa = ADA ? opt_ld(s4 + i) : zero4;
+            float4 pa = tbl_ld<true>(p4 + i), sa = ADA ? tbl_ld<true>(s4 + i) : zero4;
             float4 ga = zero4;
             if (ka) { ga = g4[i]; g4[i] = zero4; marks[i] = 0; }
             opt_four<K>(pa, sa, ga, g2, nlr, hyp, sq);
-            opt_st(p4 + i, pa);
-            if constexpr (ADA) opt_st(s4 + i, sa);
+            tbl_st<true>(p4 + i, pa);
+            if constexpr (ADA) tbl_st<true>(s4 + i, sa);
         }
     }
     long iu = i - tx;                                   // dense gradient, read in full and left alone
@@ -159,24 +157,24 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
         float4 P[NF], S[NF], G[NF];
 #pragma unroll
         for (int q = 0; q < NF; ++q) {
-            P[q] = opt_ld(opt_at4(p4 + (iu + q * stride), tx16));
-            G[q] = opt_ld(opt_at4(g4 + (iu + q * stride), tx16));
-            S[q] = ADA ? opt_ld(opt_at4(s4 + (iu + q * stride), tx16)) : zero4;
+            P[q] = tbl_ld<true>(at4(p4 + (iu + q * stride), tx16));
+            G[q] = tbl_ld<true>(at4(g4 + (iu + q * stride), tx16));
+            S[q] = ADA ? tbl_ld<true>(at4(s4 + (iu + q * stride), tx16)) : zero4;
         }
 #pragma unroll
         for (int q = 0; q < NF; ++q) {
             opt_four<K>(P[q], S[q], G[q], g2, nlr, hyp, sq);
-            opt_st(opt_at4(p4 + (iu + q * stride), tx16), P[q]);
-            if constexpr (ADA) opt_st(opt_at4(s4 + (iu + q * stride), tx16), S[q]);
+            tbl_st<true>(at4(p4 + (iu + q * stride), tx16), P[q]);
+            if constexpr (ADA) tbl_st<true>(at4(s4 + (iu + q * stride), tx16), S[q]);
         }
     }
     i = iu + tx;
     for (; i < n4; i += stride) {
-        float4 pa = opt_ld(p4 + i), sa = ADA ? opt_ld(s4 + i) : zero4;
-        const float4 ga = opt_ld(g4 + i);
+        float4 pa = tbl_ld<true>(p4 + i), sa = ADA ? tbl_ld<true>(s4 + i) : zero4;
+        const float4 ga = tbl_ld<true>(g4 + i);
         opt_four<K>(pa, sa, ga, g2, nlr, hyp, sq);
-        opt_st(p4 + i, pa);
-        if constexpr (ADA) opt_st(s4 + i, sa);
+        tbl_st<true>(p4 + i, pa);
+        if constexpr (ADA) tbl_st<true>(s4 + i, sa);
     }
     for (long k = 4 * n4 + tid; k < n; k += stride) {  // the numel % 4 tail (always read); whole unaligned tensors
         float pa = p[k], sa = ADA ? s[k] : zf;
@@ -227,11 +225,9 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
                          ((((size_t)tensors[t].param) | ((size_t)tensors[t].grad) | (ADA ? (size_t)tensors[t].state : 0)) & 15) == 0,
                      "%s: tensor %d has grad_marks but a pointer that is not 16-byte aligned", what, t);
     hipStream_t st = (hipStream_t)stream;
-    // Launch composition as K7: tensors sorted by size and dealt round-robin to the launches; a pure function of the sizes.
+    // Launch composition as K7: tensors sorted by size and dealt round-robin to the launches (tbl_launch_order)
     const int nlaunch = ceil_div(T, OPT_CHUNK);
-    std::vector<int> order(T);
-    for (int t = 0; t < T; ++t) order[t] = t;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tensors[a].numel > tensors[b].numel; });
+    const std::vector<int> order = tbl_launch_order(tensors, T);
     int slot0 = 0;
     for (int l = 0; l < nlaunch; ++l) {
         OptBatch batch;
@@ -240,14 +236,7 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
             const xdfm_opt_tensor& x = tensors[order[k]];
             batch.t[cnt++] = OptDev{x.param, x.grad, x.state, x.grad_marks, x.numel, x.l2};
         }
-        for (int k = cnt; k < OPT_CHUNK; ++k) batch.t[k] = batch.t[0];
-        batch.first[0] = 0;
-        for (int k = 0; k < OPT_CHUNK; ++k) {
-            long nb = k < cnt ? ceil_div(batch.t[k].numel, (long)OPT_BLOCK_ELEMS) : 0;
-            if (k < cnt && nb < 1) nb = 1;
-            if (nb > OPT_BX) nb = OPT_BX;
-            batch.first[k + 1] = batch.first[k] + (int)nb;
-        }
+        tbl_grid(batch, cnt, OPT_BLOCK_ELEMS, OPT_BX);
         hipLaunchKernelGGL(opt_step_kernel<K>, dim3(batch.first[cnt]), dim3(OPT_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev,
                            opt_hyper(K, eps, alpha), l2_value ? l2_ws : nullptr);
         slot0 += batch.first[cnt];

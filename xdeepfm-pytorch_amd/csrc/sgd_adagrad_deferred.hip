@@ -13,8 +13,7 @@
 // L2 value of the replayed steps goes to a 64-bit fixed-point cell by integer adds; there are no float atomics.
 #include "xdfm_internal.h"
 #include "opt_math.h"
-
-#include <vector>
+#include "table_step.h"    // the streaming accesses and the grid composer, shared with K7 / K7d
 
 #define OPTD_THREADS 256
 #define OPTD_BX 512                 // most blocks one tensor gets in the step's scan (K7s' OPT_BX)
@@ -201,7 +200,9 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_catchup_rows_kernel(
         float* base = Rp[f];                            // a null table: not deferred
         if (cc <= c1 && cc < n4 && base != nullptr) {
             // the first thread to reach the chunk in this launch claims it: CAS on the word that holds its `last` byte;
-            // duplicates of an id lose the claim and skip.  The gather runs in a later launch.
+            // duplicates of an id lose the claim and skip.  The gather runs in a later launch.  This is tbl_claim
+            // (table_step.h) spelled out: through the helper, hipcc compares `ob` with `t` as unsigned in the three
+            // instances of this kernel, and the kernels' code is kept as it was.
             unsigned* word = reinterpret_cast<unsigned*>(Rl[f] + (cc & ~3L));
             const int sh = (int)(cc & 3) * 8;
             unsigned seen = *word;      // a plain (cached) read: stale at worst, and then the CAS below returns the current word
@@ -290,7 +291,7 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_flush_kernel(const OptDefBat
 #pragma unroll
         for (int q = 0; q < NF; ++q) {
             P[q] = zero4; S[q] = zero4;
-            if (act[q]) { P[q] = opt_ld(p4 + i[q]); if constexpr (ADA) S[q] = opt_ld(s4 + i[q]); }
+            if (act[q]) { P[q] = tbl_ld<true>(p4 + i[q]); if constexpr (ADA) S[q] = tbl_ld<true>(s4 + i[q]); }
         }
         lo = opt_wave_min(lo);
         for (int st = lo + 1; st <= t; ++st) {
@@ -308,7 +309,7 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_flush_kernel(const OptDefBat
         }
 #pragma unroll
         for (int q = 0; q < NF; ++q) {
-            if (act[q]) { opt_st(p4 + i[q], P[q]); if constexpr (ADA) opt_st(s4 + i[q], S[q]); }
+            if (act[q]) { tbl_st<true>(p4 + i[q], P[q]); if constexpr (ADA) tbl_st<true>(s4 + i[q], S[q]); }
             if (in[q] && old[q]) last[i[q]] = 0;
         }
     }
@@ -330,18 +331,6 @@ static int opt_clock_ok(const char* what, const xdfm_opt_clock* clk) {
 
 static OptDefDev opt_def_dev(const xdfm_opt_tensor& x, unsigned char* last) {
     return OptDefDev{x.param, x.grad, x.state, x.grad_marks, last, x.numel, x.l2};
-}
-
-// first[] of a launch over `cnt` deferred tensors: a tensor's share of the 1-D grid follows its size
-static void opt_def_grid(OptDefBatch& batch, int cnt, int bx) {
-    for (int k = cnt; k < OPTD_CHUNK; ++k) batch.t[k] = batch.t[0];
-    batch.first[0] = 0;
-    for (int k = 0; k < OPTD_CHUNK; ++k) {
-        long nb = k < cnt ? ceil_div(batch.t[k].numel, (long)OPTD_BLOCK_ELEMS) : 0;
-        if (k < cnt && nb < 1) nb = 1;
-        if (nb > bx) nb = bx;
-        batch.first[k + 1] = batch.first[k] + (int)nb;
-    }
 }
 
 template <int K>
@@ -383,7 +372,7 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
         OptDefBatch batch;
         const int cnt = n - l0 < OPTD_CHUNK ? n - l0 : OPTD_CHUNK;
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[def[l0 + k]], last[def[l0 + k]]);
-        opt_def_grid(batch, cnt, OPTD_BX);
+        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, OPTD_BX);
         hipLaunchKernelGGL(opt_step_deferred_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock,
                            clk->rates, opt_hyper(K, eps, alpha), clk->backlog, clk->cell);
     }
@@ -413,7 +402,7 @@ static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* 
         OptDefBatch batch;
         const int cnt = T - l0 < OPTD_CHUNK ? T - l0 : OPTD_CHUNK;
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[l0 + k], last[l0 + k]);
-        opt_def_grid(batch, cnt, OPTD_FLUSH_BX);
+        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, OPTD_FLUSH_BX);
         hipLaunchKernelGGL(opt_flush_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock, clk->rates,
                            opt_hyper(K, eps, alpha), clk->backlog);
     }
