@@ -47,7 +47,9 @@
  * ABI 8 header keeps working, and the binding checks every symbol it needs by name): xdfm_embed_gather_fwd_ld (K1 with a row pitch and a dense-column
  * offset for dnn_in), xdfm_varlen_field, xdfm_varlen_pool_fwd, xdfm_varlen_pool_bwd_ws_elems, xdfm_varlen_pool_bwd
  * (K1v / K2v: pooled variable-length fields); XDFM_LINK_*, XDFM_LOSS_*, xdfm_head_fwd_ex, xdfm_head_bwd_ex (K8 with a
- * compile-time link and loss: the regression task and the mse / mae losses).
+ * compile-time link and loss: the regression task and the mse / mae losses); xdfm_compact_rows_fwd / _bwd (K11: positive-row
+ * compaction with the count on the device) and xdfm_vocab_ce_pack_hidden_n, _fwd_n, _pack_g_n, _bwd_h_n, _bwd_w_n (K9 with a
+ * device-side row count: the SFG branch of the xDeepFMPro step with batch-shaped launches, so the step can be captured).
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -700,7 +702,7 @@ int xdfm_vocab_softmax_grad(float* z, long ld, int rows, int T, const float* lse
  *   pack_hidden     hidden [R][K] fp32, contiguous -> `pack` (pack_elems(R, K) floats): MFMA fragments of H and H^T,
  *                   hi / lo halves, one power-of-two scale.  Once per step: every field's head reads the same rows.
  *   fwd             ce[f][r] = logsumexp_v(h_r.W_v + b_v) - (h_r.W_t + b_t), t = targets[f][r] (int64, clamped to
- *                   [0, V_f)); lse2 [F][rows_padded(R)] (zeroed by the caller) receives the base-2 log-sum-exp and
+ *                   [0, V_f)); lse2 [F][rows_padded(R)] receives the base-2 log-sum-exp and
  *                   wmax [F] the bits of max|W_f|: both are inputs of the backward.
  *   pack_g          upstream gradients g [F][R] -> gpack (F * (4 + rows_padded(R)) floats): g scaled to fp16 range.
  *   bwd_h           dh[r][:] = sum_f [ sum_v g[f][r] softmax_f[r][v] W_f[v][:] - g[f][r] W_f[t][:] ]
@@ -723,6 +725,47 @@ int xdfm_vocab_ce_bwd_h(const float* pack, int R, int K, const xdfm_vce_field* f
                         float* dh, long lddh, void* stream);
 int xdfm_vocab_ce_bwd_w(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, int n_blk, const long* targets,
                         const float* gpack, const float* lse2, const unsigned* wmax, void* stream);
+
+/* The same five passes with the number of rows in use on the DEVICE (n_rows: one int32 in device memory, read by the
+ * kernels; NULL = all R rows, which is what the entry points above pass).  R is then a capacity: the plan, pack_elems,
+ * rows_padded, the workspaces and every row pitch ([F][R] targets / ce / g, [R][K] hidden / dh) come from R and never from
+ * the count, so the launch sequence and every shape are the same for every count -- a captured train step replays with
+ * whatever the batch holds.  Rows r >= *n_rows are absent: their hidden rows, targets and g are never read (they may hold
+ * anything, NaN included), ce[f][r] = 0 and dh[r][:] = 0 exactly, and they add nothing to dW, db, lse2 or the operand
+ * maxima.  A 512-row group of the rows-stationary kernels behind the count returns at once and the weights-stationary
+ * kernel walks ceil(*n_rows / 32) row tiles, so absent rows cost no arithmetic.  *n_rows == 0 gives ce = 0, dh = 0, dW = 0,
+ * db = 0; a count above R counts as R.  With *n_rows == R every output has the bits of the entry points above.
+ * (fwd and fwd_n zero the padding of lse2 themselves: the caller need not clear it.) */
+int xdfm_vocab_ce_pack_hidden_n(const float* hidden, long ldh, int R, int K, float* pack, const int* n_rows, void* stream);
+int xdfm_vocab_ce_fwd_n(const float* pack, const float* hidden, long ldh, int R, int K, const xdfm_vce_field* fields, int F,
+                        const xdfm_vce_item* items, long n_items, const long* targets, float* ws, float* ce, float* lse2,
+                        unsigned* wmax, const int* n_rows, void* stream);
+int xdfm_vocab_ce_pack_g_n(const float* g, int F, int R, float* gpack, const int* n_rows, void* stream);
+int xdfm_vocab_ce_bwd_h_n(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, const xdfm_vce_item* items, long n_items,
+                          const long* targets, const float* g, const float* gpack, const float* lse2, unsigned* wmax, float* ws,
+                          float* dh, long lddh, const int* n_rows, void* stream);
+int xdfm_vocab_ce_bwd_w_n(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, int n_blk, const long* targets,
+                          const float* gpack, const float* lse2, const unsigned* wmax, const int* n_rows, void* stream);
+
+/* ------------------------------------------------------------------ K11: positive-row compaction (csrc/compact.hip)
+ * replaces: torch.nonzero(labels == 1) + three index_selects in front of the SFG decoder (the rows the reference's
+ *           `ce_loss * positive_mask` zeroes, deepctr/xdeepfm_pro/sfg_decoder.py:262-293, left out of the decoder), whose
+ *           row count reaches the host.  Every output here has the capacity B; the count stays on the device.
+ *   X        [B][ldx] the model input (xcols columns in use); cols: DEVICE int32[F], the id column of each sparse field
+ *   dnn_in   [B][ldd] decoder input rows, W floats each; y [B] labels (contiguous)
+ *   positive_only   1: a row is selected when y[b] == 1; 0: every row is
+ *   pos      [B] int32 out: the slot of row b (the number of selected rows before it: torch.nonzero's order) or -1
+ *   n_rows   [1] int32 out; inv_n [1] = 1 / (n + 1e-8), or 1 / B when not positive_only
+ *   valid    [B] 1 for slot < n, else 0;  d_rows [B][W] the selected rows, exact zeros behind them;  labels [B] likewise;
+ *   targets  [F][B] int64: the ids (X truncated towards zero) of the selected rows, 0 behind them
+ * One workgroup scans the labels (ballot + popcount + LDS, no atomics), a second launch moves the rows: every element of
+ * every output is written exactly once.  bwd: d_dnn [B][W] (contiguous) = g[pos[b]][:] for a selected row, zeros otherwise
+ * (plain stores; g [B][ldg] is the gradient of d_rows).  1 <= B <= 65536; 16-byte accesses when W, the row pitches and the
+ * base addresses are multiples of 4 floats, single floats otherwise.  Arguments are validated before any device work. */
+int xdfm_compact_rows_fwd(const float* X, long ldx, int xcols, const float* dnn_in, long ldd, const float* y, long B, int W,
+                          const int* cols, int F, int positive_only, int* pos, int* n_rows, float* inv_n, float* valid,
+                          float* d_rows, float* labels, long* targets, void* stream);
+int xdfm_compact_rows_bwd(const float* g, long ldg, const int* pos, long B, int W, float* d_dnn, void* stream);
 
 /* ------------------------------------------------------------------ AutoDis of xdeepfm_pro (K10, csrc/autodis.hip)
  * replaces: the per-field Python loop of deepctr/xdeepfm_pro/autodis.py:99-125 (Linear(1,K), LeakyReLU(0.2), Linear(K,K),

@@ -22,6 +22,11 @@
 //                        = examples), P as B operand again, dW^T += H_tile^T . P; db = column sums.  Every row of dW is
 //                        written once, complete.
 //
+// Row count on the device (the `_n` entry points; xDeepFMPro's captured step): R is then a capacity that fixes the layout, the
+// plan, the grids and the workspaces, and `n_rows` (one int32 in device memory) says how many rows are in use.  A row group of
+// vx_hs_kernel behind the count returns at once, vx_ws_kernel walks the tiles in use only, the pack and merge kernels never read
+// a row at or behind the count and write zeros for it.  A null `n_rows` = all R rows: the entry points without a count.
+//
 // Arithmetic: every product is hi*hi + hi*lo + lo*hi on fp16 halves of power-of-two scaled operands (as the CIN's
 // f16x3 kernels), fp32 accumulation; exp / log in base 2 (v_exp_f32 / v_log_f32) on fp32.
 #include "cin_x3_fwd.h"
@@ -58,9 +63,20 @@ __global__ void vx_zero_words_kernel(unsigned* __restrict__ w, int n, int stride
     if (i < n) w[(long)i * stride] = 0u;
 }
 
-// out[y] = max(out[y], bits(max |x[y * stride + i]|, i < n)) -- non-negative floats order like their bit patterns
-__global__ __launch_bounds__(256) void vx_absmax_kernel(const float* __restrict__ x, long n, long stride, unsigned* __restrict__ out, int out_stride) {
+// Rows in use: the `_n` entry points hand the kernels a device-side count (rows at and beyond it are absent); the
+// entry points without one pass a null pointer and every row of the capacity R is in use.
+__device__ __forceinline__ int vx_rows(const int* __restrict__ n_rows, int R) {
+    if (!n_rows) return R;
+    const int n = *n_rows;
+    return n < 0 ? 0 : (n < R ? n : R);
+}
+
+// out[y] = max(out[y], bits(max |x[y * stride + i]|, i < n)) -- non-negative floats order like their bit patterns; with a
+// row count, i < rows in use * per_row
+__global__ __launch_bounds__(256) void vx_absmax_kernel(const float* __restrict__ x, long n, long stride, unsigned* __restrict__ out, int out_stride,
+                                                        const int* __restrict__ n_rows, int cap, int per_row) {
     const float* __restrict__ p = x + (long)blockIdx.y * stride;
+    if (n_rows) n = (long)vx_rows(n_rows, cap) * per_row;
     float mx = 0.f;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) mx = fmaxf(mx, fabsf(p[i]));
     mx = vx_wave_max(mx);
@@ -72,11 +88,14 @@ __global__ __launch_bounds__(256) void vx_absmax_kernel(const float* __restrict_
 // dW^T = H^T P with the examples in accumulator order), hi and lo halves, scaled by one power of two for the whole matrix.
 template <int KT>
 __global__ __launch_bounds__(64) void vx_pack_hidden_kernel(const float* __restrict__ H, long ldh, int R, const unsigned* __restrict__ hmax,
-                                                            h8* __restrict__ Hf, h8* __restrict__ HTf, float* __restrict__ hscale) {
+                                                            h8* __restrict__ Hf, h8* __restrict__ HTf, float* __restrict__ hscale,
+                                                            const int* __restrict__ n_rows) {
     constexpr int KS = 2 * KT;
     const int t = blockIdx.x, lane = threadIdx.x, c = lane & 31, hh = lane >> 5;
     const float sH = x3_pow2_scale(__uint_as_float(*hmax), 12);
     if (t == 0 && lane == 0) { hscale[0] = sH; hscale[1] = 1.f / sH; }
+    R = vx_rows(n_rows, R);                 // absent rows pack as zeros; no kernel reads a tile beyond the last one in use
+    if (32 * t >= R) return;
     const int row = 32 * t + c;
 #pragma unroll
     for (int s = 0; s < KS; ++s) {
@@ -117,13 +136,15 @@ __global__ __launch_bounds__(64) void vx_pack_hidden_kernel(const float* __restr
 
 // Upstream gradients g [F][R] -> gpack = [F][4] headers {sP, 1/sP, bits of max|g|, 0} then [F][Rpad] rows gs = g * sP (0 for
 // the padding rows); sP = the power of two that puts the field's max|g| just below 2^15 (P = g * softmax <= max|g| in fp16).
-__global__ __launch_bounds__(256) void vx_pack_g_kernel(const float* __restrict__ g, int R, int Rpad, int F, float* __restrict__ gpack) {
+__global__ __launch_bounds__(256) void vx_pack_g_kernel(const float* __restrict__ g, int R, int Rpad, int F, float* __restrict__ gpack,
+                                                        const int* __restrict__ n_rows) {
     const int f = blockIdx.y;
+    const int n = vx_rows(n_rows, R);
     float* __restrict__ hdr = gpack + 4 * f;
     const float sP = x3_pow2_scale(__uint_as_float(reinterpret_cast<const unsigned*>(hdr)[2]), 15);
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i == 0) { hdr[0] = sP; hdr[1] = 1.f / sP; }
-    if (i < Rpad) gpack[4L * F + (long)f * Rpad + i] = i < R ? g[(long)f * R + i] * sP : 0.f;
+    if (i < Rpad) gpack[4L * F + (long)f * Rpad + i] = i < n ? g[(long)f * R + i] * sP : 0.f;
 }
 
 typedef xdfm_vce_field VxField;
@@ -141,8 +162,13 @@ template <int KT, int MODE>
 __global__ __launch_bounds__(64 * VX_WAVES) void vx_hs_kernel(
     const h8* __restrict__ Hf, const float* __restrict__ hscale, int ntiles, const VxField* __restrict__ fields,
     const VxItem* __restrict__ items, int F, unsigned* __restrict__ wmax_all, const float* __restrict__ lse2_all,
-    const float* __restrict__ gpack, float* __restrict__ ws, long Rpad) {
+    const float* __restrict__ gpack, float* __restrict__ ws, long Rpad, const int* __restrict__ n_rows) {
     constexpr int KS = 2 * KT, K = 32 * KT;
+    if (n_rows) {                                          // a row group behind the count has nothing to do (workgroup-uniform)
+        const int n = vx_rows(n_rows, 32 * ntiles);
+        if ((int)blockIdx.y * VX_RG >= n) return;
+        ntiles = (n + 31) / 32;                            // tiles behind the last one in use are absent, as behind the capacity
+    }
     const VxItem item = items[blockIdx.x];                 // (field, vocabulary stages [sb0, sb1), index of the range)
     const VxField fd = fields[item.field];
     const float* __restrict__ W = fd.W;
@@ -454,9 +480,14 @@ __global__ __launch_bounds__(64 * VX_WAVES) void vx_hs_kernel(
 // fmas, write ce = lse - z_target and the base-2 log-sum-exp the backward reuses.
 __global__ __launch_bounds__(256) void vx_lse_merge_kernel(const float* __restrict__ ws, const VxField* __restrict__ fields, long Rpad, int R,
                                                            const float* __restrict__ H, long ldh, const long* __restrict__ tgt_all, int K,
-                                                           float* __restrict__ ce, float* __restrict__ lse2) {
+                                                           float* __restrict__ ce, float* __restrict__ lse2, const int* __restrict__ n_rows) {
     const int r = blockIdx.x * 256 + threadIdx.x, f = blockIdx.y;
-    if (r >= R) return;
+    if (r >= Rpad) return;
+    if (r >= vx_rows(n_rows, R)) {                             // absent and padding rows: finite values for the backward's tile ring
+        lse2[(long)f * Rpad + r] = 0.f;
+        if (r < R) ce[(long)f * R + r] = 0.f;
+        return;
+    }
     const VxField fd = fields[f];
     const float2* __restrict__ part = reinterpret_cast<const float2*>(ws + fd.ws_off);
     float M = VX_NEG;
@@ -477,12 +508,16 @@ __global__ __launch_bounds__(256) void vx_lse_merge_kernel(const float* __restri
 // dh[r][k..k+4) = sum over fields (in order) of [sum over the field's ranges (in order) of its slabs - g[f][r] * W_f[target]]
 __global__ __launch_bounds__(256) void vx_dh_merge_kernel(const float* __restrict__ ws, const VxField* __restrict__ fields, int F, long Rpad,
                                                           int R, int K, const float* __restrict__ g, const long* __restrict__ tgt_all,
-                                                          float* __restrict__ dh, long lddh) {
+                                                          float* __restrict__ dh, long lddh, const int* __restrict__ n_rows) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const int k4 = K / 4;
     if (i >= (long)R * k4) return;
     const int r = (int)(i / k4), k = 4 * (int)(i % k4);
     float4 tot = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (r >= vx_rows(n_rows, R)) {
+        *reinterpret_cast<float4*>(dh + (long)r * lddh + k) = tot;
+        return;
+    }
     for (int f = 0; f < F; ++f) {
         const VxField fd = fields[f];
         const float* __restrict__ slab = ws + fd.ws_off;
@@ -518,7 +553,7 @@ template <int KT>
 __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
     const h8* __restrict__ Hf, const h8* __restrict__ HTf, const float* __restrict__ hscale, int ntiles,
     const VxField* __restrict__ fields, int F, int nblk_all, const unsigned* __restrict__ wmax_all, const float* __restrict__ lse2_all,
-    const float* __restrict__ gpack, const long* __restrict__ tgt_all, int R, long Rpad, int dbg) {
+    const float* __restrict__ gpack, const long* __restrict__ tgt_all, int R, long Rpad, int dbg, const int* __restrict__ n_rows) {
     // dbg (option "dbg", bits 20..23; timing experiments, results become wrong): 1 = no exponentials / target test / split,
     // 2 = no dW MFMAs, 4 = no z MFMAs, 8 = no tile ring traffic and no barriers
     constexpr int KS = 2 * KT, K = 32 * KT;
@@ -529,12 +564,25 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
     extern __shared__ __attribute__((aligned(16))) char ws_smem[];
     VxSlotLds<KT>* const L = reinterpret_cast<VxSlotLds<KT>*>(ws_smem);            // ring of 3 slots
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 31, hh = lane >> 5;
+    const int cap = R;                                  // the targets' row pitch; R becomes the rows in use
+    R = vx_rows(n_rows, R);
+    ntiles = (R + 31) / 32;                             // the tiles behind the count are not walked
     const int nslots = (ntiles + VX_WS_TP - 1) / VX_WS_TP;
 
     for (int gb = blockIdx.x; gb < nblk_all; gb += gridDim.x) {
         int f = 0;
         while (f + 1 < F && fields[f + 1].blk0 <= gb) ++f;              // the field this block of 256 vocabulary rows belongs to
         const VxField fd = fields[f];
+        if (ntiles == 0) {                              // no row at all: the gradients are exact zeros, no scale is read
+            const long v0 = (long)(gb - fd.blk0) * (32 * VX_WS_WAVES) + 32 * w + c;
+            if (v0 < fd.V) {
+                if (hh == 0 && fd.db) fd.db[v0] = 0.f;
+                if (fd.dW)
+                    for (int k = 16 * KT * hh; k < 16 * KT * (hh + 1); k += 4)
+                        *reinterpret_cast<float4*>(fd.dW + v0 * K + k) = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            continue;
+        }
         const float* __restrict__ W = fd.W;
         const float* __restrict__ bias = fd.bias;
         float* __restrict__ dW = fd.dW;
@@ -542,7 +590,7 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
         const int V = fd.V, blk = gb - fd.blk0;
         const float* __restrict__ lse2 = lse2_all + (long)f * Rpad;
         const float* __restrict__ gs = gpack + 4L * F + (long)f * Rpad;
-        const long* __restrict__ tgt = tgt_all + (long)f * R;
+        const long* __restrict__ tgt = tgt_all + (long)f * cap;
         const float sW = x3_pow2_scale(__uint_as_float(wmax_all[f]), 12);
         const float cw = VX_LOG2E * hscale[1] / sW;
         const float icw = -1.f / cw;                           // the tiles' lse values are parked as -lse / cw: z starts there
@@ -754,7 +802,7 @@ long xdfm_vocab_ce_plan(int F, const int* V, int R, int K, xdfm_vce_field* field
     return n;
 }
 
-int xdfm_vocab_ce_pack_hidden(const float* H, long ldh, int R, int K, float* pack, void* stream) {
+int xdfm_vocab_ce_pack_hidden_n(const float* H, long ldh, int R, int K, float* pack, const int* n_rows, void* stream) {
     XDFM_REQUIRE(H && pack, "vocab_ce_pack_hidden: null pointer");
     XDFM_REQUIRE(R > 0 && vx_k_ok(K) && ldh == K, "vocab_ce_pack_hidden: bad shape R=%d K=%d ld=%ld (rows must be contiguous)", R, K, ldh);
     hipStream_t st = (hipStream_t)stream;
@@ -763,17 +811,21 @@ int xdfm_vocab_ce_pack_hidden(const float* H, long ldh, int R, int K, float* pac
     const int tiles = ceil_div(R, 32);
     int gx = ceil_div((long)R * K, 256 * 8);
     gx = gx < 1 ? 1 : (gx > 256 ? 256 : gx);
-    hipLaunchKernelGGL(vx_absmax_kernel, dim3(gx, 1), dim3(256), 0, st, H, (long)R * K, 0L, hmax, 0);
+    hipLaunchKernelGGL(vx_absmax_kernel, dim3(gx, 1), dim3(256), 0, st, H, (long)R * K, 0L, hmax, 0, n_rows, R, K);
     h8* Hf = reinterpret_cast<h8*>(pack + 16);
     h8* HTf = Hf + (long)tiles * (K / 16) * 2 * 64;
-    if (K == 64) hipLaunchKernelGGL((vx_pack_hidden_kernel<2>), dim3(tiles), dim3(64), 0, st, H, ldh, R, hmax, Hf, HTf, pack);
-    else hipLaunchKernelGGL((vx_pack_hidden_kernel<1>), dim3(tiles), dim3(64), 0, st, H, ldh, R, hmax, Hf, HTf, pack);
+    if (K == 64) hipLaunchKernelGGL((vx_pack_hidden_kernel<2>), dim3(tiles), dim3(64), 0, st, H, ldh, R, hmax, Hf, HTf, pack, n_rows);
+    else hipLaunchKernelGGL((vx_pack_hidden_kernel<1>), dim3(tiles), dim3(64), 0, st, H, ldh, R, hmax, Hf, HTf, pack, n_rows);
     return xdfm_check_launch("vocab_ce_pack_hidden");
 }
 
-int xdfm_vocab_ce_fwd(const float* pack, const float* H, long ldh, int R, int K, const xdfm_vce_field* fields, int F,
-                      const xdfm_vce_item* items, long n_items, const long* targets, float* ws, float* ce, float* lse2,
-                      unsigned* wmax, void* stream) {
+int xdfm_vocab_ce_pack_hidden(const float* H, long ldh, int R, int K, float* pack, void* stream) {
+    return xdfm_vocab_ce_pack_hidden_n(H, ldh, R, K, pack, nullptr, stream);
+}
+
+int xdfm_vocab_ce_fwd_n(const float* pack, const float* H, long ldh, int R, int K, const xdfm_vce_field* fields, int F,
+                        const xdfm_vce_item* items, long n_items, const long* targets, float* ws, float* ce, float* lse2,
+                        unsigned* wmax, const int* n_rows, void* stream) {
     XDFM_REQUIRE(pack && H && fields && items && targets && ws && ce && lse2 && wmax, "vocab_ce_fwd: null pointer");
     XDFM_REQUIRE(R > 0 && F > 0 && n_items > 0 && vx_k_ok(K) && ldh >= K, "vocab_ce_fwd: bad shape R=%d K=%d F=%d", R, K, F);
     hipStream_t st = (hipStream_t)stream;
@@ -784,29 +836,41 @@ int xdfm_vocab_ce_fwd(const float* pack, const float* H, long ldh, int R, int K,
     const dim3 grid((unsigned)n_items, ceil_div(R, VX_RG)), block(64 * VX_WAVES);
     if (K == 64)
         hipLaunchKernelGGL((vx_hs_kernel<2, 0>), grid, block, (VxLds<2, 0>::bytes), st, Hf, pack, ntiles, fields, items, F, wmax,
-                           (const float*)nullptr, (const float*)nullptr, ws, Rpad);
+                           (const float*)nullptr, (const float*)nullptr, ws, Rpad, n_rows);
     else
         hipLaunchKernelGGL((vx_hs_kernel<1, 0>), grid, block, (VxLds<1, 0>::bytes), st, Hf, pack, ntiles, fields, items, F, wmax,
-                           (const float*)nullptr, (const float*)nullptr, ws, Rpad);
-    hipLaunchKernelGGL(vx_lse_merge_kernel, dim3(ceil_div(R, 256), F), dim3(256), 0, st, ws, fields, Rpad, R, H, ldh, targets, K, ce, lse2);
+                           (const float*)nullptr, (const float*)nullptr, ws, Rpad, n_rows);
+    hipLaunchKernelGGL(vx_lse_merge_kernel, dim3(ceil_div(Rpad, 256), F), dim3(256), 0, st, ws, fields, Rpad, R, H, ldh, targets, K, ce, lse2,
+                       n_rows);
     return xdfm_check_launch("vocab_ce_fwd");
 }
 
-int xdfm_vocab_ce_pack_g(const float* g, int F, int R, float* gpack, void* stream) {
+int xdfm_vocab_ce_fwd(const float* pack, const float* H, long ldh, int R, int K, const xdfm_vce_field* fields, int F,
+                      const xdfm_vce_item* items, long n_items, const long* targets, float* ws, float* ce, float* lse2,
+                      unsigned* wmax, void* stream) {
+    return xdfm_vocab_ce_fwd_n(pack, H, ldh, R, K, fields, F, items, n_items, targets, ws, ce, lse2, wmax, nullptr, stream);
+}
+
+int xdfm_vocab_ce_pack_g_n(const float* g, int F, int R, float* gpack, const int* n_rows, void* stream) {
     XDFM_REQUIRE(g && gpack && R > 0 && F > 0, "vocab_ce_pack_g: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const long Rpad = vx_rows_padded(R);
     hipLaunchKernelGGL(vx_zero_words_kernel, dim3(ceil_div(F, 64)), dim3(64), 0, st, reinterpret_cast<unsigned*>(gpack) + 2, F, 4);
     int gx = ceil_div(R, 2048);
     gx = gx > 64 ? 64 : gx;
-    hipLaunchKernelGGL(vx_absmax_kernel, dim3(gx, F), dim3(256), 0, st, g, (long)R, (long)R, reinterpret_cast<unsigned*>(gpack) + 2, 4);
-    hipLaunchKernelGGL(vx_pack_g_kernel, dim3(ceil_div(Rpad, 256), F), dim3(256), 0, st, g, R, (int)Rpad, F, gpack);
+    hipLaunchKernelGGL(vx_absmax_kernel, dim3(gx, F), dim3(256), 0, st, g, (long)R, (long)R, reinterpret_cast<unsigned*>(gpack) + 2, 4,
+                       n_rows, R, 1);
+    hipLaunchKernelGGL(vx_pack_g_kernel, dim3(ceil_div(Rpad, 256), F), dim3(256), 0, st, g, R, (int)Rpad, F, gpack, n_rows);
     return xdfm_check_launch("vocab_ce_pack_g");
 }
 
-int xdfm_vocab_ce_bwd_h(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, const xdfm_vce_item* items, long n_items,
-                        const long* targets, const float* g, const float* gpack, const float* lse2, unsigned* wmax, float* ws,
-                        float* dh, long lddh, void* stream) {
+int xdfm_vocab_ce_pack_g(const float* g, int F, int R, float* gpack, void* stream) {
+    return xdfm_vocab_ce_pack_g_n(g, F, R, gpack, nullptr, stream);
+}
+
+int xdfm_vocab_ce_bwd_h_n(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, const xdfm_vce_item* items, long n_items,
+                          const long* targets, const float* g, const float* gpack, const float* lse2, unsigned* wmax, float* ws,
+                          float* dh, long lddh, const int* n_rows, void* stream) {
     XDFM_REQUIRE(pack && fields && items && targets && g && gpack && lse2 && wmax && ws && dh, "vocab_ce_bwd_h: null pointer");
     XDFM_REQUIRE(R > 0 && F > 0 && n_items > 0 && vx_k_ok(K) && lddh >= K && lddh % 4 == 0, "vocab_ce_bwd_h: bad shape R=%d K=%d F=%d", R, K, F);
     hipStream_t st = (hipStream_t)stream;
@@ -816,17 +880,23 @@ int xdfm_vocab_ce_bwd_h(const float* pack, int R, int K, const xdfm_vce_field* f
     const dim3 grid((unsigned)n_items, ceil_div(R, VX_RG)), block(64 * VX_WAVES);
     if (K == 64)
         hipLaunchKernelGGL((vx_hs_kernel<2, 1>), grid, block, (VxLds<2, 1>::bytes), st, Hf, pack, ntiles, fields, items, F, wmax, lse2, gpack,
-                           ws, Rpad);
+                           ws, Rpad, n_rows);
     else
         hipLaunchKernelGGL((vx_hs_kernel<1, 1>), grid, block, (VxLds<1, 1>::bytes), st, Hf, pack, ntiles, fields, items, F, wmax, lse2, gpack,
-                           ws, Rpad);
+                           ws, Rpad, n_rows);
     hipLaunchKernelGGL(vx_dh_merge_kernel, dim3(ceil_div((long)R * (K / 4), 256)), dim3(256), 0, st, ws, fields, F, Rpad, R, K, g, targets,
-                       dh, lddh);
+                       dh, lddh, n_rows);
     return xdfm_check_launch("vocab_ce_bwd_h");
 }
 
-int xdfm_vocab_ce_bwd_w(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, int n_blk, const long* targets,
-                        const float* gpack, const float* lse2, const unsigned* wmax, void* stream) {
+int xdfm_vocab_ce_bwd_h(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, const xdfm_vce_item* items, long n_items,
+                        const long* targets, const float* g, const float* gpack, const float* lse2, unsigned* wmax, float* ws,
+                        float* dh, long lddh, void* stream) {
+    return xdfm_vocab_ce_bwd_h_n(pack, R, K, fields, F, items, n_items, targets, g, gpack, lse2, wmax, ws, dh, lddh, nullptr, stream);
+}
+
+int xdfm_vocab_ce_bwd_w_n(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, int n_blk, const long* targets,
+                          const float* gpack, const float* lse2, const unsigned* wmax, const int* n_rows, void* stream) {
     XDFM_REQUIRE(pack && fields && targets && gpack && lse2 && wmax, "vocab_ce_bwd_w: null pointer");
     XDFM_REQUIRE(R > 0 && F > 0 && n_blk > 0 && vx_k_ok(K), "vocab_ce_bwd_w: bad shape R=%d K=%d F=%d", R, K, F);
     hipStream_t st = (hipStream_t)stream;
@@ -838,11 +908,16 @@ int xdfm_vocab_ce_bwd_w(const float* pack, int R, int K, const xdfm_vce_field* f
     const int dbg = (xdfm_opt(OPT_DBG) >> 20) & 15;
     if (K == 64)
         hipLaunchKernelGGL((vx_ws_kernel<2>), dim3(grid), dim3(64 * VX_WS_WAVES), 3 * sizeof(VxSlotLds<2>), st, Hf, HTf, pack, tiles, fields, F,
-                           n_blk, wmax, lse2, gpack, targets, R, Rpad, dbg);
+                           n_blk, wmax, lse2, gpack, targets, R, Rpad, dbg, n_rows);
     else
         hipLaunchKernelGGL((vx_ws_kernel<1>), dim3(grid), dim3(64 * VX_WS_WAVES), 3 * sizeof(VxSlotLds<1>), st, Hf, HTf, pack, tiles, fields, F,
-                           n_blk, wmax, lse2, gpack, targets, R, Rpad, dbg);
+                           n_blk, wmax, lse2, gpack, targets, R, Rpad, dbg, n_rows);
     return xdfm_check_launch("vocab_ce_bwd_w");
+}
+
+int xdfm_vocab_ce_bwd_w(const float* pack, int R, int K, const xdfm_vce_field* fields, int F, int n_blk, const long* targets,
+                        const float* gpack, const float* lse2, const unsigned* wmax, void* stream) {
+    return xdfm_vocab_ce_bwd_w_n(pack, R, K, fields, F, n_blk, targets, gpack, lse2, wmax, nullptr, stream);
 }
 
 }  // extern "C"

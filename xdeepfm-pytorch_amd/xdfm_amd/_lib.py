@@ -105,6 +105,13 @@ SIGNATURES = {
     "xdfm_vocab_ce_pack_g": (c_int, [P, c_int, c_int, P, P]),
     "xdfm_vocab_ce_bwd_h": (c_int, [P, c_int, c_int, P, c_int, P, c_long, P, P, P, P, P, P, P, c_long, P]),
     "xdfm_vocab_ce_bwd_w": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, P, P]),
+    "xdfm_vocab_ce_pack_hidden_n": (c_int, [P, c_long, c_int, c_int, P, P, P]),
+    "xdfm_vocab_ce_fwd_n": (c_int, [P, P, c_long, c_int, c_int, P, c_int, P, c_long, P, P, P, P, P, P, P]),
+    "xdfm_vocab_ce_pack_g_n": (c_int, [P, c_int, c_int, P, P, P]),
+    "xdfm_vocab_ce_bwd_h_n": (c_int, [P, c_int, c_int, P, c_int, P, c_long, P, P, P, P, P, P, P, c_long, P, P]),
+    "xdfm_vocab_ce_bwd_w_n": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P]),
+    "xdfm_compact_rows_fwd": (c_int, [P, c_long, c_int, P, c_long, P, c_long, c_int, P, c_int, c_int, P, P, P, P, P, P, P, P]),
+    "xdfm_compact_rows_bwd": (c_int, [P, c_long, P, c_long, c_int, P, P]),
     "xdfm_autodis_supported": (c_int, [c_int, c_int]),
     "xdfm_autodis_ws_elems": (c_size_t, [c_long, c_int, c_int, c_int]),
     "xdfm_autodis_fwd": (c_int, [P, c_long, c_long, c_int, c_int, c_int, P, P, P, P, P]),

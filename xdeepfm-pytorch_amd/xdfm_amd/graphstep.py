@@ -17,7 +17,8 @@ Guards:
     change re-captures;
   * anything unexpected (capture error, unsupported optimizer, row-parallel run, profiling hooks)
     falls back to the eager step, permanently for that model after a capture error.
-`XDFM_HIP_GRAPH=0` disables the replay.
+`XDFM_HIP_GRAPH=0` disables the replay.  xDeepFMPro's step is captured when its SFG branch takes the static route
+(xdfm_amd/pro.py, `XDFM_PRO_GRAPH`).
 """
 import ctypes
 import gc
@@ -43,10 +44,12 @@ def census(graph: "torch.cuda.CUDAGraph"):
 
 
 class _Entry(object):
-    __slots__ = ("sig", "eager", "graph", "sx", "sy", "out", "nodes")
+    __slots__ = ("sig", "eager", "graph", "sx", "sy", "out", "nodes", "extra", "log")
 
     def __init__(self, sig):
         self.sig, self.eager, self.graph, self.sx, self.sy, self.out, self.nodes = sig, 0, None, None, None, None, 0
+        # what the model's `_loss_forward` left in `_step_extra` / `_step_log` during the capture: tensors of THIS graph
+        self.extra = self.log = None
 
 
 class GraphedStep(object):
@@ -122,6 +125,12 @@ class GraphedStep(object):
             m.optim.note_replay()          # deferred table update: periodic flush, step count (the step's Python does not run)
         ent.graph.replay()
         self.replays += 1
+        # the step's Python does not run on replay: a model that logs a value per step (xDeepFMPro's sfg_loss) must find
+        # the tensors of the graph that just ran, not those of the shape captured last (full batch / tail batch)
+        if ent.extra is not None or "_step_extra" in m.__dict__:
+            m.__dict__["_step_extra"] = ent.extra
+        if ent.log is not None or "_step_log" in m.__dict__:
+            m.__dict__["_step_log"] = ent.log
         if dp is not None:          # captured: the first half; exchange, scatter, all-reduce and optimizer follow eagerly
             y_pred, loss, stash = ent.out
             return m._split_step_second(y_pred, loss, stash, m._l2_fusion())
@@ -167,11 +176,13 @@ class GraphedStep(object):
                                    % (n_memset, n_other, n))
             g.instantiate()
             ent.graph, ent.out, ent.nodes = g, out, n
+            extra = m.__dict__.get("_step_extra")
+            ent.extra, ent.log = None if extra is None else extra.detach(), m.__dict__.get("_step_log")
             return True
         except Exception as exc:      # noqa: BLE001 -- any failure means: keep training eagerly
             warnings.warn("xdfm: HIP-graph capture of the train step failed (%s); continuing with eager launches" % (exc,))
             self.disabled = True
-            ent.graph = ent.sx = ent.sy = ent.out = None
+            ent.graph = ent.sx = ent.sy = ent.out = ent.extra = ent.log = None
             if m._plan is not None:
                 m._plan.reg_defer = None
             return False

@@ -1064,8 +1064,8 @@ def _vce_plan(R, K, vocabs, dev):
         lib.xdfm_vocab_ce_plan(len(vocabs), V.ctypes.data, R, K, fields.ctypes.data, items.ctypes.data, n, ctypes.byref(ws),
                                ctypes.byref(nblk))
         items_dev = torch.from_numpy(items.view(np.uint8)).to(dev)
-        if len(_VCE_PLANS) > 64:
-            _VCE_PLANS.clear()
+        if len(_VCE_PLANS) > 64:               # the dynamic route asks for a new row count almost every step; a plan a captured
+            _VCE_PLANS.clear()                 # step uses is also held by its VocabHeadsState, which never lets go of it
         plan = _VCE_PLANS[key] = (fields, items_dev, int(n), int(ws.value), int(nblk.value))
     return plan
 
@@ -1079,18 +1079,62 @@ def _vce_fields(plan, Ws, bs, dWs, dbs, dev):
     return torch.from_numpy(fields.view(np.uint8)).to(dev)
 
 
+class VocabHeadsState:
+    """What `VocabHeadsCE` keeps across steps for one set of heads (a model owns one): the gradient tensors of the head
+    parameters and, per (capacity, K), the field table on the device.  The table holds the pointers of W, bias, dW and
+    db; all four are stable from step to step, so it is uploaded once -- outside any graph capture -- and again only
+    when a pointer changed (`EmbedPlan.pointer_table` is the same pattern).  The forward and the backward read the same
+    table.  The gradients handed to autograd are fresh views of the kept tensors: a second backward before the optimizer
+    step would overwrite the first one's result, so the state serves a train step with ONE backward per forward (the
+    models pass it inside their own step only; everything else allocates per call)."""
+
+    def __init__(self):
+        self.grads = None        # (key, dWs, dbs)
+        # (plan key, pointers) -> (plan, device table).  Nothing is ever evicted: a captured train step addresses the
+        # plan's work items, the table and the gradient tensors by raw pointer and replays without running Python, so
+        # this object is their only owner for as long as the model lives.  One entry per batch shape (a few hundred
+        # bytes each) and per set of parameter addresses.
+        self.tables = {}
+        self.current = {}        # plan key -> the pointers of the table in use
+        self.retired = []        # gradient tensors replaced after the parameters moved
+
+    def grad_buffers(self, Ws, bs):
+        key = tuple((t.data_ptr(), tuple(t.shape), t.device) for t in tuple(Ws) + tuple(bs))
+        if self.grads is None or self.grads[0] != key:
+            if self.grads is not None:
+                self.retired.append(self.grads)
+            self.grads = (key, [torch.empty_like(w) for w in Ws], [torch.empty_like(b) for b in bs])
+        return self.grads[1], self.grads[2]
+
+    def table(self, plan_key, Ws, bs, dWs, dbs, dev):
+        """(plan, device table) for this capacity and these tensors."""
+        ptrs = tuple(t.data_ptr() for t in tuple(Ws) + tuple(bs) + tuple(dWs) + tuple(dbs))
+        hit = self.tables.get((plan_key, ptrs))
+        if hit is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("xdfm: the vocabulary heads' field table is stale inside a graph capture -- run the step "
+                                   "once eagerly with these parameters and this batch shape before capturing it")
+            R, K, vocabs, _ = plan_key
+            plan = _vce_plan(R, K, list(vocabs), dev)
+            hit = self.tables[(plan_key, ptrs)] = (plan, _vce_fields(plan, Ws, bs, dWs, dbs, dev))
+        self.current[plan_key] = ptrs
+        return hit
+
+
 class VocabHeadsCE(torch.autograd.Function):
     """ce[f][r] of ALL sparse fields' heads over the same hidden rows, logits never in HBM (csrc/vocab_ce_x3.hip; the
     heads of deepctr/xdeepfm_pro/sfg_decoder.py:146-149 + F.cross_entropy of :277-283).  hidden [R, K] (K = 32 or 64),
-    targets [F, R] int64, then the F weights [V_f, K] and the F biases [V_f].  The hidden layer is packed into MFMA
-    fragments once per pass; all fields share each launch (a table of per-field pointers and work items): log-sum-exp
-    partials + merge in the forward; in the backward the hidden gradient (partial slabs summed in a fixed order) and
-    the weight / bias gradients (every row written once, the target's -g included)."""
+    targets [F, R] int64, n_rows (None, or one int32 on the device: the rows in use, R is then a capacity -- rows behind the
+    count are never read, their ce and dh are exact zeros, they add nothing to dW / db, and every launch and shape is that
+    of the capacity), state (None or a `VocabHeadsState`), then the F weights [V_f, K] and the F biases [V_f].  The hidden
+    layer is packed into MFMA fragments once per pass; all fields share each launch (a table of per-field pointers and
+    work items): log-sum-exp partials + merge in the forward; in the backward the hidden gradient (partial slabs summed in
+    a fixed order) and the weight / bias gradients (every row written once, the target's -g included)."""
 
     calls = 0                 # forward passes taken (tests assert that a golden reached this path)
 
     @staticmethod
-    def forward(ctx, hidden, targets, *params):
+    def forward(ctx, hidden, targets, n_rows, state, *params):
         lib = _lib.load()
         VocabHeadsCE.calls += 1
         F_ = len(params) // 2
@@ -1102,21 +1146,33 @@ class VocabHeadsCE(torch.autograd.Function):
         for t in params:
             if not t.is_contiguous():
                 raise ValueError("xdfm: head parameters must be contiguous")
-        plan = _vce_plan(R, K, [w.shape[0] for w in Ws], dev)
-        fields = _vce_fields(plan, Ws, bs, [None] * F_, [None] * F_, dev)
+        if n_rows is not None and not (n_rows.is_cuda and n_rows.dtype == torch.int32 and n_rows.numel() == 1):
+            raise ValueError("xdfm: n_rows must be one int32 on the device")
+        plan_key = (R, K, tuple(w.shape[0] for w in Ws), dev)
+        need = ctx.needs_input_grad
+        # kept gradient tensors only when nothing is accumulated into: a .grad left in place would alias them
+        if state is not None and all(need[4:]) and all(p.grad is None for p in params):
+            dWs, dbs = state.grad_buffers(Ws, bs)
+            plan, fields = state.table(plan_key, Ws, bs, dWs, dbs, dev)
+            ctx.kept = (fields, dWs, dbs)
+        else:
+            plan = _vce_plan(R, K, [w.shape[0] for w in Ws], dev)
+            fields = _vce_fields(plan, Ws, bs, [None] * F_, [None] * F_, dev)
+            ctx.kept = None
         pack = torch.empty(lib.xdfm_vocab_ce_pack_elems(R, K), dtype=torch.float32, device=dev)
-        _lib.check(lib.xdfm_vocab_ce_pack_hidden(_ptr(hidden), K, R, K, _ptr(pack), _stream()), "vocab_ce_pack_hidden")
+        _lib.check(lib.xdfm_vocab_ce_pack_hidden_n(_ptr(hidden), K, R, K, _ptr(pack), _ptr(n_rows), _stream()), "vocab_ce_pack_hidden")
         Rpad = lib.xdfm_vocab_ce_rows_padded(R)
         ce = torch.empty(F_, R, dtype=torch.float32, device=dev)
-        lse2 = torch.zeros(F_, Rpad, dtype=torch.float32, device=dev)
+        lse2 = torch.empty(F_, Rpad, dtype=torch.float32, device=dev)
         wmax = torch.empty(F_, dtype=torch.int32, device=dev)
         ws = torch.empty(plan[3], dtype=torch.float32, device=dev)
         flops = 2.0 * R * K * sum(w.shape[0] for w in Ws)                  # of the reference's nn.Linear, all heads
-        _lib.check(_run("vocab_ce_fwd", flops, lambda: lib.xdfm_vocab_ce_fwd(
+        _lib.check(_run("vocab_ce_fwd", flops, lambda: lib.xdfm_vocab_ce_fwd_n(
             _ptr(pack), _ptr(hidden), K, R, K, _ptr(fields), F_, _ptr(plan[1]), plan[2], _ptr(targets), _ptr(ws), _ptr(ce), _ptr(lse2),
-            _ptr(wmax), _stream())), "vocab_ce_fwd")
+            _ptr(wmax), _ptr(n_rows), _stream())), "vocab_ce_fwd")
         ctx.save_for_backward(hidden, targets, pack, lse2, wmax, *params)
         ctx.plan = plan
+        ctx.n_rows = n_rows
         return ce
 
     @staticmethod
@@ -1129,36 +1185,102 @@ class VocabHeadsCE(torch.autograd.Function):
         R, K = hidden.shape
         dev = hidden.device
         plan = ctx.plan
+        n_rows = ctx.n_rows
         g = g.contiguous()
         Rpad = lib.xdfm_vocab_ce_rows_padded(R)
         gpack = torch.empty(F_ * (4 + Rpad), dtype=torch.float32, device=dev)
         flops = 2.0 * R * K * sum(w.shape[0] for w in Ws)     # per product of the reference's backward (dH; dW), recompute not counted
-        _lib.check(lib.xdfm_vocab_ce_pack_g(_ptr(g), F_, R, _ptr(gpack), _stream()), "vocab_ce_pack_g")
-        dWs = [torch.empty_like(Ws[f]) if ctx.needs_input_grad[2 + f] else None for f in range(F_)]
-        dbs = [torch.empty_like(bs[f]) if ctx.needs_input_grad[2 + F_ + f] else None for f in range(F_)]
-        fields = _vce_fields(plan, Ws, bs, dWs, dbs, dev)
+        _lib.check(lib.xdfm_vocab_ce_pack_g_n(_ptr(g), F_, R, _ptr(gpack), _ptr(n_rows), _stream()), "vocab_ce_pack_g")
+        if ctx.kept is not None:
+            fields, dWs, dbs = ctx.kept
+        else:
+            dWs = [torch.empty_like(Ws[f]) if ctx.needs_input_grad[4 + f] else None for f in range(F_)]
+            dbs = [torch.empty_like(bs[f]) if ctx.needs_input_grad[4 + F_ + f] else None for f in range(F_)]
+            fields = _vce_fields(plan, Ws, bs, dWs, dbs, dev)
         dh = None
         if ctx.needs_input_grad[0]:
             dh = torch.empty_like(hidden)
             ws = torch.empty(plan[3], dtype=torch.float32, device=dev)
-            _lib.check(_run("vocab_ce_bwd_h", flops, lambda: lib.xdfm_vocab_ce_bwd_h(
+            _lib.check(_run("vocab_ce_bwd_h", flops, lambda: lib.xdfm_vocab_ce_bwd_h_n(
                 _ptr(pack), R, K, _ptr(fields), F_, _ptr(plan[1]), plan[2], _ptr(targets), _ptr(g), _ptr(gpack), _ptr(lse2), _ptr(wmax),
-                _ptr(ws), _ptr(dh), K, _stream())), "vocab_ce_bwd_h")
+                _ptr(ws), _ptr(dh), K, _ptr(n_rows), _stream())), "vocab_ce_bwd_h")
         if any(t is not None for t in dWs + dbs):
-            _lib.check(_run("vocab_ce_bwd_w", flops, lambda: lib.xdfm_vocab_ce_bwd_w(
-                _ptr(pack), R, K, _ptr(fields), F_, plan[4], _ptr(targets), _ptr(gpack), _ptr(lse2), _ptr(wmax), _stream())),
-                "vocab_ce_bwd_w")
-        return (dh, None, *dWs, *dbs)
+            _lib.check(_run("vocab_ce_bwd_w", flops, lambda: lib.xdfm_vocab_ce_bwd_w_n(
+                _ptr(pack), R, K, _ptr(fields), F_, plan[4], _ptr(targets), _ptr(gpack), _ptr(lse2), _ptr(wmax), _ptr(n_rows),
+                _stream())), "vocab_ce_bwd_w")
+        if ctx.kept is not None:                  # fresh views: autograd may adopt them as .grad without a copy
+            dWs, dbs = [t.view_as(t) for t in dWs], [t.view_as(t) for t in dbs]
+        return (dh, None, None, None, *dWs, *dbs)
 
 
 def vocab_heads_ce_supported(K: int) -> bool:
     return bool(_lib.load().xdfm_vocab_ce_x3_supported(int(K)))
 
 
-def vocab_heads_ce(hidden, targets, weights, biases):
-    """[F, R] cross-entropies of F heads (weights[f] [V_f, K], biases[f] [V_f]) over hidden [R, K], targets [F, R] int64."""
+def vocab_heads_ce(hidden, targets, weights, biases, n_rows=None, state=None):
+    """[F, R] cross-entropies of F heads (weights[f] [V_f, K], biases[f] [V_f]) over hidden [R, K], targets [F, R] int64.
+    n_rows: one int32 on the device = the rows in use (R is a capacity then); state: a `VocabHeadsState` kept by the caller."""
     _need_cuda(hidden, "decoder hidden layer")
-    return VocabHeadsCE.apply(hidden, targets, *weights, *biases)
+    return VocabHeadsCE.apply(hidden, targets, n_rows, state, *weights, *biases)
+
+
+# --------------------------------------------------------------------------------------------- #
+# positive-row compaction                                                                        #
+# --------------------------------------------------------------------------------------------- #
+class CompactRows(torch.autograd.Function):
+    """K11 (csrc/compact.hip): the rows of a batch whose label is 1 (or all rows), moved to the front of tensors that keep
+    the batch's capacity B, in the order torch.nonzero gives; the count stays on the device.  X [B, cols] (any row
+    stride), dnn_in [B, W], y [B], cols (device int32 [F]: the id column of each sparse field) ->
+    (n_rows [1] int32, inv_n [1] = 1 / (n + 1e-8) or 1 / B, valid [B] 1 / 0, d_rows [B, W] with exact zeros behind the
+    count, labels [B], targets [F, B] int64).  Only d_rows is differentiable: the backward hands dnn_in a full [B, W]
+    gradient, the selected rows' rows of d(d_rows) and zeros elsewhere."""
+
+    @staticmethod
+    def forward(ctx, X, dnn_in, y, cols, positive_only):
+        lib = _lib.load()
+        B, W = dnn_in.shape
+        dev = dnn_in.device
+        F_ = int(cols.numel())
+        if X.stride(1) != 1 or X.stride(0) < X.shape[1]:
+            X = X.contiguous()
+        if dnn_in.stride(1) != 1 or dnn_in.stride(0) < W:
+            dnn_in = dnn_in.contiguous()
+        y = y.reshape(-1).contiguous()
+        if y.numel() != B or X.shape[0] != B:
+            raise ValueError("xdfm: compact_rows needs one label per row, got %d labels for %d rows" % (y.numel(), B))
+        i32 = dict(dtype=torch.int32, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        pos, n_rows = torch.empty(B, **i32), torch.empty(1, **i32)
+        inv_n, valid, labels = torch.empty(1, **f32), torch.empty(B, **f32), torch.empty(B, **f32)
+        d_rows = torch.empty(B, W, **f32)
+        targets = torch.empty(F_, B, dtype=torch.int64, device=dev)
+        _lib.check(lib.xdfm_compact_rows_fwd(_ptr(X), X.stride(0), X.shape[1], _ptr(dnn_in), dnn_in.stride(0), _ptr(y), B, W,
+                                             _ptr(cols), F_, 1 if positive_only else 0, _ptr(pos), _ptr(n_rows), _ptr(inv_n),
+                                             _ptr(valid), _ptr(d_rows), _ptr(labels), _ptr(targets), _stream()), "compact_rows_fwd")
+        ctx.save_for_backward(pos)
+        ctx.mark_non_differentiable(n_rows, inv_n, valid, labels, targets)
+        return n_rows, inv_n, valid, d_rows, labels, targets
+
+    @staticmethod
+    def backward(ctx, _gn, _gi, _gv, g, _gl, _gt):
+        if g is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        lib = _lib.load()
+        pos, = ctx.saved_tensors
+        B, W = g.shape
+        if g.stride(1) != 1 or g.stride(0) < W:
+            g = g.contiguous()
+        d_dnn = torch.empty(B, W, dtype=torch.float32, device=g.device)
+        _lib.check(lib.xdfm_compact_rows_bwd(_ptr(g), g.stride(0), _ptr(pos), B, W, _ptr(d_dnn), _stream()), "compact_rows_bwd")
+        return None, d_dnn, None, None, None
+
+
+def compact_rows(X, dnn_in, y, cols, positive_only=True):
+    y = y.to(torch.float32)             # K11 reads float labels; `labels == 1` of the dynamic route takes any dtype
+    _need_cuda(dnn_in, "decoder input")
+    _need_cuda(X, "model input")
+    _need_cuda(y, "labels")
+    return CompactRows.apply(X, dnn_in, y, cols, bool(positive_only))
 
 
 # --------------------------------------------------------------------------------------------- #

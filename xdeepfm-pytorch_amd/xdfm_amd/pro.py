@@ -15,9 +15,15 @@ What runs where:
     (`ops.AutoDis`, csrc/autodis.hip) on float32 GPU tensors with K <= 32 buckets and D <= 64; outside that envelope, on
     the CPU or with XDFM_AUTODIS_NATIVE=0 it is the reference's per-field loop on torch ops;
   * the decoder MLP and LabelAwareAttention are small dense layers on torch ops.
-The pro train step launches eagerly (the positive-row compaction has a data-dependent shape).
+The SFG branch has two routes (`BaseModelSFG.compute_sfg_loss_fused`).  The static route (XDFM_PRO_GRAPH=1, a GPU model whose heads the
+fused kernels serve): K11 (`ops.compact_rows`, csrc/compact.hip) moves the positive rows to the front of
+tensors that keep the batch's capacity and leaves their number on the device, the decoder runs on the capacity rows and the
+heads' kernels take the count from the device -- every shape depends on the batch shape only, so the train step is captured
+and replayed like every other model's (xdfm_amd/graphstep.py).  The dynamic route (the default, and everything else) selects the
+rows with torch.nonzero, whose shape reaches the host: that step launches eagerly.
 """
 import os
+import warnings
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -28,6 +34,12 @@ from . import ops
 from .inputs import DenseFeat, SparseFeat
 from .layers import CIN, DNN
 from .models import BaseModel
+
+
+def pro_graph_enabled() -> bool:
+    """XDFM_PRO_GRAPH (default 0): 1 puts the SFG branch on the static route, whose train step is captured and replayed;
+    unset, empty or 0 keeps the dynamic route (torch.nonzero; eager launches)."""
+    return os.environ.get("XDFM_PRO_GRAPH", "0").strip() not in ("", "0")
 
 
 # ------------------------------------------------------------------------------------------------- #
@@ -46,6 +58,16 @@ class LabelAwareAttention(nn.Module):
             labels = labels.squeeze(-1)
         label_emb = self.label_embedding(labels.long())
         return self.attention_net(torch.cat([x, label_emb], dim=-1))
+
+    def forward_native(self, x: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """forward's value on `ops.dense` / `ops.dense_relu` (their bias gradients are the library's column sums: no memset
+        node in a captured step).  The embedding lookup of a 0 / 1 label is the product [1 - l, l] . E: exact, and its
+        backward is a GEMM instead of an index scatter."""
+        l = labels.reshape(-1).to(x.dtype).trunc()
+        label_emb = ops.dense(torch.stack([1.0 - l, l], dim=1), self.label_embedding.weight.t(), None)
+        net = self.attention_net
+        gate = ops.dense_relu(torch.cat([x, label_emb], dim=-1), net[0].weight, net[0].bias)
+        return torch.sigmoid(ops.dense(gate, net[2].weight, net[2].bias))
 
 
 class SFGDecoder(nn.Module):
@@ -83,6 +105,18 @@ class SFGDecoder(nn.Module):
         if self.use_label_aware_attention and labels is not None:
             decoder_input = decoder_input * self.label_attention(decoder_input, labels)
         return self.shared_layers(decoder_input)
+
+    def hidden_native(self, decoder_input: torch.Tensor, labels: Optional[torch.Tensor]) -> torch.Tensor:
+        """`hidden` with every nn.Linear routed through `ops.dense` / `ops.dense_relu` (same modules, same values)."""
+        if self.use_label_aware_attention and labels is not None:
+            decoder_input = decoder_input * self.label_attention.forward_native(decoder_input, labels)
+        x = decoder_input
+        for mod in self.shared_layers:
+            if isinstance(mod, nn.Linear):
+                x = ops.dense_relu(x, mod.weight, mod.bias)         # every Linear of shared_layers is followed by nn.ReLU
+            elif not isinstance(mod, nn.ReLU):
+                x = mod(x)                                          # nn.Dropout
+        return x
 
     def forward(self, sparse_embeddings, dense_values, labels=None):
         """The reference's signature (lists of [B,1,D] / [B,1] tensors) -> (dict of [B, V_f] logits, [B, nd]).  This
@@ -140,6 +174,19 @@ class SFGLoss(nn.Module):
         total = self.sparse_weight * total_sparse + self.dense_weight * total_dense
         loss_dict['sfg_total'] = total
         return total, loss_dict
+
+
+class _ZeroLoss(torch.autograd.Function):
+    """A zero that depends on `params`: its backward hands each of them an exact zero gradient."""
+
+    @staticmethod
+    def forward(ctx, *params):
+        ctx.save_for_backward(*params)
+        return torch.zeros((), dtype=params[0].dtype, device=params[0].device)
+
+    @staticmethod
+    def backward(ctx, g):
+        return tuple(torch.zeros_like(p) for p in ctx.saved_tensors)
 
 
 # ------------------------------------------------------------------------------------------------- #
@@ -284,7 +331,8 @@ class BaseModelSFG(BaseModel):
         super().compile(optimizer, loss, metrics)
         if self.use_sfg:                                   # basemodel_sfg.py:588-590
             self.metrics_names.insert(1, "sfg_loss")
-        self._optim_capturable = False                     # eager launches: the positive-row compaction is data dependent
+        if not (self.use_sfg and self._sfg_static()):
+            self._optim_capturable = False                 # eager launches: the dynamic route's row selection is data dependent
 
     def forward_with_sfg(self, X, y=None):
         raise NotImplementedError("Subclass must implement forward_with_sfg")
@@ -293,10 +341,71 @@ class BaseModelSFG(BaseModel):
         return self.forward_with_sfg(X, None)[0]
 
     # ------------------------------------------------------------------ SFG loss on the fused layouts
+    def _sfg_static(self, X=None, dnn_in=None) -> bool:
+        """True when the SFG branch takes the static route: XDFM_PRO_GRAPH is 1, the model (and the batch at hand) is
+        float32 on a GPU, and the heads are of a width the fused kernels serve.  Everything else keeps the dynamic route."""
+        if not pro_graph_enabled() or self.sfg_decoder is None or not self.sparse_feature_columns:
+            return False
+        heads = [self.sfg_decoder.sparse_heads[fc.name] for fc in self.sparse_feature_columns]
+        tensors = [t for h in heads for t in (h.weight, h.bias)] + [t for t in (X, dnn_in) if t is not None]
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+            return False
+        if dnn_in is not None and (dnn_in.dim() != 2 or dnn_in.shape[0] > 65536 or
+                                   dnn_in.shape[1] != len(heads) * self.embedding_dim + self._sfg_dense_width()):
+            return False
+        return ops.vocab_heads_ce_supported(heads[0].weight.shape[1])
+
+    def _sfg_dense_width(self) -> int:
+        return sum(b - a for a, b in (self.feature_index[fc.name] for fc in self.dense_feature_columns))
+
+    def _sfg_loss_static(self, X, dnn_in, labels):
+        """The static route: K11, the decoder on the capacity rows, K9 by the device-side count, per-field sums times
+        inv_n.  Rows behind the count are zero rows of the decoder input; their cross-entropies and hidden gradients are
+        exact zeros (K9) and the dense head's squared error is weighted by `valid`, so they add nothing to the loss or to
+        any gradient -- the values are those of the dynamic route."""
+        dec, fn = self.sfg_decoder, self.sfg_loss_fn
+        fcs = list(self.sparse_feature_columns)
+        key = (X.device, tuple(self.feature_index[fc.name][0] for fc in fcs))
+        hit = self.__dict__.get("_sfg_cols")
+        if hit is None or hit[0] != key:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("xdfm: first SFG step inside a graph capture -- run the step once eagerly before")
+            hit = self.__dict__["_sfg_cols"] = (key, torch.tensor(key[1], dtype=torch.int32, device=X.device), ops.VocabHeadsState())
+        _, cols, state = hit
+        n_rows, inv_n, valid, d_rows, l_rows, targets = ops.compact_rows(X, dnn_in, labels, cols, fn.positive_only)
+        hidden = dec.hidden_native(d_rows, l_rows)
+        heads = [dec.sparse_heads[fc.name] for fc in fcs]
+        ce_all = ops.vocab_heads_ce(hidden, targets, [h.weight for h in heads], [h.bias for h in heads], n_rows=n_rows,
+                                    state=state if self.__dict__.get("_own_step") else None)
+        per_field = ce_all.sum(dim=1) * inv_n
+        loss_dict = {'sfg_sparse_%s' % fc.name: per_field[k] for k, fc in enumerate(fcs)}
+        total_sparse = per_field.sum()
+        total_dense = torch.zeros((), device=X.device)
+        if dec.dense_head is not None:
+            nd = self._sfg_dense_width()
+            want = d_rows[:, d_rows.shape[1] - nd:].detach()        # the dense values of the selected rows, as K1 copied them
+            err = ops.dense(hidden, dec.dense_head.weight, dec.dense_head.bias) - want
+            total_dense = (((err * err).mean(dim=-1) * valid).sum() * inv_n).reshape(())
+            loss_dict['sfg_dense'] = total_dense
+        total = fn.sparse_weight * total_sparse + fn.dense_weight * total_dense
+        loss_dict['sfg_total'] = total
+        return total, {'sfg_loss': total, 'sfg_loss_dict': loss_dict}
+
     def compute_sfg_loss_fused(self, X, dnn_in, labels):
         """sfg loss from K1's `dnn_in` rows ([sparse embeddings | dense values] = the decoder input of
         sfg_decoder.py:113-136) -- arithmetic of compute_sfg_loss (basemodel_sfg.py:420-476) + SFGLoss, with the rows
         the mask zeroes left out and the vocabulary heads evaluated tile by tile."""
+        if torch.is_grad_enabled() and not self.__dict__.get("_own_step"):
+            # driven by hand (forward_with_sfg + a backward of the caller's): that backward binds the parameters' gradient
+            # accumulators to the caller's stream -- the default stream, which must not take part in a capture -- for as
+            # long as the caller keeps the loss alive (xdfm_amd/graphstep.py).  Such a model keeps eager launches.
+            if getattr(self, "_optim_capturable", False):
+                warnings.warn("xdfm: this %s was driven by hand (its SFG loss was computed with gradients outside "
+                              "train_on_batch / fit); its train step launches eagerly from now on instead of being replayed "
+                              "from a captured graph, until compile() is called again" % type(self).__name__)
+            self._optim_capturable = False
+        if self._sfg_static(X, dnn_in):
+            return self._sfg_loss_static(X, dnn_in, labels)
         dec, fn = self.sfg_decoder, self.sfg_loss_fn
         lab = labels.reshape(-1)
         if fn.positive_only:
@@ -334,6 +443,11 @@ class BaseModelSFG(BaseModel):
                 mse = F.mse_loss(dec.dense_head(hidden), x_rows[:, cols], reduction='none').mean(dim=-1)
                 total_dense = mse.sum() / num_positive
                 loss_dict['sfg_dense'] = total_dense
+        else:
+            # no selected row: the reference's masked loss (`ce_loss * positive_mask`, sfg_decoder.py:285-293) is a zero whose
+            # gradients are zero TENSORS, so its optimizer steps the decoder's parameters (moments decay, counters advance);
+            # absent gradients would make it skip them
+            total_sparse = total_sparse + _ZeroLoss.apply(*[p for p in dec.parameters() if p.requires_grad])
         total = fn.sparse_weight * total_sparse + fn.dense_weight * total_dense
         loss_dict['sfg_total'] = total
         return total, {'sfg_loss': total, 'sfg_loss_dict': loss_dict}
