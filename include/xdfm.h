@@ -49,7 +49,8 @@
  * (K1v / K2v: pooled variable-length fields); XDFM_LINK_*, XDFM_LOSS_*, xdfm_head_fwd_ex, xdfm_head_bwd_ex (K8 with a
  * compile-time link and loss: the regression task and the mse / mae losses); xdfm_compact_rows_fwd / _bwd (K11: positive-row
  * compaction with the count on the device) and xdfm_vocab_ce_pack_hidden_n, _fwd_n, _pack_g_n, _bwd_h_n, _bwd_w_n (K9 with a
- * device-side row count: the SFG branch of the xDeepFMPro step with batch-shaped launches, so the step can be captured).
+ * device-side row count: the SFG branch of the xDeepFMPro step with batch-shaped launches, so the step can be captured);
+ * xdfm_compact_rows_fwd_n (K11 whose normaliser is counted over a second label vector: the global batch of a row-parallel step).
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -766,6 +767,16 @@ int xdfm_compact_rows_fwd(const float* X, long ldx, int xcols, const float* dnn_
                           const int* cols, int F, int positive_only, int* pos, int* n_rows, float* inv_n, float* valid,
                           float* d_rows, float* labels, long* targets, void* stream);
 int xdfm_compact_rows_bwd(const float* g, long ldg, const int* pos, long B, int W, float* d_dnn, void* stream);
+/* xdfm_compact_rows_fwd whose normaliser comes from a second label vector: count_y [n_count] (contiguous) are the labels of the
+ * GLOBAL batch of a row-parallel step, of which y [B] is this rank's shard (the SFG loss divides by the positives of the
+ * global batch, deepctr/xdeepfm_pro/sfg_decoder.py:262-268).  pos, n_rows, valid, d_rows, labels and targets come from y
+ * exactly as above; inv_n [1] = 1 / (#{count_y == 1} + 1e-8), or 1 / n_count when not positive_only -- the bits
+ * xdfm_compact_rows_fwd leaves when count_y are its labels.  Counted by the same one-workgroup scan (ballot + popcount, no
+ * atomics, no further launch), so a captured step reads a new count from count_y at every replay.  n_count is independent of
+ * B: 1 <= n_count <= 65536 * 1024.  count_y == NULL (n_count ignored): xdfm_compact_rows_fwd, bit for bit. */
+int xdfm_compact_rows_fwd_n(const float* X, long ldx, int xcols, const float* dnn_in, long ldd, const float* y, long B, int W,
+                            const int* cols, int F, int positive_only, const float* count_y, long n_count, int* pos, int* n_rows,
+                            float* inv_n, float* valid, float* d_rows, float* labels, long* targets, void* stream);
 
 /* ------------------------------------------------------------------ AutoDis of xdeepfm_pro (K10, csrc/autodis.hip)
  * replaces: the per-field Python loop of deepctr/xdeepfm_pro/autodis.py:99-125 (Linear(1,K), LeakyReLU(0.2), Linear(K,K),

@@ -112,6 +112,7 @@ SIGNATURES = {
     "xdfm_vocab_ce_bwd_w_n": (c_int, [P, c_int, c_int, P, c_int, c_int, P, P, P, P, P, P]),
     "xdfm_compact_rows_fwd": (c_int, [P, c_long, c_int, P, c_long, P, c_long, c_int, P, c_int, c_int, P, P, P, P, P, P, P, P]),
     "xdfm_compact_rows_bwd": (c_int, [P, c_long, P, c_long, c_int, P, P]),
+    "xdfm_compact_rows_fwd_n": (c_int, [P, c_long, c_int, P, c_long, P, c_long, c_int, P, c_int, c_int, P, c_long, P, P, P, P, P, P, P, P]),
     "xdfm_autodis_supported": (c_int, [c_int, c_int]),
     "xdfm_autodis_ws_elems": (c_size_t, [c_long, c_int, c_int, c_int]),
     "xdfm_autodis_fwd": (c_int, [P, c_long, c_long, c_int, c_int, c_int, P, P, P, P, P]),

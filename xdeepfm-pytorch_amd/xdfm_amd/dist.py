@@ -8,7 +8,9 @@ Here every rank holds a full replica (Criteo-scale tables fit 288 GB), takes a c
 slice of each global batch, and one exchange step per iteration makes the replicas' gradients
 identical:
 
-  * dense weights (CIN, DNN, heads, attention: a few MB): ONE flat all-reduce SUM;
+  * dense weights (CIN, DNN, heads, attention: a few MB): ONE flat all-reduce SUM; a gradient of INPLACE_MIN_NUMEL
+    elements or more (the vocabulary heads of xDeepFMPro's SFG decoder: 0.67 GB at 1e5 rows per field) is all-reduced
+    where it lies, one collective each, instead of being copied into the flat buffer and back;
   * embedding tables: never all-reduced as dense [V, D] tensors.  The per-rank row gradients
     (B_local x (m x D + X row + 1) floats, 7.7 MB at B=4096, m=26, D=16) are all-gathered in ONE
     collective and every rank runs the same single scatter launch over all ranks' rows, so the
@@ -20,6 +22,10 @@ import torch
 import torch.distributed as dist
 
 _ctx = None
+
+# Gradients of at least this many elements (4 MiB of float32) are all-reduced in place, `RowParallel.reduce_dense_grads`.
+# Every dense gradient of the xDeepFM models lies below it: they keep the one flat collective.
+INPLACE_MIN_NUMEL = 1 << 20
 
 
 def current():
@@ -128,9 +134,27 @@ class RowParallel(object):
         for p in params:
             self._replicated.add(id(p))
 
-    def reduce_dense_grads(self, model):
-        """One flat all-reduce SUM over every gradient that is not already replicated."""
-        grads = [p.grad for p in model.parameters() if p.grad is not None and id(p) not in self._replicated]
+    def reduce_dense_grads(self, model, inplace_min_numel=None):
+        """All-reduce SUM over every gradient that is not already replicated: one flat collective for the gradients of
+        fewer than `inplace_min_numel` elements (default INPLACE_MIN_NUMEL), one collective in place for each larger one --
+        no second copy of a table-sized gradient and no two passes over it.  The same sums either way, and every rank
+        takes the same split and issues the same collectives (the split depends on the shapes only: a large gradient
+        that is not contiguous is reduced through a contiguous copy of its own, never routed to the flat buffer), so
+        the replicas stay bit-identical."""
+        if inplace_min_numel is None:
+            inplace_min_numel = INPLACE_MIN_NUMEL
+        grads = []
+        for p in model.parameters():
+            g = p.grad
+            if g is None or id(p) in self._replicated:
+                continue
+            if g.numel() >= inplace_min_numel:
+                if g.is_contiguous():
+                    self.all_reduce_sum(g)
+                else:
+                    g.copy_(self.all_reduce_sum(g.contiguous()))
+            else:
+                grads.append(g)
         if not grads:
             return
         flat = torch.cat([g.reshape(-1) for g in grads])

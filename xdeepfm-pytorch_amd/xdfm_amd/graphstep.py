@@ -44,12 +44,15 @@ def census(graph: "torch.cuda.CUDAGraph"):
 
 
 class _Entry(object):
-    __slots__ = ("sig", "eager", "graph", "sx", "sy", "out", "nodes", "extra", "log")
+    __slots__ = ("sig", "eager", "graph", "sx", "sy", "out", "nodes", "extra", "log", "grads")
 
     def __init__(self, sig):
         self.sig, self.eager, self.graph, self.sx, self.sy, self.out, self.nodes = sig, 0, None, None, None, None, 0
         # what the model's `_loss_forward` left in `_step_extra` / `_step_log` during the capture: tensors of THIS graph
         self.extra = self.log = None
+        # row-parallel: (parameter, gradient tensor) as the captured first half left them -- the eager second half reads
+        # `.grad`, which an eager step of another batch shape (a ragged tail) has pointed elsewhere in the meantime
+        self.grads = None
 
 
 class GraphedStep(object):
@@ -132,6 +135,8 @@ class GraphedStep(object):
         if ent.log is not None or "_step_log" in m.__dict__:
             m.__dict__["_step_log"] = ent.log
         if dp is not None:          # captured: the first half; exchange, scatter, all-reduce and optimizer follow eagerly
+            for p, g in ent.grads:
+                p.grad = g          # the tensors THIS graph writes
             y_pred, loss, stash = ent.out
             return m._split_step_second(y_pred, loss, stash, m._l2_fusion())
         return ent.out
@@ -176,13 +181,14 @@ class GraphedStep(object):
                                    % (n_memset, n_other, n))
             g.instantiate()
             ent.graph, ent.out, ent.nodes = g, out, n
+            ent.grads = [(p, p.grad) for p in m.parameters() if p.grad is not None] if xdist.current() is not None else None
             extra = m.__dict__.get("_step_extra")
             ent.extra, ent.log = None if extra is None else extra.detach(), m.__dict__.get("_step_log")
             return True
         except Exception as exc:      # noqa: BLE001 -- any failure means: keep training eagerly
             warnings.warn("xdfm: HIP-graph capture of the train step failed (%s); continuing with eager launches" % (exc,))
             self.disabled = True
-            ent.graph = ent.sx = ent.sy = ent.out = ent.extra = ent.log = None
+            ent.graph = ent.sx = ent.sy = ent.out = ent.extra = ent.log = ent.grads = None
             if m._plan is not None:
                 m._plan.reg_defer = None
             return False

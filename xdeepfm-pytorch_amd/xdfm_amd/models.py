@@ -592,16 +592,21 @@ class BaseModel(nn.Module):
             # Dense weights: all-reduce the data gradients, then add the L2 gradient locally.
             reg_t = self.get_regularization_loss(_defer_tables=True, _part="tables")
             reg_d = self.get_regularization_loss(_part="rest")
-            (loss * self.__dict__.get("_row_weight", 1.0) + reg_t).backward()
+            # A model's further term (`_step_extra`) is a sum over the rows of the shard like the data loss.
+            self._with_step_extra(loss * self.__dict__.get("_row_weight", 1.0) + reg_t).backward()
             dp.reduce_dense_grads(self)
             (reg_d + self.aux_loss).backward()
-            total_loss = loss.detach() + reg_t.detach() + reg_d.detach() + self.aux_loss
+            total_loss = self._with_step_extra(loss.detach() + reg_t.detach() + reg_d.detach() + self.aux_loss).detach()
         self.optim.step()
         if fuse is not None and self.optim.l2_value is not None:
             total_loss = total_loss.detach() + self.optim.l2_value
         # detached: a caller that keeps these alive must not keep the step's autograd graph (and with it the
         # parameters' AccumulateGrad nodes and their stream) alive into the next step
         return y_pred.detach(), loss.detach(), total_loss.detach()
+
+    def _global_batch_labels(self, y):
+        """`fit` under row-parallel training: the labels of the global batch, before they are sharded.  A model whose
+        objective has a term normalised over the global batch (xDeepFMPro's SFG loss) keeps them for the step."""
 
     def add_auxiliary_loss(self, aux_loss, alpha):
         self.aux_loss = aux_loss * alpha
@@ -764,6 +769,7 @@ class BaseModel(nn.Module):
             total_loss_epoch = 0.0
             step_no = 0
             logged = {}
+            has_extra = False
             order = epoch_order(sample_num, shuffle)
             if order is not None:
                 order = order.to(X_all.device)
@@ -774,6 +780,7 @@ class BaseModel(nn.Module):
                     xb = self._rows(X_all, order, start, start + global_bs)
                     yb = self._rows(Y_all, order, start, start + global_bs)
                     if dp is not None:
+                        self._global_batch_labels(yb)
                         xb, yb = dp.shard(xb), dp.shard(yb)
                         self.__dict__["_row_weight"] = dp.row_weight()
                     xd = xb.to(self.device)
@@ -787,12 +794,16 @@ class BaseModel(nn.Module):
                     # sync per step that leaves the GPU idle while the next step is being enqueued.  The values are
                     # parked on the device instead and read once per epoch, summed in the same order in double.
                     if loss_log is None or loss_log.device != total_loss.device:
-                        loss_log = torch.empty((steps_per_epoch + 1, 3), dtype=torch.float32, device=total_loss.device)
+                        loss_log = torch.zeros((steps_per_epoch + 1, 4), dtype=torch.float32, device=total_loss.device)
                     loss_log[step_no, 0:1].copy_(loss.detach().reshape(1))
                     loss_log[step_no, 1:2].copy_(total_loss.detach().reshape(1))
                     step_log = self.__dict__.get("_step_log")           # (name, value) a model wants summed per epoch
                     if step_log is not None:
                         loss_log[step_no, 2:3].copy_(step_log[1].reshape(1))
+                    step_extra = self.__dict__.get("_step_extra")       # the further term of the step's objective, if any
+                    if step_extra is not None:              # a step without the term leaves the zero the column holds
+                        has_extra = True
+                        loss_log[step_no, 3:4].copy_(step_extra.detach().reshape(1))
                     step_no += 1
                     if verbose > 0:
                         yt, yp = yd, y_pred
@@ -823,6 +834,14 @@ class BaseModel(nn.Module):
                     # the data loss is a SUM over the global batch; the L2 part (total - data) is the same on every rank
                     data_sum = dp.all_reduce_sum(data_l.clone())
                     vals = [a + (t - d) for a, t, d in zip(data_sum.tolist(), total_l.tolist(), data_l.tolist())]
+                    if has_extra or self.__dict__.get("_step_log") is not None:
+                        # a model's further term and its logged value are sums over the shard's rows too: each rank's own
+                        # share leaves the total, the sum over ranks enters it
+                        # (a step that set neither left zeros: the columns are cleared after every epoch)
+                        own = loss_log[:step_no, 2:4]
+                        both = dp.all_reduce_sum(own.clone())
+                        vals = [v - e + s for v, e, s in zip(vals, own[:, 1].tolist(), both[:, 1].tolist())]
+                        loss_log[:step_no, 2].copy_(both[:, 0])
                 else:
                     vals = total_l.tolist()
                 for v in vals:
@@ -839,6 +858,8 @@ class BaseModel(nn.Module):
                 for v in loss_log[:step_no, 2].tolist():
                     extra_sum += v
                 epoch_logs[step_log[0]] = extra_sum / sample_num
+            if loss_log is not None and step_no:
+                loss_log[:step_no, 2:4].zero_()      # only steps that have such a value write it: the rest must read as zero
             for name, k in logged.items():
                 vals = metric_log[:step_no, k].tolist()
                 if name == "auc" and any(v != v for v in vals):

@@ -1233,10 +1233,12 @@ class CompactRows(torch.autograd.Function):
     stride), dnn_in [B, W], y [B], cols (device int32 [F]: the id column of each sparse field) ->
     (n_rows [1] int32, inv_n [1] = 1 / (n + 1e-8) or 1 / B, valid [B] 1 / 0, d_rows [B, W] with exact zeros behind the
     count, labels [B], targets [F, B] int64).  Only d_rows is differentiable: the backward hands dnn_in a full [B, W]
-    gradient, the selected rows' rows of d(d_rows) and zeros elsewhere."""
+    gradient, the selected rows' rows of d(d_rows) and zeros elsewhere.  With `count_y` (float labels of the GLOBAL batch
+    of a row-parallel step, any length) inv_n = 1 / (#{count_y == 1} + 1e-8) or 1 / count_y.numel(); everything else still
+    comes from y.  The kernel reads count_y from the device at every launch, so a captured step follows its contents."""
 
     @staticmethod
-    def forward(ctx, X, dnn_in, y, cols, positive_only):
+    def forward(ctx, X, dnn_in, y, cols, positive_only, count_y=None):
         lib = _lib.load()
         B, W = dnn_in.shape
         dev = dnn_in.device
@@ -1254,9 +1256,15 @@ class CompactRows(torch.autograd.Function):
         inv_n, valid, labels = torch.empty(1, **f32), torch.empty(B, **f32), torch.empty(B, **f32)
         d_rows = torch.empty(B, W, **f32)
         targets = torch.empty(F_, B, dtype=torch.int64, device=dev)
-        _lib.check(lib.xdfm_compact_rows_fwd(_ptr(X), X.stride(0), X.shape[1], _ptr(dnn_in), dnn_in.stride(0), _ptr(y), B, W,
-                                             _ptr(cols), F_, 1 if positive_only else 0, _ptr(pos), _ptr(n_rows), _ptr(inv_n),
-                                             _ptr(valid), _ptr(d_rows), _ptr(labels), _ptr(targets), _stream()), "compact_rows_fwd")
+        if count_y is None:
+            _lib.check(lib.xdfm_compact_rows_fwd(_ptr(X), X.stride(0), X.shape[1], _ptr(dnn_in), dnn_in.stride(0), _ptr(y), B, W,
+                                                 _ptr(cols), F_, 1 if positive_only else 0, _ptr(pos), _ptr(n_rows), _ptr(inv_n),
+                                                 _ptr(valid), _ptr(d_rows), _ptr(labels), _ptr(targets), _stream()), "compact_rows_fwd")
+        else:
+            _lib.check(lib.xdfm_compact_rows_fwd_n(_ptr(X), X.stride(0), X.shape[1], _ptr(dnn_in), dnn_in.stride(0), _ptr(y), B, W,
+                                                   _ptr(cols), F_, 1 if positive_only else 0, _ptr(count_y), count_y.numel(),
+                                                   _ptr(pos), _ptr(n_rows), _ptr(inv_n), _ptr(valid), _ptr(d_rows), _ptr(labels),
+                                                   _ptr(targets), _stream()), "compact_rows_fwd_n")
         ctx.save_for_backward(pos)
         ctx.mark_non_differentiable(n_rows, inv_n, valid, labels, targets)
         return n_rows, inv_n, valid, d_rows, labels, targets
@@ -1264,7 +1272,7 @@ class CompactRows(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _gn, _gi, _gv, g, _gl, _gt):
         if g is None or not ctx.needs_input_grad[1]:
-            return None, None, None, None, None
+            return None, None, None, None, None, None
         lib = _lib.load()
         pos, = ctx.saved_tensors
         B, W = g.shape
@@ -1272,15 +1280,20 @@ class CompactRows(torch.autograd.Function):
             g = g.contiguous()
         d_dnn = torch.empty(B, W, dtype=torch.float32, device=g.device)
         _lib.check(lib.xdfm_compact_rows_bwd(_ptr(g), g.stride(0), _ptr(pos), B, W, _ptr(d_dnn), _stream()), "compact_rows_bwd")
-        return None, d_dnn, None, None, None
+        return None, d_dnn, None, None, None, None
 
 
-def compact_rows(X, dnn_in, y, cols, positive_only=True):
+def compact_rows(X, dnn_in, y, cols, positive_only=True, count_y=None):
     y = y.to(torch.float32)             # K11 reads float labels; `labels == 1` of the dynamic route takes any dtype
     _need_cuda(dnn_in, "decoder input")
     _need_cuda(X, "model input")
     _need_cuda(y, "labels")
-    return CompactRows.apply(X, dnn_in, y, cols, bool(positive_only))
+    if count_y is not None:
+        _need_cuda(count_y, "labels of the global batch")
+        if count_y.dtype != torch.float32 or not count_y.is_contiguous() or count_y.numel() < 1:
+            # no silent copy: a captured step must keep reading the caller's buffer
+            raise ValueError("xdfm: compact_rows needs count_y as a non-empty contiguous float32 tensor")
+    return CompactRows.apply(X, dnn_in, y, cols, bool(positive_only), count_y)
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -21,6 +21,9 @@ tensors that keep the batch's capacity and leaves their number on the device, th
 heads' kernels take the count from the device -- every shape depends on the batch shape only, so the train step is captured
 and replayed like every other model's (xdfm_amd/graphstep.py).  The dynamic route (the default, and everything else) selects the
 rows with torch.nonzero, whose shape reaches the host: that step launches eagerly.
+Row-parallel training (xdfm_amd/dist.py): every rank runs the branch on the positive rows of its shard and divides by the
+number of positives of the GLOBAL batch (`BaseModelSFG.sfg_norm_labels`), so the ranks' terms and gradients add up to those
+of one process on the global batch.
 """
 import os
 import warnings
@@ -30,6 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import dist as xdist
 from . import ops
 from .inputs import DenseFeat, SparseFeat
 from .layers import CIN, DNN
@@ -324,10 +328,6 @@ class BaseModelSFG(BaseModel):
         self.to(device)
 
     def compile(self, optimizer, loss=None, metrics=None):
-        from . import dist as xdist
-        if xdist.current() is not None and self.use_sfg:
-            raise NotImplementedError("xDeepFMPro under row-parallel training: the SFG loss divides by the number of positives "
-                                      "of the GLOBAL batch (sfg_decoder.py:262-268), which the per-rank step does not exchange yet")
         super().compile(optimizer, loss, metrics)
         if self.use_sfg:                                   # basemodel_sfg.py:588-590
             self.metrics_names.insert(1, "sfg_loss")
@@ -339,6 +339,72 @@ class BaseModelSFG(BaseModel):
 
     def forward(self, X):
         return self.forward_with_sfg(X, None)[0]
+
+    # ------------------------------------------------------------------ the normaliser of the SFG loss
+    # SFGLoss divides the summed losses of the selected rows by their number in the batch (sfg_decoder.py:262-268).  Under
+    # row-parallel training "the batch" is the global one, of which a rank holds a shard: `sfg_norm_labels` is the one
+    # place that says which labels define the step's normaliser, and both routes ask it.
+    def _global_batch_labels(self, y):
+        """BaseModel.fit hands over the labels of the global batch before it shards them."""
+        if self.use_sfg:
+            self.__dict__["_sfg_handed"] = y
+
+    def _sfg_bind_normaliser(self, x, y):
+        """Before a train step, outside any capture: fix the labels that define this step's normaliser.  A single process:
+        None, i.e. the step's own labels.  Row-parallel: the labels `fit` handed over, or -- `train_on_batch` called
+        directly -- as many ones and zeros as one all-reduce of (local positives, local rows) counts; a stand-in row
+        (weight 0) counts for nothing.  They are kept in one buffer per global batch size, whose address a captured step
+        reads again at every replay.  No buffer is ever released: a captured first half holds the address of its buffer,
+        replays without running Python and is keyed on nothing that knows the buffer, so this dict is the buffer's only
+        owner for as long as the model lives (`ops.VocabHeadsState` keeps its tables for the same reason).  One float per
+        row of a global batch size the model has seen: 128 KB at 8 ranks of 4096 rows."""
+        handed = self.__dict__.pop("_sfg_handed", None)
+        dp = xdist.current()
+        if dp is None or not self.use_sfg or not self.training:
+            self.__dict__["_sfg_norm_y"] = None
+            return
+        if handed is None:
+            lab = y.reshape(-1)
+            rw = float(self.__dict__.get("_row_weight", 1.0))
+            v = torch.stack([(lab == 1).sum().to(torch.float64) * rw, torch.tensor(lab.numel() * rw, dtype=torch.float64,
+                                                                                   device=lab.device)]).to(dp.flag_device())
+            n_pos, n_all = (int(round(c)) for c in dp.all_reduce_sum(v).tolist())
+            handed = torch.zeros(max(n_all, 1), dtype=torch.float32)
+            handed[:n_pos] = 1.0
+        handed = handed.reshape(-1)
+        bufs = self.__dict__.setdefault("_sfg_norm_bufs", {})
+        key = (handed.numel(), x.device)
+        buf = bufs.get(key)
+        if buf is None:
+            buf = bufs[key] = torch.empty(handed.numel(), dtype=torch.float32, device=x.device)
+        buf.copy_(handed)
+        self.__dict__["_sfg_norm_y"] = buf
+
+    def sfg_norm_labels(self, labels):
+        """The labels that define this step's normaliser: the step's own in a single process (and whenever nothing was
+        bound), those of the global batch under row-parallel training."""
+        norm_y = self.__dict__.get("_sfg_norm_y")
+        return labels.reshape(-1) if norm_y is None else norm_y
+
+    def sfg_normaliser(self, labels) -> float:
+        """What the summed losses of the selected rows are divided by: (number of positives among `sfg_norm_labels`) + 1e-8,
+        or the number of rows without `sfg_positive_only` (sfg_decoder.py:262-268).  Reads the count back to the host."""
+        norm_y = self.sfg_norm_labels(labels)
+        if self.sfg_positive_only:
+            return int((norm_y == 1).sum()) + 1e-8
+        return float(norm_y.numel())
+
+    def _sfg_row_weight(self) -> float:
+        """0 on a rank that holds only a stand-in row of a global batch with fewer rows than ranks (dist.RowParallel.shard):
+        that row adds nothing to the SFG term either."""
+        return float(self.__dict__.get("_row_weight", 1.0))
+
+    def train_on_batch(self, x, y):
+        self._sfg_bind_normaliser(x, y)
+        try:
+            return super().train_on_batch(x, y)
+        finally:
+            self.__dict__["_sfg_norm_y"] = None         # a loss computed by hand afterwards is normalised by its own labels
 
     # ------------------------------------------------------------------ SFG loss on the fused layouts
     def _sfg_static(self, X=None, dnn_in=None) -> bool:
@@ -360,9 +426,10 @@ class BaseModelSFG(BaseModel):
 
     def _sfg_loss_static(self, X, dnn_in, labels):
         """The static route: K11, the decoder on the capacity rows, K9 by the device-side count, per-field sums times
-        inv_n.  Rows behind the count are zero rows of the decoder input; their cross-entropies and hidden gradients are
-        exact zeros (K9) and the dense head's squared error is weighted by `valid`, so they add nothing to the loss or to
-        any gradient -- the values are those of the dynamic route."""
+        inv_n (which K11 counts over `sfg_norm_labels` when those are not the step's own: no host read).  Rows behind the
+        count are zero rows of the decoder input; their cross-entropies and hidden gradients are exact zeros (K9) and the
+        dense head's squared error is weighted by `valid`, so they add nothing to the loss or to any gradient -- the
+        values are those of the dynamic route."""
         dec, fn = self.sfg_decoder, self.sfg_loss_fn
         fcs = list(self.sparse_feature_columns)
         key = (X.device, tuple(self.feature_index[fc.name][0] for fc in fcs))
@@ -372,7 +439,8 @@ class BaseModelSFG(BaseModel):
                 raise RuntimeError("xdfm: first SFG step inside a graph capture -- run the step once eagerly before")
             hit = self.__dict__["_sfg_cols"] = (key, torch.tensor(key[1], dtype=torch.int32, device=X.device), ops.VocabHeadsState())
         _, cols, state = hit
-        n_rows, inv_n, valid, d_rows, l_rows, targets = ops.compact_rows(X, dnn_in, labels, cols, fn.positive_only)
+        n_rows, inv_n, valid, d_rows, l_rows, targets = ops.compact_rows(X, dnn_in, labels, cols, fn.positive_only,
+                                                                         count_y=self.__dict__.get("_sfg_norm_y"))
         hidden = dec.hidden_native(d_rows, l_rows)
         heads = [dec.sparse_heads[fc.name] for fc in fcs]
         ce_all = ops.vocab_heads_ce(hidden, targets, [h.weight for h in heads], [h.bias for h in heads], n_rows=n_rows,
@@ -410,10 +478,10 @@ class BaseModelSFG(BaseModel):
         lab = labels.reshape(-1)
         if fn.positive_only:
             rows = torch.nonzero(lab == 1).reshape(-1)      # host-visible shape: this step is not graph-captured
-            num_positive = rows.numel() + 1e-8
+            num_positive = rows.numel() + 1e-8 if self.__dict__.get("_sfg_norm_y") is None else self.sfg_normaliser(lab)
             x_rows, d_rows, l_rows = X.index_select(0, rows), dnn_in.index_select(0, rows), lab.index_select(0, rows)
         else:
-            x_rows, d_rows, l_rows, num_positive = X, dnn_in, lab, float(lab.shape[0])
+            x_rows, d_rows, l_rows, num_positive = X, dnn_in, lab, self.sfg_normaliser(lab)
         loss_dict = {}
         total_sparse = torch.zeros((), device=X.device)
         total_dense = torch.zeros((), device=X.device)
@@ -444,7 +512,8 @@ class BaseModelSFG(BaseModel):
                 total_dense = mse.sum() / num_positive
                 loss_dict['sfg_dense'] = total_dense
         else:
-            # no selected row: the reference's masked loss (`ce_loss * positive_mask`, sfg_decoder.py:285-293) is a zero whose
+            # no selected row (row-parallel: none on THIS rank; it still joins every collective of the step, with exact zeros):
+            # the reference's masked loss (`ce_loss * positive_mask`, sfg_decoder.py:285-293) is a zero whose
             # gradients are zero TENSORS, so its optimizer steps the decoder's parameters (moments decay, counters advance);
             # absent gradients would make it skip them
             total_sparse = total_sparse + _ZeroLoss.apply(*[p for p in dec.parameters() if p.requires_grad])
@@ -472,8 +541,11 @@ class BaseModelSFG(BaseModel):
         # forward_with_sfg returns no sfg_info; same here, BaseModel.fit shares that behaviour)
         self._step_log = ("sfg_loss", torch.zeros((), device=loss.device)) if self.use_sfg else None
         if self.use_sfg and sfg_info is not None:
-            self._step_extra = self.sfg_weight * sfg_info['sfg_loss']
-            self._step_log = ("sfg_loss", sfg_info['sfg_loss'].detach())
+            sfg = sfg_info['sfg_loss']
+            if self._sfg_row_weight() != 1.0:
+                sfg = sfg * self._sfg_row_weight()
+            self._step_extra = self.sfg_weight * sfg
+            self._step_log = ("sfg_loss", sfg.detach())
         return y_pred, loss
 
 

@@ -19,6 +19,10 @@ adds `--synthetic N` (no data file needed) and multi-process launch:
 
     python xdftrain_amd.py --synthetic 200000 --epochs 2 --embedding_dim 16
     python -m torch.distributed.run --nproc-per-node 8 xdftrain_amd.py --data_path train.txt ...
+    python -m torch.distributed.run --nproc-per-node 8 xdftrain_pro.py --data_path train.txt ...   # xDeepFMPro, SFG included
+
+Under a launcher `--batch_size` is per process; the global batch is batch_size x world size (the reference's DataParallel
+rule).  xDeepFMPro's SFG loss is normalised by the positives of the global batch on every rank.
 """
 import argparse
 import json
