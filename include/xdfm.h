@@ -51,6 +51,8 @@
  * compaction with the count on the device) and xdfm_vocab_ce_pack_hidden_n, _fwd_n, _pack_g_n, _bwd_h_n, _bwd_w_n (K9 with a
  * device-side row count: the SFG branch of the xDeepFMPro step with batch-shaped launches, so the step can be captured);
  * xdfm_compact_rows_fwd_n (K11 whose normaliser is counted over a second label vector: the global batch of a row-parallel step).
+ * xdfm_varlen_pool_bwd_rows_ws_elems, xdfm_varlen_pool_bwd_rows (K2v over the exchanged rows of a row-parallel step: the positions
+ * of the maxima are recomputed, not passed) -- additions again, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -206,6 +208,21 @@ int xdfm_varlen_pool_bwd(const float* X, long ldx, int B, const xdfm_varlen_fiel
                          const float* d_lin, long ld_lin, const unsigned char* argpos,
                          const int* cols, const int* vocab, float* d_flat, const long* tab_off, const long* lin_off,
                          float* ws, void* stream);
+/* The same backward over EXCHANGED rows (row-parallel training: every rank scatters all ranks' rows, and has run the forward
+ * for its own only).  X [R][ldx]: the gathered rows, rank-major, zero pad rows of ragged ranks included.  g_rows [R][ld_g]:
+ * per-example row gradients in the DNN input's layout, field slot0 + f of row r at g_rows[r * ld_g + (slot0 + f) * D], the two
+ * uses of the pooled row already summed (ld_g >= (slot0 + F) * D).  d_lin [R] with row stride ld_lin (0 = 1).  No argpos: for
+ * XDFM_POOL_MAX fields the position of the first maximum is recomputed from the tables in `fields` by the forward's own walk
+ * (same validity, masked positions as w - 1e9f, ties to the lowest position) -- call it BEFORE the tables are updated.  Then
+ * xdfm_varlen_pool_bwd's expand and reduce run over the R rows: same d_flat / tab_off / lin_off / cols / vocab, same bits as
+ * that call on the same rows in the same order; an all-zero row adds nothing.  An id outside [0, vocab), at any position,
+ * raises err_flag (device int[1] or NULL) and is clamped.  ws: xdfm_varlen_pool_bwd_rows_ws_elems floats, 16-byte aligned. */
+size_t xdfm_varlen_pool_bwd_rows_ws_elems(long R, int F, int D, int Tmax);
+int xdfm_varlen_pool_bwd_rows(const float* X, long ldx, int R, const xdfm_varlen_field* fields,
+                              const xdfm_varlen_field* fields_host, int F, int D, int slot0,
+                              const float* g_rows, long ld_g, const float* d_lin, long ld_lin,
+                              const int* cols, const int* vocab, float* d_flat, const long* tab_off, const long* lin_off,
+                              float* ws, int* err_flag, void* stream);
 
 /* ------------------------------------------------------------------ embedding scatter (K2)
  * replaces: autograd of the above (aten::embedding_dense_backward x52, sparse=False,

@@ -24,6 +24,36 @@ __device__ __forceinline__ long vl_length(const float* __restrict__ xrow, const 
     return n;
 }
 
+// One (example, field, column): the pooled value, and for max the position of the first maximum.  The forward and the
+// exchanged-rows backward (which recomputes that position instead of being handed it) share this walk, so both pick the same
+// position: validity by the length column or id != 0, masked positions compete as w - 1e9, ties go to the lowest position.
+__device__ __forceinline__ float vl_pool_one(const float* __restrict__ xrow, const xdfm_varlen_field& fd, const float* __restrict__ tab,
+                                             int stride, int off, int* pos_out, bool* bad) {
+    const long len = fd.len_col >= 0 ? (long)xrow[fd.len_col] : 0;
+    float acc = 0.f, best = 0.f;
+    int pos = 0;
+    long cnt = 0;
+    for (int t = 0; t < fd.maxlen; ++t) {
+        long id = (long)xrow[fd.col + t];                          // truncation as Tensor.long() (inputs.py:225)
+        const bool valid = fd.len_col >= 0 ? (long)t < len : id != 0;
+        if (id < 0 || id >= fd.vocab) {                            // every position is looked up, padded ones included
+            *bad = true;
+            id = id < 0 ? 0 : fd.vocab - 1;
+        }
+        const float w = tab[id * stride + off];
+        if (fd.combiner == XDFM_POOL_MAX) {
+            const float v = valid ? w : w - 1e9f;                  // w - (1 - mask) * 1e9 (sequence.py:66)
+            if (t == 0 || v > best) { best = v; pos = t; }         // the first maximum
+        } else if (valid) {
+            acc += w;
+            ++cnt;
+        }
+    }
+    *pos_out = pos;
+    if (fd.combiner == XDFM_POOL_MEAN) return acc / ((float)(fd.len_col >= 0 ? len : cnt) + 1e-8f);   // sequence.py:74
+    return fd.combiner == XDFM_POOL_MAX ? best : acc;
+}
+
 __global__ __launch_bounds__(VL_THREADS) void varlen_pool_fwd_kernel(
     const float* __restrict__ X, long ldx, int B, const xdfm_varlen_field* __restrict__ fields, int F, int D, int slot0,
     float* __restrict__ emb_fm, float* __restrict__ dnn_in, long ld_dnn, int dnn_off, float* __restrict__ lin_out,
@@ -40,31 +70,8 @@ __global__ __launch_bounds__(VL_THREADS) void varlen_pool_fwd_kernel(
     bool bad = false;
     for (int f = 0; f < F; ++f) {
         const xdfm_varlen_field fd = fields[f];
-        const float* tab = is_lin ? fd.lin : fd.table;
-        const int stride = is_lin ? 1 : D, off = is_lin ? 0 : d;
-        const long len = fd.len_col >= 0 ? (long)xrow[fd.len_col] : 0;
-        float acc = 0.f, best = 0.f;
         int pos = 0;
-        long cnt = 0;
-        for (int t = 0; t < fd.maxlen; ++t) {
-            long id = (long)xrow[fd.col + t];                          // truncation as Tensor.long() (inputs.py:225)
-            const bool valid = fd.len_col >= 0 ? (long)t < len : id != 0;
-            if (id < 0 || id >= fd.vocab) {                            // every position is looked up, padded ones included
-                bad = true;
-                id = id < 0 ? 0 : fd.vocab - 1;
-            }
-            const float w = tab[id * stride + off];
-            if (fd.combiner == XDFM_POOL_MAX) {
-                const float v = valid ? w : w - 1e9f;                  // w - (1 - mask) * 1e9 (sequence.py:66)
-                if (t == 0 || v > best) { best = v; pos = t; }         // the first maximum
-            } else if (valid) {
-                acc += w;
-                ++cnt;
-            }
-        }
-        float r = acc;
-        if (fd.combiner == XDFM_POOL_MEAN) r = acc / ((float)(fd.len_col >= 0 ? len : cnt) + 1e-8f);   // sequence.py:74
-        else if (fd.combiner == XDFM_POOL_MAX) r = best;
+        const float r = vl_pool_one(xrow, fd, is_lin ? fd.lin : fd.table, is_lin ? 1 : D, is_lin ? 0 : d, &pos, &bad);
         if (is_lin) {
             lin_acc += r;
         } else {
@@ -74,6 +81,35 @@ __global__ __launch_bounds__(VL_THREADS) void varlen_pool_fwd_kernel(
         if (argpos) argpos[((long)b * F + f) * W + d] = (unsigned char)pos;
     }
     if (is_lin) lin_out[b] += lin_acc;
+    if (bad && err_flag) atomicOr(err_flag, 1);
+}
+
+// Exchanged rows (row-parallel training): the positions of the maxima of R rows that this rank did not run the forward for,
+// from the tables as they are before the update -- [R][F][D + 1] bytes as the forward writes them, 0 for sum and mean fields,
+// whose ids are only checked against the vocabulary (by the linear column's thread).  One thread per (row, column).
+__global__ __launch_bounds__(VL_THREADS) void varlen_rows_argpos_kernel(
+    const float* __restrict__ X, long ldx, int R, const xdfm_varlen_field* __restrict__ fields, int F, int D, bool tabs, bool lins,
+    unsigned char* __restrict__ argpos, int* __restrict__ err_flag) {
+    const int W = D + 1;
+    const long idx = (long)blockIdx.x * VL_THREADS + threadIdx.x;
+    if (idx >= (long)R * W) return;
+    const int r = (int)(idx / W), d = (int)(idx - (long)r * W);
+    const bool is_lin = d == D;
+    const float* xrow = X + (long)r * ldx;
+    bool bad = false;
+    for (int f = 0; f < F; ++f) {
+        const xdfm_varlen_field fd = fields[f];
+        int pos = 0;
+        if (fd.combiner == XDFM_POOL_MAX) {
+            if (is_lin ? lins : tabs) vl_pool_one(xrow, fd, is_lin ? fd.lin : fd.table, is_lin ? 1 : D, is_lin ? 0 : d, &pos, &bad);
+        } else if (is_lin) {
+            for (int t = 0; t < fd.maxlen; ++t) {
+                const long id = (long)xrow[fd.col + t];
+                bad = bad || id < 0 || id >= fd.vocab;
+            }
+        }
+        argpos[((long)r * F + f) * W + d] = (unsigned char)pos;
+    }
     if (bad && err_flag) atomicOr(err_flag, 1);
 }
 
@@ -210,6 +246,40 @@ int xdfm_varlen_pool_bwd(const float* X, long ldx, int B, const xdfm_varlen_fiel
         rc = xdfm_embed_scatter_bwd_marked(ids, F, (int)P, cols, vocab, F, 1, nullptr, 0, g_lin, nullptr, 0, nullptr, 0, d_flat, lin_off,
                                            nullptr, nullptr, nullptr, stream);
     return rc;
+}
+
+// ws: [what xdfm_varlen_pool_bwd takes for R rows | argpos R*F*(D+1) bytes], the second part on a 16-byte boundary
+size_t xdfm_varlen_pool_bwd_rows_ws_elems(long R, int F, int D, int Tmax) {
+    if (R <= 0 || F <= 0 || D <= 0 || Tmax <= 0) return 0;
+    return xdfm_varlen_pool_bwd_ws_elems(R, F, D, Tmax) + vl_pad4(((size_t)R * F * (D + 1) + 3) / 4);
+}
+
+int xdfm_varlen_pool_bwd_rows(const float* X, long ldx, int R, const xdfm_varlen_field* fields, const xdfm_varlen_field* fields_host,
+                              int F, int D, int slot0, const float* g_rows, long ld_g, const float* d_lin, long ld_lin,
+                              const int* cols, const int* vocab, float* d_flat, const long* tab_off, const long* lin_off, float* ws,
+                              int* err_flag, void* stream) {
+    XDFM_REQUIRE(X && fields && fields_host && cols && vocab && d_flat && ws, "varlen_pool_bwd_rows: null pointer");
+    XDFM_REQUIRE(R > 0 && F > 0 && D > 0 && slot0 >= 0, "varlen_pool_bwd_rows: bad shape R=%d F=%d D=%d slot0=%d", R, F, D, slot0);
+    XDFM_REQUIRE(!g_rows || ld_g >= ((long)slot0 + F) * D, "varlen_pool_bwd_rows: ld_g=%ld smaller than (slot0 + F) * D = %ld", ld_g,
+                 ((long)slot0 + F) * D);
+    XDFM_REQUIRE((((size_t)ws) & 15) == 0, "varlen_pool_bwd_rows: ws must be 16-byte aligned");
+    const bool tabs = tab_off && g_rows;
+    const bool lins = lin_off && d_lin;
+    if (!tabs && !lins) return XDFM_OK;
+    int tmax = 0;
+    // the argmax walk reads the tables: those whose gradient is asked for must be there
+    const int rc = vl_check_fields("varlen_pool_bwd_rows", fields_host, F, ldx, tabs, lins, &tmax);
+    if (rc) return rc;
+    XDFM_REQUIRE((long)R * tmax < 0x7fffffffL, "varlen_pool_bwd_rows: R * Tmax = %ld too large", (long)R * tmax);
+    unsigned char* argpos = reinterpret_cast<unsigned char*>(ws + xdfm_varlen_pool_bwd_ws_elems(R, F, D, tmax));
+    const long threads = (long)R * (D + 1);
+    hipLaunchKernelGGL(varlen_rows_argpos_kernel, dim3(ceil_div(threads, VL_THREADS)), dim3(VL_THREADS), 0, (hipStream_t)stream, X, ldx, R,
+                       fields, F, D, tabs, lins, argpos, err_flag);
+    const int rl = xdfm_check_launch("varlen_pool_bwd_rows (argpos)");
+    if (rl) return rl;
+    // the exchanged row gradients have the DNN input's layout: example-major, field slot0 + f at column (slot0 + f) * D
+    return xdfm_varlen_pool_bwd(X, ldx, R, fields, fields_host, F, D, slot0, nullptr, g_rows, ld_g, slot0 * D, d_lin, ld_lin, argpos, cols,
+                                vocab, d_flat, tab_off, lin_off, ws, stream);
 }
 
 }  // extern "C"

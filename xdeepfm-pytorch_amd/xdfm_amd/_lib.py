@@ -31,6 +31,8 @@ SIGNATURES = {
     "xdfm_varlen_pool_bwd_ws_elems": (c_size_t, [c_long, c_int, c_int, c_int]),
     "xdfm_varlen_pool_bwd": (c_int, [P, c_long, c_int, P, P, c_int, c_int, c_int, P, P, c_long, c_int, P, c_long, P, P, P, P, P, P,
                                      P, P]),
+    "xdfm_varlen_pool_bwd_rows_ws_elems": (c_size_t, [c_long, c_int, c_int, c_int]),
+    "xdfm_varlen_pool_bwd_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, c_int, P, c_long, P, c_long, P, P, P, P, P, P, P, P]),
     "xdfm_embed_scatter_bwd": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, c_int, P, P, P, P, P, P, P, P]),
     "xdfm_embed_scatter_bwd_marked": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, c_int, P, P, c_long, P, c_long,
                                               P, P, P, P, P, P]),

@@ -182,7 +182,9 @@ class RowParallel(object):
         values) and its linear-logit gradient -- 1.9 KB per example at config 2.  Ranks with fewer rows (ragged last
         batch) pad with zero rows, which scatter exact zeros.  The gathered buffer is handed to the scatter as
         strided views, so every rank runs ONE scatter launch over all ranks' rows in rank order; no transposes, no
-        per-rank launches.  Returns [(X, None, row_grads, d_lin)] for EmbedGather.scatter."""
+        per-rank launches.  With pooled variable-length fields m counts their field slots too, and the same three views
+        feed K2v over exchanged rows (ops.varlen_rows_grads): their ids and lengths are columns of X, nothing more is
+        shipped.  Returns [(X, None, row_grads, d_lin)] for EmbedGather.scatter."""
         sizes = self.step_sizes()
         B = X.shape[0]
         if B != sizes[self.rank]:

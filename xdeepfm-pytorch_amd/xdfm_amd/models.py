@@ -267,12 +267,14 @@ class BaseModel(nn.Module):
             if len(dims) > 1:
                 raise ValueError("embedding_dim of SparseFeat and VarlenSparseFeat must be same in this model!")
             dp = xdist.current()
-            if dp is not None and (varlen or self.linear_model.varlen_sparse_feature_columns):
-                raise NotImplementedError("row-parallel training does not take VarLenSparseFeat columns")
             lin_sparse = self.linear_model.sparse_feature_columns
             self._fused_linear = [fc.name for fc in lin_sparse] == [fc.name for fc in sparse] and \
                 [fc.name for fc in self.linear_model.dense_feature_columns] == [fc.name for fc in dense] and \
                 [fc.name for fc in self.linear_model.varlen_sparse_feature_columns] == [fc.name for fc in varlen]
+            if dp is not None and not self._fused_linear and (varlen or self.linear_model.varlen_sparse_feature_columns):
+                # without the fused gather there is no row exchange for the pooled fields' ids and gradients to ride on
+                raise NotImplementedError("row-parallel training takes VarLenSparseFeat columns only when "
+                                          "linear_feature_columns and dnn_feature_columns list the same columns in the same order")
             dense_cols = [c for fc in dense for c in range(*self.feature_index[fc.name])]
             D = dims.pop() if dims else 1
             # the pooled variable-length fields follow the sparse ones: field slots m .. m+F-1 of the CIN input,
@@ -287,6 +289,12 @@ class BaseModel(nn.Module):
                 self._plan.dp = dp
                 dp.mark_replicated([self.embedding_dict[fc.embedding_name].weight for fc in sparse])
                 dp.mark_replicated(self.linear_model.parameters())
+                if varlen:
+                    # the pooled fields ride on the same exchange: K2v runs over all ranks' rows (ops.varlen_rows_grads)
+                    vtabs = [self.embedding_dict[fc.embedding_name].weight for fc in varlen]
+                    self._vplan.gather = self._plan
+                    self._plan.varlen_owners = vtabs + self.linear_model.varlen_tables()
+                    dp.mark_replicated(vtabs)
         return self._plan
 
     def fused_inputs(self, X):

@@ -83,6 +83,8 @@ class EmbedPlan:
         self._arenas = {}
         self.catchup = None       # set by optim.TableAdam (deferred update): brings the rows of X up to date before they are read
         self.last_gather = None   # (X, embedding tables, linear tables) of the latest gather: the rows a deferred update is keyed by
+        self.varlen_req = None    # left by VarLenPool.backward when the pooled fields' table gradients wait for the exchange (dp)
+        self.varlen_owners = None  # the parameters those gradients belong to: the F [V, D] tables, then the F [V, 1] tables
 
     def on(self, device):
         key = str(device)
@@ -234,18 +236,25 @@ class EmbedGather(torch.autograd.Function):
         X = ctx.saved_tensors[0]
         tables = ctx.saved_tensors[1:]
         plan = ctx.plan
+        varlen, plan.varlen_req = plan.varlen_req, None      # VarLenPool.backward ran just before: its fields ride on our exchange
         if plan.stash is not None:
             # split step (row-parallel run replayed from a HIP graph): the scatter needs the other ranks' rows, so
             # it runs after the exchange, outside the captured part -- see apply_stashed_scatter
-            plan.stash.append((plan, X, d_emb, d_dnn, d_lin, ctx.has_lin, ctx.shapes, tables, ctx.needs_input_grad[1]))
+            plan.stash.append((plan, X, d_emb, d_dnn, d_lin, ctx.has_lin, ctx.shapes, tables, ctx.needs_input_grad[1], varlen))
             return (None, None, None, None) + (None,) * len(tables)
         need_w = ctx.needs_input_grad[1]
-        grads, d_w = EmbedGather.scatter(plan, X, d_emb, d_dnn, d_lin, ctx.has_lin, ctx.shapes, tables, need_w)
+        grads, d_w, vgrads = EmbedGather.scatter(plan, X, d_emb, d_dnn, d_lin, ctx.has_lin, ctx.shapes, tables, need_w, varlen)
+        if vgrads is not None:
+            # those tables are no inputs of this node: their gradients are accumulated the way AccumulateGrad would
+            for p, g in _varlen_owned(plan, varlen, vgrads):
+                p.grad = g if p.grad is None else p.grad + g
         return (None, d_w if (need_w and plan.nd) else None, None, None) + tuple(grads)
 
     @staticmethod
-    def scatter(plan, X, d_emb, d_dnn, d_lin, has_lin, shapes, tables, need_w=True):
-        """Dense table gradients (views of one flat buffer) and the dense-weight gradient from the row gradients."""
+    def scatter(plan, X, d_emb, d_dnn, d_lin, has_lin, shapes, tables, need_w=True, varlen=None):
+        """Dense table gradients (views of one flat buffer) and the dense-weight gradient from the row gradients; third,
+        the table gradients of the pooled variable-length fields when their backward left a request (`varlen`, row-parallel
+        only: K2v runs once over the same exchanged rows), else None."""
         lib = _lib.load()
         m, D, nd = plan.m, plan.D, plan.nd
         dev = X.device
@@ -278,6 +287,9 @@ class EmbedGather(torch.autograd.Function):
         pieces = [(X, d_emb, d_dnn, d_lin)]
         if plan.dp is not None:
             pieces = plan.dp.exchange_rows(X, d_emb, d_dnn, d_lin)
+        elif varlen is not None:
+            raise RuntimeError("xdfm: the variable-length fields wait for a row exchange that this gather does not make")
+        vgrads = None
         for (Xr, de, dd, dl) in pieces:
             B = Xr.shape[0]
             # the exchange hands over strided views of one gathered buffer: rows may be wider than their payload
@@ -292,7 +304,9 @@ class EmbedGather(torch.autograd.Function):
                 _ptr(Xr), Xr.stride(0), B, _ptr(cols), _ptr(vocab), m, D, _ptr(dcols) if nd else None, nd,
                 _ptr(de), _ptr(dd), ld_dnn, _ptr(dl), ld_lin, _ptr(flat), _ptr(tab_off), _ptr(lin_off), _ptr(d_w),
                 _ptr(marks), _stream())), "embed_scatter_bwd")
-        return grads, d_w
+            if varlen is not None:
+                vgrads = varlen_rows_grads(varlen, Xr, dd, dl, ld_lin)
+        return grads, d_w, vgrads
 
 
 # --------------------------------------------------------------------------------------------- #
@@ -327,6 +341,11 @@ class VarLenPlan:
         self._dev = {}
         self._desc = {}
         self._off_cache = {}
+        self.gather = None        # row-parallel: the EmbedPlan whose row exchange carries these fields' ids and row gradients
+
+    def exchanged(self):
+        """True when the table gradients are built from all ranks' rows after the gather's exchange (xdfm_amd.dist)."""
+        return self.gather is not None and self.gather.dp is not None
 
     def on(self, device):
         key = str(device)
@@ -410,7 +429,8 @@ class VarLenPool(torch.autograd.Function):
             raise ValueError("xdfm: VarLenPool: lin must be contiguous [B, 1]")
         _, _, flag = plan.on(X.device)
         host, dev = plan.descriptors(emb_tables, lin_tables, X.device)
-        argpos = torch.empty((B, F, D + 1), dtype=torch.uint8, device=X.device)
+        # row-parallel: the backward runs over all ranks' rows and recomputes the positions of the maxima itself
+        argpos = None if plan.exchanged() else torch.empty((B, F, D + 1), dtype=torch.uint8, device=X.device)
         # algorithmic bytes: ids + the looked-up rows (+ linear rows) + the pooled rows to both consumers
         T = sum(plan.maxlens)
         nbytes = B * (4 * T + T * ((4 * D if n_emb else 0) + (4 if lin_tables else 0)) + 2 * 4 * F * D)
@@ -423,6 +443,7 @@ class VarLenPool(torch.autograd.Function):
         ctx.plan, ctx.n_emb, ctx.n_lin = plan, n_emb, len(lin_tables)
         ctx.shapes = [tuple(t.shape) for t in tables]
         ctx.desc = (host, dev)
+        ctx.exchanged = argpos is None
         ctx.save_for_backward(X, argpos)
         return emb_fm, dnn_in, lin
 
@@ -434,7 +455,14 @@ class VarLenPool(torch.autograd.Function):
         F, D = plan.F, plan.D
         need = ctx.needs_input_grad[6:]
         grads = [None] * len(ctx.shapes)
-        if any(need):
+        if ctx.exchanged:
+            # row-parallel: no local table gradients.  The gather's backward, which runs next, takes this request along to
+            # its row exchange (EmbedGather.scatter -> varlen_rows_grads); d_emb / d_dnn / d_lin go on to it unchanged.
+            if any(need):
+                if ctx.n_emb != F or ctx.n_lin != F:
+                    raise RuntimeError("xdfm: row-parallel VarLenPool needs the [V, D] and the [V, 1] tables of every field")
+                plan.gather.varlen_req = (plan, ctx.desc, ctx.shapes, tuple(need))
+        elif any(need):
             dev = X.device
             B = X.shape[0]
             sizes, offs, total, off_dev = plan.grad_layout(ctx.shapes, dev)
@@ -460,14 +488,50 @@ class VarLenPool(torch.autograd.Function):
         return (None, d_emb, d_dnn, d_lin, None, None) + tuple(grads)
 
 
+def varlen_rows_grads(req, Xr, G, dl, ld_lin):
+    """K2v over exchanged rows: the dense gradients of the F [V, D] tables and the F [V, 1] tables of a VarLenPool whose
+    backward left `req`, from strided views of the gathered buffer -- Xr [R, ncols], G [R, >= (slot0 + F) * D] (row
+    gradients, example-major), dl [R].  One call; the positions of the maxima are recomputed from the tables, which are the
+    same on every rank until the optimizer runs."""
+    vplan, (host, desc), shapes, _ = req
+    lib = _lib.load()
+    F, D = vplan.F, vplan.D
+    dev, R = Xr.device, Xr.shape[0]
+    if G is None or dl is None or Xr.stride(1) != 1 or G.stride(1) != 1 or G.shape[1] < (vplan.slot0 + F) * D:
+        raise RuntimeError("xdfm: the exchanged rows do not carry the variable-length fields' gradients")
+    sizes, offs, total, off_dev = vplan.grad_layout(shapes, dev)
+    flat = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+    cols, vocab, flag = vplan.on(dev)
+    ws = torch.empty(lib.xdfm_varlen_pool_bwd_rows_ws_elems(R, F, D, vplan.Tmax), dtype=torch.float32, device=dev)
+    P = R * vplan.Tmax
+    nbytes = 4 * P * F * (D + 2) * 2
+    _lib.check(_run("varlen_pool_bwd_rows[bytes]", nbytes, lambda: lib.xdfm_varlen_pool_bwd_rows(
+        _ptr(Xr), Xr.stride(0), R, _ptr(desc), ctypes.cast(host, ctypes.c_void_p), F, D, vplan.slot0, _ptr(G), G.stride(0),
+        _ptr(dl), ld_lin, _ptr(cols), _ptr(vocab), _ptr(flat), _ptr(off_dev[:F]), _ptr(off_dev[F:2 * F]), _ptr(ws), _ptr(flag),
+        _stream())), "varlen_pool_bwd_rows")
+    return [flat[o:o + n].view(sh) for o, n, sh in zip(offs, sizes, shapes)]
+
+
+def _varlen_owned(plan, req, vgrads):
+    """(parameter, gradient) of the variable-length tables that want one."""
+    owners = plan.varlen_owners
+    if owners is None or len(owners) != len(vgrads):
+        raise RuntimeError("xdfm: EmbedPlan.varlen_owners must name the %d variable-length tables" % len(vgrads))
+    return [(p, g) for p, g, n in zip(owners, vgrads, req[3]) if n]
+
+
 def apply_stashed_scatter(stash, dense_w, params=None):
     """Second half of a split step: exchange + scatter for every stashed gather backward; the gradients are
     assigned to `.grad` of the tables (`params`: the model's own parameter objects, in the gather's order) and of
-    `dense_w`, the linear part's dense weight, directly."""
+    `dense_w`, the linear part's dense weight, directly.  A gather whose pooled variable-length fields wait for the same
+    exchange hands their table gradients over too: assigned to `.grad` of `plan.varlen_owners`."""
     with torch.no_grad():
-        for (plan, X, d_emb, d_dnn, d_lin, has_lin, shapes, tables, need_w) in stash:
-            grads, d_w = EmbedGather.scatter(plan, X, d_emb, d_dnn, d_lin, has_lin, shapes, tables,
-                                             bool(need_w and dense_w is not None))
+        for (plan, X, d_emb, d_dnn, d_lin, has_lin, shapes, tables, need_w, varlen) in stash:
+            grads, d_w, vgrads = EmbedGather.scatter(plan, X, d_emb, d_dnn, d_lin, has_lin, shapes, tables,
+                                                     bool(need_w and dense_w is not None), varlen)
+            if vgrads is not None:
+                for p, g in _varlen_owned(plan, varlen, vgrads):
+                    p.grad = g
             owners = params if params is not None and len(params) == len(tables) else tables
             for t, g in zip(owners, grads):
                 t.grad = g
