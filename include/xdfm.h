@@ -450,6 +450,28 @@ int xdfm_colsum(const float* g, long rows, int cols, long ld, float* ws, float* 
 int xdfm_relu_bwd_colsum(const float* g, const float* y, long rows, int cols, long ldg, long ldy, float* ws, float* gz,
                          float* out, void* stream);
 
+/* ------------------------------------------------------------------ dense layer on fp32 MFMA (csrc/dnn.hip)
+ * replaces: one layer of deepctr/layers/core.py:120-134 with its autograd -- y = act(x W^T + b), dx = gz W,
+ * dW = gz^T x, db = column sums of gz, where gz = (y > 0) ? g : 0 for a ReLU layer (y = the layer's output) and g itself
+ * with y = NULL.  gz is formed while the operands are loaded and never stored.  fp32 operands and accumulators
+ * (v_mfma_f32_32x32x2_f32); every global access is a dword, so rows need no alignment beyond 4 bytes.
+ * x [rows][ldx >= in], W [out][in] contiguous, b [out] or NULL, y / g [rows][ld >= out], dx [rows][lddx >= in],
+ * dW [out][in], db [out] or NULL (no bias gradient wanted).
+ * xdfm_dense_supported: rows >= 1, in in [1, 2^20], out a multiple of 32 in [32, 2^20]; the other entry points
+ * return XDFM_ERR_INVALID outside it.  act: XDFM_ACT_LINEAR or XDFM_ACT_RELU.
+ * xdfm_dense_bwd_w splits the contraction over the rows (256 rows a split, at most 32 splits), leaves one slab and
+ * one bias partial per split in ws (xdfm_dense_bwd_w_ws_elems floats; nothing in it needs initialising) and adds
+ * them in split order in a second launch: no atomics, the same bits on every run.  No entry point synchronises,
+ * allocates or issues a memset. */
+int xdfm_dense_supported(long rows, int in, int out);
+size_t xdfm_dense_bwd_w_ws_elems(long rows, int in, int out);          /* 0 outside xdfm_dense_supported */
+int xdfm_dense_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act, float* y,
+                   long ldy, void* stream);
+int xdfm_dense_bwd_x(const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in, float* dx,
+                     long lddx, void* stream);
+int xdfm_dense_bwd_w(const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in, int out,
+                     float* ws, float* dW, float* db, void* stream);
+
 /* ------------------------------------------------------------------ output head: link + loss (K8)
  * z_b = lin_b + <u_b, wu> + <v_b, wv> + bias,  pred = LINK(z),  loss = sum_b LOSS(pred_b, y_b).
  * replaces: cin_linear / dnn_linear (the two [B,K]x[K,1] products of deepctr/models/xdeepfm.py:95-105), the

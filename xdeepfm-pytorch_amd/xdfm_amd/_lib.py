@@ -122,6 +122,11 @@ SIGNATURES = {
     "xdfm_colsum_ws_elems": (c_size_t, [c_int]),
     "xdfm_colsum": (c_int, [P, c_long, c_int, c_long, P, P, P]),
     "xdfm_relu_bwd_colsum": (c_int, [P, P, c_long, c_int, c_long, c_long, P, P, P, P]),
+    "xdfm_dense_supported": (c_int, [c_long, c_int, c_int]),
+    "xdfm_dense_bwd_w_ws_elems": (c_size_t, [c_long, c_int, c_int]),
+    "xdfm_dense_fwd": (c_int, [P, c_long, c_int, c_long, P, c_int, P, c_int, P, c_long, P]),
+    "xdfm_dense_bwd_x": (c_int, [P, c_long, P, c_long, c_long, c_int, P, c_int, P, c_long, P]),
+    "xdfm_dense_bwd_w": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, c_int, P, P, P, P]),
     "xdfm_l2_reg_fwd": (c_int, [P, P, P, c_int, P, P, P]),
     "xdfm_l2_reg_bwd": (c_int, [P, P, P, c_int, P, P, P, c_int, P]),
 }

@@ -203,9 +203,12 @@ class CINAttentionV2(_CINBase):
 
 
 class DNN(nn.Module):
-    """ReLU / linear MLP (deepctr/layers/core.py:67-134).  The GEMMs are far below 2 % of the step's
-    FLOPs and go to hipBLASLt through torch (ops.Dense: bias gradient by the library's memset-free column
-    sum, so that the step can be captured in a HIP graph); Dice / PReLU belong to other models of the zoo."""
+    """ReLU / linear MLP (deepctr/layers/core.py:67-134).  Its GEMMs are far below 2 % of the step's FLOPs but, run as
+    six library GEMMs plus the mask and bias-gradient passes, were 7.5 % of the flagship step's time: layers whose
+    width is a multiple of 32 run their backward in the fp32-MFMA kernels of csrc/dnn.hip (ops.Dense / ops.DenseReLU,
+    `XDFM_DNN_NATIVE`).  Other widths keep hipBLASLt through torch, with the bias gradient by the library's
+    memset-free column sum; either way the step can be captured in a HIP graph.  Dice / PReLU belong to other models of
+    the zoo."""
 
     def __init__(self, inputs_dim, hidden_units, activation='relu', l2_reg=0, dropout_rate=0, use_bn=False,
                  init_std=0.0001, dice_dim=3, seed=1024, device='cpu'):

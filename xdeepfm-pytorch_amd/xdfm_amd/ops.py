@@ -883,21 +883,95 @@ def attn_pool(fm, B, D, mhsa_layers, layer_norms, pooling, use_res):
 # --------------------------------------------------------------------------------------------- #
 # dense layer                                                                                    #
 # --------------------------------------------------------------------------------------------- #
+def _env_switch(environ, key, default=True):
+    """'0' turns a switch off; unset or anything else leaves the default."""
+    v = environ.get(key)
+    return default if v is None else v != "0"
+
+
+# XDFM_DNN_NATIVE (default 1): dense layers run the fp32-MFMA kernels of csrc/dnn.hip where xdfm_dense_supported says so.
+# Read once, at import; tools/dnn_probe.py and the tests flip this attribute to run both paths in one process (a captured
+# graph keeps the path it was captured with).
+DNN_NATIVE = _env_switch(os.environ, "XDFM_DNN_NATIVE")
+# Per operation: the forward kernel (xdfm_dense_fwd) does not beat its library counterpart at the flagship shapes (16.8
+# against 16.0 us for 4096 x 429 -> 256, 11.5 against 9.9 us for 256 -> 256; DESIGN 4.3d), so the forward stays on the
+# library GEMM with its fused bias / ReLU epilogue.  The two backward kernels replace three launches each and do win.
+DNN_NATIVE_FWD = False
+
+
+def _ld(t):
+    """Row pitch of a 2-D tensor whose rows are contiguous (a one-row tensor's stride(0) is arbitrary)."""
+    return max(int(t.stride(0)), int(t.shape[1]))
+
+
+def _rows_ok(t):
+    return t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) >= t.shape[1])
+
+
+def dense_native(x, W, b=None):
+    """Does y = x W^T + b run the native kernels?  fp32 device tensors, x [rows][in] with contiguous rows, W [out][in]
+    contiguous, out a multiple of 32 (xdfm_dense_supported), and the XDFM_DNN_NATIVE switch on."""
+    if not (DNN_NATIVE and x.is_cuda and W.is_cuda and x.dim() == 2 and W.dim() == 2 and x.dtype == torch.float32
+            and W.dtype == torch.float32 and x.shape[0] >= 1 and x.shape[1] == W.shape[1] and W.is_contiguous() and _rows_ok(x)):
+        return False
+    if b is not None and not (b.is_cuda and b.dtype == torch.float32 and b.dim() == 1 and b.is_contiguous()):
+        return False
+    return bool(_lib.load().xdfm_dense_supported(x.shape[0], x.shape[1], W.shape[0]))
+
+
+def _dense_fwd_native(x, W, b, act):
+    lib = _lib.load()
+    rows, k = x.shape
+    out = W.shape[0]
+    y = torch.empty(rows, out, dtype=torch.float32, device=x.device)
+    _lib.check(_run("dense_fwd", 0.0, lambda: lib.xdfm_dense_fwd(_ptr(x), rows, k, _ld(x), _ptr(W), out, _ptr(b), act, _ptr(y), out,
+                                                                 _stream())), "dense_fwd")
+    return y
+
+
+def _dense_bwd_native(g, y, x, W, need_dx, need_dw, need_db):
+    """(dx, dW, db) of one layer; y: the ReLU layer's output (its mask is applied while g is loaded) or None."""
+    lib = _lib.load()
+    rows, k = x.shape
+    out = W.shape[0]
+    if not _rows_ok(g):
+        g = g.contiguous()
+    ldy = _ld(y) if y is not None else 0
+    dx = dW = db = None
+    if need_dx:
+        dx = torch.empty(rows, k, dtype=torch.float32, device=g.device)
+        _lib.check(_run("dense_bwd_x", 0.0, lambda: lib.xdfm_dense_bwd_x(_ptr(g), _ld(g), _ptr(y), ldy, rows, out, _ptr(W), k, _ptr(dx), k,
+                                                                         _stream())), "dense_bwd_x")
+    if need_dw or need_db:
+        ws = torch.empty(lib.xdfm_dense_bwd_w_ws_elems(rows, k, out), dtype=torch.float32, device=g.device)
+        dW = torch.empty(out, k, dtype=torch.float32, device=g.device)
+        db = torch.empty(out, dtype=torch.float32, device=g.device) if need_db else None
+        _lib.check(_run("dense_bwd_w", 0.0, lambda: lib.xdfm_dense_bwd_w(_ptr(g), _ld(g), _ptr(y), ldy, _ptr(x), _ld(x), rows, k, out,
+                                                                         _ptr(ws), _ptr(dW), _ptr(db), _stream())), "dense_bwd_w")
+    return dx, dW if need_dw else None, db
+
+
 class Dense(torch.autograd.Function):
-    """y = x W^T + b (deepctr/layers/core.py:120-134).  The three GEMMs stay with hipBLASLt; the bias
-    gradient is the library's own column sum, because ATen's `sum(0)` zeroes a semaphore buffer with
-    hipMemsetAsync and a memset node inside a captured HIP graph is not ordered reliably on this stack
-    (tools/graph_memset_probe.py) -- with it the train step contains no memset at all."""
+    """y = x W^T + b (deepctr/layers/core.py:120-134).  Where `dense_native` holds, both gradients run the fp32-MFMA
+    kernels of csrc/dnn.hip (the bias gradient comes out of the weight-gradient kernel; the forward only with
+    DNN_NATIVE_FWD).  Elsewhere the three GEMMs stay with hipBLASLt and the bias gradient is the library's own column sum, because ATen's `sum(0)` zeroes a
+    semaphore buffer with hipMemsetAsync and a memset node inside a captured HIP graph is not ordered reliably on this
+    stack (tools/graph_memset_probe.py) -- either way the train step contains no memset at all."""
 
     @staticmethod
     def forward(ctx, x, W, b):
         ctx.save_for_backward(x, W)
         ctx.has_bias = b is not None
+        if DNN_NATIVE_FWD and dense_native(x, W, b):
+            return _dense_fwd_native(x, W, b, ACT_CODES["linear"])
         return torch.nn.functional.linear(x, W, b)
 
     @staticmethod
     def backward(ctx, g):
         x, W = ctx.saved_tensors
+        if dense_native(x, W):
+            return _dense_bwd_native(g, None, x, W, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                     ctx.has_bias and ctx.needs_input_grad[2])
         g = g.contiguous()
         dx = g.mm(W) if ctx.needs_input_grad[0] else None
         dW = g.t().mm(x) if ctx.needs_input_grad[1] else None
@@ -912,19 +986,28 @@ class Dense(torch.autograd.Function):
 
 
 class DenseReLU(torch.autograd.Function):
-    """y = relu(x W^T + b): the ReLU rides in the GEMM's epilogue (hipBLASLt, `torch._addmm_activation`), and its
-    backward mask is applied by the pass that sums the bias gradient (`xdfm_relu_bwd_colsum`) -- two launches fewer
-    each way per hidden layer than linear + nn.ReLU (deepctr/layers/core.py:120-134)."""
+    """y = relu(x W^T + b).  Native (`dense_native`): the backward kernels
+    apply the mask (y > 0) while they load g, so no masked copy of g is allocated or written, and the bias gradient is a
+    by-product of the weight-gradient kernel (with DNN_NATIVE_FWD, bias and ReLU in the epilogue of xdfm_dense_fwd too).
+    Forward, and elsewhere the backward as well: the ReLU rides in the library GEMM's epilogue (hipBLASLt,
+    `torch._addmm_activation`), and its backward mask is applied by the pass that sums the bias gradient
+    (`xdfm_relu_bwd_colsum`) -- two launches fewer each way per hidden layer than linear + nn.ReLU
+    (deepctr/layers/core.py:120-134)."""
 
     @staticmethod
     def forward(ctx, x, W, b):
-        y = torch._addmm_activation(b, x, W.t(), use_gelu=False)
+        if DNN_NATIVE_FWD and dense_native(x, W, b):
+            y = _dense_fwd_native(x, W, b, ACT_CODES["relu"])
+        else:
+            y = torch._addmm_activation(b, x, W.t(), use_gelu=False)
         ctx.save_for_backward(x, W, y)
         return y
 
     @staticmethod
     def backward(ctx, g):
         x, W, y = ctx.saved_tensors
+        if dense_native(x, W):
+            return _dense_bwd_native(g, y, x, W, *ctx.needs_input_grad)
         lib = _lib.load()
         g = g.contiguous()
         rows, cols = g.shape
