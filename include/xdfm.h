@@ -461,7 +461,7 @@ int xdfm_relu_bwd_colsum(const float* g, const float* y, long rows, int cols, lo
  * return XDFM_ERR_INVALID outside it.  act: XDFM_ACT_LINEAR or XDFM_ACT_RELU.
  * xdfm_dense_bwd_w splits the contraction over the rows (256 rows a split, at most 32 splits), leaves one slab and
  * one bias partial per split in ws (xdfm_dense_bwd_w_ws_elems floats; nothing in it needs initialising) and adds
- * them in split order in a second launch: no atomics, the same bits on every run.  No entry point synchronises,
+ * them over a fixed pairwise tree in a second launch: no atomics, the same bits on every run.  No entry point synchronises,
  * allocates or issues a memset. */
 int xdfm_dense_supported(long rows, int in, int out);
 size_t xdfm_dense_bwd_w_ws_elems(long rows, int in, int out);          /* 0 outside xdfm_dense_supported */

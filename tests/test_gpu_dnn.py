@@ -10,7 +10,11 @@ measured pairs.
 Inputs are O(1): standard normal x and g, W ~ N(0, 1 / in), b ~ N(0, 1).  A ReLU layer's y holds exact zeros in about
 half of its cells, each facing a non-zero g, so the mask's `> 0` edge decides real values.  Both backward paths and the
 reference take the SAME y (the native forward's), so that a pre-activation within rounding of zero cannot flip a mask
-between them.  The strided case passes x, g and y as column windows of wider matrices (ld > columns)."""
+between them.  The strided cases pass x, g and y as column windows of wider matrices (ld > columns).
+
+Also here: the needs_input_grad combinations of both autograd functions (returned tensors against the full call's bits, the
+launches that ran) and a chained layers.DNN tower with the native switch on and off against a float64 replay.  The entry
+points called directly -- exact integer cases, pitches, guards -- are in tests/test_gpu_dnn_abi.py."""
 import faulthandler
 
 import numpy as np
@@ -30,6 +34,14 @@ CASES = {
     "r257_k256_o256_none": (257, 256, 256, False, True, False),
     "r520_k40_o64_relu": (520, 40, 64, True, True, False),
     "r520_k40_o64_none_nobias": (520, 40, 64, False, False, False),
+    # out a multiple of 32 but not of 64 (a half-empty last tile), one past / one short of the 64-tile, 5 / 9 / 29 splits of
+    # the weight gradient (9: the last split holds one row; 29: rows beyond DN_MAX_SPLIT * 256), exactly 256 rows: one split
+    "r65_k65_o96_relu": (65, 65, 96, True, True, False),
+    "r63_k31_o160_none": (63, 31, 160, False, True, False),
+    "r1100_k13_o32_relu": (1100, 13, 32, True, True, False),
+    "r2049_k40_o64_relu_strided": (2049, 40, 64, True, True, True),
+    "r8225_k65_o96_relu": (8225, 65, 96, True, True, False),
+    "r256_k33_o32_relu": (256, 33, 32, True, True, False),
 }
 _CACHE = {}
 
@@ -225,3 +237,123 @@ def test_ops_dense_relu_runs_the_native_kernels_when_supported_and_the_library_o
         _same_as_stock(un, x, W, b)
     finally:
         ops.DNN_NATIVE, ops.PROFILE = saved_native, saved_profile
+
+
+@pytest.mark.parametrize("relu", [True, False], ids=["DenseReLU", "Dense"])
+def test_needs_input_grad_combinations_return_the_full_calls_bits_and_launch_only_what_is_needed(relu):
+    """(65, 65, 96): no dx, no dW but db, no db and -- Dense -- a layer without bias.  What is returned equals the full
+    call's bits, the rest is None, and the ops.PROFILE brackets list the launches that ran, nothing else."""
+    from xdfm_amd import ops
+    dev = _dev()
+    rows, k, out = 65, 65, 96
+    gen = torch.Generator().manual_seed(4242)
+    x = torch.randn(rows, k, generator=gen).to(dev)
+    W = (torch.randn(out, k, generator=gen) / float(np.sqrt(k))).to(dev)
+    b = torch.randn(out, generator=gen).to(dev)
+    g = torch.randn(rows, out, generator=gen).to(dev)
+    fn = ops.DenseReLU if relu else ops.Dense
+    saved_native, saved_profile = ops.DNN_NATIVE, ops.PROFILE
+    try:
+        ops.DNN_NATIVE = True
+        assert ops.dense_native(x, W, b)
+        y = torch.relu(torch.addmm(b, x, W.t())) if relu else None
+        if relu:
+            assert 0 < int((y == 0).sum()) < y.numel()
+
+        def run(needs, has_bias=True):
+            ctx = _Ctx(needs)
+            ctx.has_bias = has_bias
+            ctx.saved_tensors = (x, W, y) if relu else (x, W)
+            ops.PROFILE = []
+            got = fn.backward(ctx, g)
+            names = [p[0] for p in ops.PROFILE]
+            ops.PROFILE = None
+            return got, names
+
+        full, names = run((True, True, True))
+        assert names == ["dense_bwd_x", "dense_bwd_w"] and all(t is not None for t in full)
+        combos = [((False, True, True), True, ["dense_bwd_w"]), ((True, False, True), True, ["dense_bwd_x", "dense_bwd_w"]),
+                  ((True, True, False), True, ["dense_bwd_x", "dense_bwd_w"])]
+        if not relu:
+            combos.append(((True, True, True), False, ["dense_bwd_x", "dense_bwd_w"]))
+        for needs, has_bias, launches in combos:
+            got, names = run(needs, has_bias)
+            assert names == launches, (needs, has_bias, names)
+            wanted = (needs[0], needs[1], needs[2] and has_bias)
+            for key, t, ref, w in zip(("dx", "dW", "db"), got, full, wanted):
+                if w:
+                    assert t is not None and torch.equal(t, ref), (needs, has_bias, key)
+                else:
+                    assert t is None, (needs, has_bias, key)
+    finally:
+        ops.DNN_NATIVE, ops.PROFILE = saved_native, saved_profile
+
+
+def test_chained_tower_native_against_library_and_a_float64_replay():
+    """layers.DNN (32, 96, 32), relu, rows 65, input width 13, with ops.DNN_NATIVE on and off.  Both runs use the library
+    forward, so their outputs -- and hence their masks -- are the same bits.  Every gradient of the native run is within
+    max(2 x the library run's error, 1 ulp) of a float64 replay, layer by layer, of the backward.
+
+    The replay takes its masks (and each layer's input) from the fp32 activations of the run, not from a float64 forward:
+    a pre-activation within rounding of zero would open a cell in one precision and close it in the other, and the two
+    backward passes would then differentiate different functions -- a difference of the whole g in that cell, not a
+    rounding error.  The kernels under test see the fp32 activations; so does the reference."""
+    from xdfm_amd import layers, ops
+    dev = _dev()
+    rows, k, hidden = 65, 13, (32, 96, 32)
+    gen = torch.Generator().manual_seed(31337)
+    net = layers.DNN(k, hidden, activation="relu", dropout_rate=0, use_bn=False, device=dev)
+    with torch.no_grad():
+        for lin in net.linears:
+            lin.weight.copy_((torch.randn(lin.weight.shape, generator=gen) / float(np.sqrt(lin.weight.shape[1]))).to(dev))
+            lin.bias.copy_(torch.randn(lin.bias.shape, generator=gen).to(dev))
+    x0 = torch.randn(rows, k, generator=gen)
+    g0 = torch.randn(rows, hidden[-1], generator=gen)
+    params = [p for lin in net.linears for p in (lin.weight, lin.bias)]
+    saved_native, saved_profile = ops.DNN_NATIVE, ops.PROFILE
+    runs = {}
+    try:
+        for native in (True, False):
+            ops.DNN_NATIVE, ops.PROFILE = native, []
+            x = x0.to(dev).requires_grad_(True)
+            for p in params:
+                p.grad = None
+            y = net(x)
+            y.backward(g0.to(dev))
+            names = [p[0] for p in ops.PROFILE if p[0] != "dense_fwd"]          # the forward's only with DNN_NATIVE_FWD
+            ops.PROFILE = None
+            assert names == (["dense_bwd_x", "dense_bwd_w"] * 3 if native else []), names
+            runs[native] = dict(y=y.detach().clone(), grads=[x.grad.clone()] + [p.grad.clone() for p in params])
+        # the fp32 activations of the run: ops.dense_relu per layer, the library forward both runs used
+        ops.DNN_NATIVE = False
+        acts = [x0.to(dev)]
+        with torch.no_grad():
+            for lin in net.linears:
+                acts.append(ops.dense_relu(acts[-1], lin.weight, lin.bias))
+    finally:
+        ops.DNN_NATIVE, ops.PROFILE = saved_native, saved_profile
+    assert torch.equal(runs[True]["y"], runs[False]["y"]) and torch.equal(acts[-1], runs[True]["y"])
+    acts = [a.cpu() for a in acts]
+    for a in acts[1:]:
+        assert 0 < int((a == 0).sum()) < a.numel()
+    # float64 replay of the backward, last layer first
+    g6 = g0.double()
+    ref = {}
+    for i in reversed(range(3)):
+        W6 = net.linears[i].weight.detach().cpu().double()
+        gz = torch.where(acts[i + 1] > 0, g6, torch.zeros_like(g6))
+        ref[1 + 2 * i], ref[2 + 2 * i] = gz.t() @ acts[i].double(), gz.sum(0)
+        g6 = gz @ W6
+    ref[0] = g6
+    labels = ["dx"] + ["%s%d" % (n, i) for i in range(3) for n in ("dW", "db")]
+    bad = []
+    for j, label in enumerate(labels):
+        want = ref[j]
+        e_nat = float((runs[True]["grads"][j].cpu().double() - want).abs().max())
+        e_lib = float((runs[False]["grads"][j].cpu().double() - want).abs().max())
+        floor = float(np.spacing(np.float32(want.abs().max())))
+        print("%-28s %-3s native %.3e  library %.3e  floor (1 ulp) %.3e" % ("tower_r65_k13_32_96_32", label, e_nat, e_lib, floor))
+        assert runs[True]["grads"][j].shape == want.shape
+        if not e_nat <= max(FACTOR * e_lib, floor):
+            bad.append((label, e_nat, e_lib, floor))
+    assert not bad, bad
