@@ -573,7 +573,8 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
         int f = 0;
         while (f + 1 < F && fields[f + 1].blk0 <= gb) ++f;              // the field this block of 256 vocabulary rows belongs to
         const VxField fd = fields[f];
-        if (ntiles == 0) {                              // no row at all: the gradients are exact zeros, no scale is read
+        if (ntiles == 0 || fd.V == 1) {                 // no row at all: the gradients are exact zeros, no scale is read; a head of
+                                                        // one entry: softmax == onehot == 1, so they are exact zeros as well
             const long v0 = (long)(gb - fd.blk0) * (32 * VX_WS_WAVES) + 32 * w + c;
             if (v0 < fd.V) {
                 if (hh == 0 && fd.db) fd.db[v0] = 0.f;
@@ -591,28 +592,39 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
         const float* __restrict__ lse2 = lse2_all + (long)f * Rpad;
         const float* __restrict__ gs = gpack + 4L * F + (long)f * Rpad;
         const long* __restrict__ tgt = tgt_all + (long)f * cap;
-        const float sW = x3_pow2_scale(__uint_as_float(wmax_all[f]), 12);
-        const float cw = VX_LOG2E * hscale[1] / sW;
-        const float icw = -1.f / cw;                           // the tiles' lse values are parked as -lse / cw: z starts there
         const float inv_b = gpack[4 * f + 1], inv_w = inv_b * hscale[1];
         const long v = (long)blk * (32 * VX_WS_WAVES) + 32 * w + c;
         const bool live = v < V;
         const long vc = live ? v : V - 1;
+        // The wave's 32 rows are one block of the forward (vx_hs_kernel<KT, 0>::publish): the same power-of-two scale of the
+        // block's own maximum, the same hi / lo halves, and in zmma the same order of terms from zero, so that z has the
+        // forward's bits.  softmax = 2^(z - lse2) is then off by the rounding of lse2 alone (half an ulp: z - max is exact for
+        // the row's dominant entry); with one scale per head and accumulators started at -lse / cw it was several ulp(lse2),
+        // a relative error of 5e-4 at logits of 2e3.
         h8 bh[KS], bl[KS];
+        float sW;
         {
             const float4* __restrict__ src = reinterpret_cast<const float4*>(W + vc * K + 8 * hh);
+            float x[KS][8];
+            float amax = 0.f;
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 const float4 a = src[4 * s], b = src[4 * s + 1];
-                const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+                x[s][0] = a.x; x[s][1] = a.y; x[s][2] = a.z; x[s][3] = a.w; x[s][4] = b.x; x[s][5] = b.y; x[s][6] = b.z; x[s][7] = b.w;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) { x[s][e] = live ? x[s][e] : 0.f; amax = fmaxf(amax, fabsf(x[s][e])); }
+            }
+            sW = x3_pow2_scale(vx_wave_max(amax), 12);
+#pragma unroll
+            for (int s = 0; s < KS; ++s)
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
                     h2 p, q;
-                    x3_split2(live ? x[e] * sW : 0.f, live ? x[e + 1] * sW : 0.f, p, q);
+                    x3_split2(x[s][e] * sW, x[s][e + 1] * sW, p, q);
                     bh[s][e] = p.x; bh[s][e + 1] = p.y; bl[s][e] = q.x; bl[s][e + 1] = q.y;
                 }
-            }
         }
+        const float cw = VX_LOG2E * hscale[1] * (1.f / sW);
         const float b2 = live ? bias[vc] * VX_LOG2E : -INFINITY;
         const int vi = live ? (int)v : -2;
         f32x16 acc[KT];
@@ -623,9 +635,9 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
         float dbacc = 0.f;
 
         h8 stage[PER];
-        unsigned stage_l = 0u;                              // bits of -lse2 / cw or gs, or a target id
+        unsigned stage_l = 0u;                              // bits of lse2 or gs, or a target id
         auto fetch = [&](int sl) {                          // slot sl = tiles VX_WS_TP * sl ..; a tile past the last one repeats it with
-#pragma unroll                                              // zero gradients (gs is zero beyond R, the targets are -1)
+#pragma unroll                                              // zero gradients (gs is zero beyond R, the targets are -1) and lse2 = 1e38
             for (int i = 0; i < PER; ++i) {
                 const int e = threadIdx.x + i * NTH;
                 const int u = e / NTL, r = e - u * NTL;
@@ -634,7 +646,9 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
             }
             const int q = threadIdx.x >> 6, i = threadIdx.x & 63;          // q: 0 lse, 1 gs, 2 targets; i: row within the slot
             const long row = 32L * VX_WS_TP * sl + i;
-            if (q == 0) stage_l = __float_as_uint(lse2[row] * icw);
+            // the repeated tile's rows have lse2 = 0 in memory: z - 0 would be the last tile's bare logits, and 2^z = inf above 128
+            // turns the product with their zero gradient into NaN.  An lse2 of 1e38 makes every 2^(z - lse2) of such a row 0.
+            if (q == 0) stage_l = __float_as_uint(row < 32L * ntiles ? lse2[row] : -VX_NEG);
             else if (q == 1) stage_l = __float_as_uint(gs[row]);
             else if (q == 2) {
                 const long tv = row < R ? tgt[row] : -1;
@@ -660,16 +674,13 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
         __syncthreads();
         auto zmma = [&](int buf, int u, f32x16& z) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {                       // accumulators start at -lse[row] / cw
-                const float4 lq = *reinterpret_cast<const float4*>(L[buf].lse[u] + 8 * q + 4 * hh);
-                z[4 * q] = lq.x; z[4 * q + 1] = lq.y; z[4 * q + 2] = lq.z; z[4 * q + 3] = lq.w;
-            }
+            for (int r = 0; r < 16; ++r) z[r] = 0.f;
             if (dbg & 4) return;
 #pragma unroll
-            for (int s = 0; s < KS; ++s) {
+            for (int s = 0; s < KS; ++s) {                      // the forward's order: W lo * H hi, W hi * H lo, W hi * H hi
                 const h8 ah = L[buf].hf[u][(s * 2 + 0) * 64 + lane], al = L[buf].hf[u][(s * 2 + 1) * 64 + lane];
-                z = x3_mfma<3>(al, bh[s], z);
                 z = x3_mfma<3>(ah, bl[s], z);
+                z = x3_mfma<3>(al, bh[s], z);
                 z = x3_mfma<3>(ah, bh[s], z);
             }
         };
@@ -686,11 +697,12 @@ __global__ __launch_bounds__(64 * VX_WS_WAVES, 1) void vx_ws_kernel(
             for (int q = 0; q < 4; ++q) {
                 const float4 gq = *reinterpret_cast<const float4*>(L[buf].gs[u] + 8 * q + 4 * hh);
                 const int4 tq = *reinterpret_cast<const int4*>(L[buf].tgt[u] + 8 * q + 4 * hh);
+                const float4 lq = *reinterpret_cast<const float4*>(L[buf].lse[u] + 8 * q + 4 * hh);
                 // the row's own target entry is subtracted here, so dW / db are complete when they are stored
-                const float p0 = (vx_exp2(fmaf(z[4 * q], cw, b2)) - (tq.x == vi ? 1.f : 0.f)) * gq.x;
-                const float p1 = (vx_exp2(fmaf(z[4 * q + 1], cw, b2)) - (tq.y == vi ? 1.f : 0.f)) * gq.y;
-                const float p2 = (vx_exp2(fmaf(z[4 * q + 2], cw, b2)) - (tq.z == vi ? 1.f : 0.f)) * gq.z;
-                const float p3 = (vx_exp2(fmaf(z[4 * q + 3], cw, b2)) - (tq.w == vi ? 1.f : 0.f)) * gq.w;
+                const float p0 = (vx_exp2(fmaf(z[4 * q], cw, b2) - lq.x) - (tq.x == vi ? 1.f : 0.f)) * gq.x;
+                const float p1 = (vx_exp2(fmaf(z[4 * q + 1], cw, b2) - lq.y) - (tq.y == vi ? 1.f : 0.f)) * gq.y;
+                const float p2 = (vx_exp2(fmaf(z[4 * q + 2], cw, b2) - lq.z) - (tq.z == vi ? 1.f : 0.f)) * gq.z;
+                const float p3 = (vx_exp2(fmaf(z[4 * q + 3], cw, b2) - lq.w) - (tq.w == vi ? 1.f : 0.f)) * gq.w;
                 dbacc += (p0 + p1) + (p2 + p3);
                 h2 a, b;
                 const int sp = q >> 1, e = 4 * (q & 1);
