@@ -53,6 +53,8 @@
  * xdfm_compact_rows_fwd_n (K11 whose normaliser is counted over a second label vector: the global batch of a row-parallel step).
  * xdfm_varlen_pool_bwd_rows_ws_elems, xdfm_varlen_pool_bwd_rows (K2v over the exchanged rows of a row-parallel step: the positions
  * of the maxima are recomputed, not passed) -- additions again, the version stays 8.
+ * xdfm_dense_fwd_drop, xdfm_dense_bwd_x_drop, xdfm_dense_bwd_w_drop, xdfm_dense_dropout_mask (dropout of the DNN tower inside
+ * the dense kernels: a hashed keep mask, read back off the stored output) -- additions, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -471,6 +473,32 @@ int xdfm_dense_bwd_x(const float* g, long ldg, const float* y, long ldy, long ro
                      long lddx, void* stream);
 int xdfm_dense_bwd_w(const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in, int out,
                      float* ws, float* dW, float* db, void* stream);
+/* The same layer followed by dropout (deepctr/layers/core.py:134, nn.Dropout after the activation), in the same launches.
+ * Forward: y = keep ? relu(x W^T + b) * s : 0 with the fp32 s = 1.0f / (1.0f - p_drop), one rounding.  The keep bit of cell
+ * (layer, row, col) is a counter-based hash -- nothing is stored, and the draw matches nn.Dropout in distribution only (it
+ * is not torch's Philox stream), as the attention's does:
+ *     mix(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16          (32-bit, wrapping)
+ *     k    = mix((uint32)seed ^ ((uint32)layer * 0x9E3779B1))
+ *     rk   = mix(k + (uint32)(seed >> 32) + (uint32)(row0 + row) * 0x85EBCA77)
+ *     keep = mix(rk + (uint32)col * 0x9E3779B1) >= thresh,     thresh = min((uint32)(p_drop * 2^32), 2^32 - 1)
+ * seed: a DEVICE scalar the kernel reads (a captured graph sees a new value at every replay); layer >= 0 separates the
+ * layers that share one seed; row0 >= 0 is added to the row index, so a caller holding rows [row0, row0 + rows) of a batch
+ * draws that batch's bits.  y > 0 then holds exactly where the cell was kept and its pre-activation was positive, so the
+ * stored output is the whole mask: the backward calls take that y and compute dx, dW, db from gz = (y > 0) ? g * s : 0 with
+ * the same fp32 s the forward used (recomputed from p_drop), one rounding -- what native_dropout_backward followed by
+ * threshold_backward gives.  Splits, workspace (xdfm_dense_bwd_w_ws_elems) and summation order are those of
+ * xdfm_dense_bwd_w.  p_drop = 0 runs the plain kernels: the bits of the entry points above, any act, seed may be NULL.
+ * XDFM_ERR_INVALID: p_drop outside [0, 1); p_drop > 0 with seed = NULL, with act != XDFM_ACT_RELU (the backward reads the mask
+ * off y > 0) or, in the backward calls, with y = NULL; layer < 0; row0 < 0; whatever the plain entry points refuse.
+ * xdfm_dense_dropout_mask writes keep [rows][out] as bytes (1 = kept): a test hook. */
+int xdfm_dense_fwd_drop(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act, float* y,
+                        long ldy, float p_drop, const unsigned long long* seed, int layer, long row0, void* stream);
+int xdfm_dense_bwd_x_drop(const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in, float* dx,
+                          long lddx, float p_drop, void* stream);
+int xdfm_dense_bwd_w_drop(const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in, int out,
+                          float* ws, float* dW, float* db, float p_drop, void* stream);
+int xdfm_dense_dropout_mask(long rows, int out, float p_drop, const unsigned long long* seed, int layer, long row0,
+                            unsigned char* keep, void* stream);
 
 /* ------------------------------------------------------------------ output head: link + loss (K8)
  * z_b = lin_b + <u_b, wu> + <v_b, wv> + bias,  pred = LINK(z),  loss = sum_b LOSS(pred_b, y_b).

@@ -4,6 +4,9 @@ the two layers of the flagship DNN tower (batch 4096: 429 -> 256 and 256 -> 256,
   python tools/dnn_probe.py            per operation: forward, input gradient, weight + bias gradient; then a whole layer
                                        forward + backward through ops.dense_relu with ops.DNN_NATIVE on and off
   python tools/dnn_probe.py --rows N   another batch size
+  python tools/dnn_probe.py --dropout P   the native dropout (ops.dense_relu_dropout) against ops.dense_relu + nn.Dropout: one
+                                       layer forward + backward at both shapes, then the flagship train step with
+                                       dnn_dropout = P under both settings of ops.DNN_DROPOUT_NATIVE (profiles/dnn_dropout_probe.md)
 
 Library arm of an operation = what runs with XDFM_DNN_NATIVE=0: torch._addmm_activation; gz.mm(W); xdfm_relu_bwd_colsum
 (mask pass + bias gradient, once per layer, booked with the weight gradient) + gz.t().mm(x).
@@ -81,6 +84,89 @@ def layer_pass(x, W, b, g):
 def set_arm(native):
     ops.DNN_NATIVE = native
 
+
+def dropout_layer_pass(x, W, b, g, p, native, drop):
+    a = [x.detach().requires_grad_(True), W.detach().requires_grad_(True), b.detach().requires_grad_(True)]
+    if native:
+        ops.dense_relu_dropout(a[0], a[1], a[2], p, ops.draw_dropout_seed(x.device), 0).backward(g)      # the seed draw is part of the arm
+    else:
+        drop(ops.dense_relu(*a)).backward(g)
+
+
+def flagship_step_model(p, native):
+    """bench.py's criteo_c2 model (1e5 rows per table: the tower does not see the tables) with dnn_dropout = p, its train
+    step captured with ops.DNN_DROPOUT_NATIVE = native."""
+    import bench
+    from xdfm_amd import graphstep
+    cfg = dict(bench.WORKLOADS["criteo_c2"])
+    vocab = bench.preset_vocab("mid", cfg["n_sparse"])
+    from deepctr.inputs import DenseFeat, SparseFeat
+    from deepctr.models import xDeepFM
+    cols = [SparseFeat("C%d" % (i + 1), v, cfg["emb_dim"]) for i, v in enumerate(vocab)]
+    cols += [DenseFeat("I%d" % (i + 1), 1) for i in range(cfg["n_dense"])]
+    torch.manual_seed(0)
+    model = xDeepFM(cols, cols, dnn_hidden_units=cfg["dnn"], cin_layer_size=cfg["cin"], l2_reg_dnn=1e-5, dnn_dropout=p, device=dev)
+    model.compile("adam", "binary_crossentropy", metrics=[])
+    model.train()
+    step = model.__dict__["_graphed_step"] = graphstep.GraphedStep(model)
+    batches = [(torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev))
+               for X, y in bench.synthetic_batches(4, ROWS, vocab, cfg["n_dense"], seed=1)]
+    ops.DNN_DROPOUT_NATIVE = native
+    for i in range(5):                                   # two eager steps, the capture, two replays
+        model.train_on_batch(*batches[i % len(batches)])
+    torch.cuda.synchronize()
+    ops.DNN_DROPOUT_NATIVE = True
+    nodes = [e.nodes for e in step.entries.values() if e.graph is not None]
+    assert step.replays >= 2 and not step.disabled and len(nodes) == 1, (step.replays, step.disabled, nodes)
+    return model, batches, nodes[0]
+
+
+def dropout_probe(p):
+    """--dropout P: (a) one layer forward + backward through ops.dense_relu_dropout against ops.dense_relu + nn.Dropout at both
+    flagship layers; (b) the flagship train step with dnn_dropout = P under both settings of ops.DNN_DROPOUT_NATIVE.  Alternating
+    blocks in one process; `spread_us` is the largest (max - min) over an arm's blocks."""
+    torch.manual_seed(0)
+    drop = torch.nn.Dropout(p).train()
+    for k, out in LAYERS:
+        x = torch.randn(ROWS, k, device=dev)
+        W = torch.randn(out, k, device=dev) / k ** 0.5
+        b = torch.randn(out, device=dev)
+        g = torch.randn(ROWS, out, device=dev)
+        assert ops.dense_dropout_native(x, W, b, p)
+        graphs = {native: graph_of(lambda native=native: dropout_layer_pass(x, W, b, g, p, native, drop)) for native in (True, False)}
+        t = {True: [], False: []}
+        for blk in range(BLOCKS):
+            for native in ((True, False) if blk % 2 == 0 else (False, True)):
+                t[native].append(us_per_call(graphs[native]))
+        print(json.dumps({"what": "dropout %g, layer forward + backward %d x %d -> %d" % (p, ROWS, k, out),
+                          "native_median_us": round(statistics.median(t[True]), 2), "stock_median_us": round(statistics.median(t[False]), 2),
+                          "native_min_max_us": [round(min(t[True]), 2), round(max(t[True]), 2)],
+                          "stock_min_max_us": [round(min(t[False]), 2), round(max(t[False]), 2)],
+                          "spread_us": round(max(max(v) - min(v) for v in t.values()), 2)}), flush=True)
+    arms = {native: flagship_step_model(p, native) for native in (True, False)}
+    STEPS = 20
+    t = {True: [], False: []}
+    for blk in range(BLOCKS):
+        for native in ((True, False) if blk % 2 == 0 else (False, True)):
+            model, batches, _ = arms[native]
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(STEPS):
+                model.train_on_batch(*batches[i % len(batches)])
+            e1.record()
+            torch.cuda.synchronize()
+            t[native].append(e0.elapsed_time(e1) * 1e3 / STEPS)
+    print(json.dumps({"what": "flagship train step (criteo_c2, 1e5-row tables, batch %d), dnn_dropout %g" % (ROWS, p),
+                      "native_median_us": round(statistics.median(t[True]), 1), "stock_median_us": round(statistics.median(t[False]), 1),
+                      "native_min_max_us": [round(min(t[True]), 1), round(max(t[True]), 1)],
+                      "stock_min_max_us": [round(min(t[False]), 1), round(max(t[False]), 1)],
+                      "spread_us": round(max(max(v) - min(v) for v in t.values()), 1),
+                      "graph_nodes": {"native": arms[True][2], "stock": arms[False][2]}}), flush=True)
+
+
+if "--dropout" in sys.argv:
+    dropout_probe(float(sys.argv[sys.argv.index("--dropout") + 1]))
+    sys.exit(0)
 
 torch.manual_seed(0)
 total = {"native": 0.0, "library": 0.0}

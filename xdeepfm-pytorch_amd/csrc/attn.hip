@@ -137,10 +137,6 @@ struct AttnDrop {
     unsigned thresh;                    // keep iff hash >= thresh   (thresh = p * 2^32)
     float keep_scale;                   // 1 / (1 - p)
 };
-__device__ __forceinline__ unsigned drop_mix(unsigned x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
 __device__ __forceinline__ unsigned drop_row_key(unsigned long long seed, int b, int layer, int n_layers, int h, int nh,
                                                  int q) {
     const unsigned w0 = ((unsigned)b * (unsigned)n_layers + (unsigned)layer) * (unsigned)nh + (unsigned)h;
@@ -1027,9 +1023,8 @@ static int attn_drop_args(float p_drop, const unsigned long long* seed, AttnDrop
     if (p_drop == 0.f) return 0;
     if (!seed) return xdfm_fail(XDFM_ERR_INVALID, "%s: dropout p=%g needs a device seed", who, p_drop);
     d->seed = seed;
-    const double t = (double)p_drop * 4294967296.0;
-    d->thresh = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-    d->keep_scale = 1.0f / (1.0f - p_drop);
+    d->thresh = xdfm_drop_thresh(p_drop);
+    d->keep_scale = xdfm_drop_keep_scale(p_drop);
     return 0;
 }
 

@@ -4,7 +4,7 @@
 // gradient), the threshold_backward pass that wrote gz = (y > 0) ? g : 0, and the bias gradient's column sum with its
 // finish launch.  gz is never stored: the two backward kernels form it while they stage their operand.
 // (The host side runs the two backward kernels; the forward kernel does not beat the library GEMM yet and is kept,
-// tested, behind ops.DNN_NATIVE_FWD.)
+// tested, behind ops.DNN_NATIVE_FWD.  With dropout the host runs all three: see "Dropout" below.)
 //
 // One kernel template serves the three products C[M x N] = sum_k A[k][m] * B[k][n]:
 //   forward   y  = act(x W^T + b)   M = rows, N = out, K = in     A = x  (k contiguous)   B = W  (k contiguous)
@@ -27,6 +27,12 @@
 // dW splits the contraction over the rows across blockIdx.z; every split leaves a slab and, for the bias gradient, the
 // column sums of its gz rows.  A second launch adds them over a fixed pairwise tree: no atomics, no zeroed cells, same bits
 // every run.
+//
+// Dropout (the _drop entry points; deepctr/layers/core.py:134 applies nn.Dropout after every activation).  The forward's
+// DROP epilogue stores d = keep ? relu(z) * s : 0 with s = 1 / (1 - p) and keep a counter-based hash of (seed, layer, row,
+// column): d > 0 holds exactly where the cell was kept AND z > 0, so the layer's output is its own mask.  The two backward
+// kernels already select on y > 0 while they stage g; their SCALED instances multiply the selected value by the same s.
+// No mask is stored or regenerated, no launch is added either way.
 #include "xdfm_internal.h"
 
 #define DN_T 64                    // tile edge (rows and columns of C per workgroup)
@@ -46,7 +52,23 @@ struct DnArgs {
     const float* bias; int relu;                         // forward epilogue
     float* dbpart;                                       // dW: split z leaves its column sums of gz at dbpart + z * M
     long M, N, K, kper;                                  // kper: contraction indices per split (a multiple of DN_K)
+    // dropout (behind the fields above: the plain instances read none of these)
+    const unsigned long long* seed;                      // DROP epilogue: device scalar, read by the kernel
+    long row0;                                           //   row r of this call is row row0 + r of the mask
+    unsigned thresh; int layer;                          //   keep iff hash >= thresh
+    float keep_scale;                                    // 1 / (1 - p): DROP epilogue and the SCALED stagings of g
 };
+
+// Keep bit of cell (layer, row, col): three rounds of drop_mix, the shape of the attention's key (attn.hip, drop_row_key).
+__device__ __forceinline__ unsigned dn_drop_layer_key(unsigned long long seed, int layer) {
+    return drop_mix((unsigned)seed ^ ((unsigned)layer * 0x9E3779B1U));
+}
+__device__ __forceinline__ unsigned dn_drop_row_key(unsigned layer_key, unsigned long long seed, long row) {
+    return drop_mix(layer_key + (unsigned)(seed >> 32) + (unsigned)row * 0x85EBCA77U);
+}
+__device__ __forceinline__ bool dn_drop_keep(unsigned row_key, long col, unsigned thresh) {
+    return drop_mix(row_key + (unsigned)col * 0x9E3779B1U) >= thresh;
+}
 
 __device__ __forceinline__ int dn_lds(int p, int m) { return p * DN_PLANE + (m << 2); }
 
@@ -55,7 +77,9 @@ __device__ __forceinline__ int dn_lds(int p, int m) { return p * DN_PLANE + (m <
 // write (hipcc puts a load behind a condition into a branch of its own and waits for it there).
 // KC (k contiguous in memory, src[m * ld + k]): lanes run along k, element e is row (t >> 5) + 16 e.
 // otherwise (m contiguous, src[k * ld + m]):    lanes run along m, wave q stages plane q.
-template <bool KC, bool MASK>
+// SCALED (with MASK): a live value is multiplied by gscale, one rounding -- the gradient through a dropout layer whose
+// kept cells are the y > 0 ones.
+template <bool KC, bool MASK, bool SCALED = false>
 struct DnStage {
     float v[DN_E], y[DN_E];
     long off[DN_E], offy[DN_E];    // KC: row offsets of the (clamped) rows; otherwise [0]: the (clamped) column
@@ -117,12 +141,13 @@ struct DnStage {
         }
     }
     // returns the sum of the staged values in element order (the bias gradient's share of this thread)
-    __device__ __forceinline__ float store(float* __restrict__ tile) {
+    __device__ __forceinline__ float store(float* __restrict__ tile, float gscale = 1.f) {
         const int t = threadIdx.x;
 #pragma unroll
         for (int e = 0; e < DN_E; ++e) {
             const bool live = (ok >> e & 1u) && (!MASK || y[e] > 0.f);
-            v[e] = live ? v[e] : 0.f;
+            if (SCALED) v[e] = live ? v[e] * gscale : 0.f;
+            else v[e] = live ? v[e] : 0.f;
         }
         if (KC) {
             const int k = t & 31, p = (k >> 3) * 2 + (k & 1);
@@ -139,7 +164,8 @@ struct DnStage {
     }
 };
 
-enum { DN_EPI_FWD = 0, DN_EPI_PLAIN = 1, DN_EPI_SLAB = 2 };
+// the last three are the dropout instances of the first three: the forward's DROP epilogue, dX and dW with g scaled
+enum { DN_EPI_FWD = 0, DN_EPI_PLAIN = 1, DN_EPI_SLAB = 2, DN_EPI_FWD_DROP = 3, DN_EPI_PLAIN_SCALED = 4, DN_EPI_SLAB_SCALED = 5 };
 
 template <bool AKC, bool BKC, bool MASK, int EPI>
 __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
@@ -152,7 +178,12 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
     const long kend = kbeg + a.kper < a.K ? kbeg + a.kper : a.K;
     const int steps = (int)((kend - kbeg + DN_K - 1) / DN_K);
 
-    DnStage<AKC, MASK> sa;
+    constexpr bool FWD = EPI == DN_EPI_FWD || EPI == DN_EPI_FWD_DROP;
+    constexpr bool SLAB = EPI == DN_EPI_SLAB || EPI == DN_EPI_SLAB_SCALED;
+    constexpr bool SCALED = EPI == DN_EPI_PLAIN_SCALED || EPI == DN_EPI_SLAB_SCALED;
+    static_assert(!SCALED || MASK, "g is scaled where the mask is open");
+    const float gscale = SCALED ? a.keep_scale : 1.f;
+    DnStage<AKC, MASK, SCALED> sa;
     DnStage<BKC, false> sb;
     sa.init(a.lda, a.lday, m0, a.M);
     sb.init(a.ldb, 0, n0, a.N);
@@ -163,7 +194,7 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
 
     sa.load(a.A, a.Ay, a.lda, a.lday, kbeg, kend);
     sb.load(a.B, nullptr, a.ldb, 0, kbeg, kend);
-    bsum += sa.store(lds);
+    bsum += sa.store(lds, gscale);
     sb.store(lds + DN_TILE);
     __syncthreads();
     for (int it = 0; it < steps; ++it) {
@@ -185,7 +216,7 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
         }
         if (more) {
             float* nxt = lds + ((it + 1) & 1) * 2 * DN_TILE;
-            bsum += sa.store(nxt);
+            bsum += sa.store(nxt, gscale);
             sb.store(nxt + DN_TILE);
         }
         __syncthreads();
@@ -202,20 +233,31 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
         float* C = a.C + (long)blockIdx.z * a.cslab;
         const long col = n0 + wn + c;
         float bv = 0.f;
-        if (EPI == DN_EPI_FWD && a.bias && col < a.N) bv = a.bias[col];
+        if (FWD && a.bias && col < a.N) bv = a.bias[col];
+        unsigned long long seed = 0;
+        unsigned layer_key = 0;
+        if (EPI == DN_EPI_FWD_DROP) {
+            seed = *a.seed;
+            layer_key = dn_drop_layer_key(seed, a.layer);
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const long row = m0 + wm + frag_row(r, s);
             if (row >= a.M || col >= a.N) continue;
             float v = acc[r];
-            if (EPI == DN_EPI_FWD) {
+            if (FWD) {
                 v += bv;
                 if (a.relu) v = v < 0.f ? 0.f : v;
+            }
+            if (EPI == DN_EPI_FWD_DROP) {
+                // this lane owns one cell of each of its 16 rows: one row key per row
+                const unsigned rk = dn_drop_row_key(layer_key, seed, a.row0 + row);
+                v = dn_drop_keep(rk, col, a.thresh) ? v * a.keep_scale : 0.f;
             }
             C[row * a.ldc + col] = v;
         }
     }
-    if (EPI == DN_EPI_SLAB) {
+    if (SLAB) {
         // column sums of this split's gz rows: thread (m = t & 63, wave q) summed plane q of every stage
         if (a.dbpart && blockIdx.y == 0) {             // uniform over the workgroup
             __syncthreads();
@@ -267,8 +309,118 @@ static inline int dn_splits(long rows) {
     return (int)(n < 1 ? 1 : (n > DN_MAX_SPLIT ? DN_MAX_SPLIT : n));
 }
 
+// The keep mask the DROP epilogue draws, written out: keep[row][col] (1 = kept).  Test hook, like attn_dropout_mask_kernel.
+__global__ __launch_bounds__(256) void dense_dropout_mask_kernel(long rows, int out, const unsigned long long* __restrict__ seed_p,
+                                                                 unsigned thresh, int layer, long row0, unsigned char* __restrict__ keep) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= rows * out) return;
+    const long row = e / out, col = e - row * out;
+    const unsigned long long seed = seed_p ? *seed_p : 0ull;           // NULL only with p_drop = 0: thresh = 0 keeps every cell
+    const unsigned rk = dn_drop_row_key(dn_drop_layer_key(seed, layer), seed, row0 + row);
+    keep[e] = dn_drop_keep(rk, col, thresh) ? 1 : 0;
+}
+
 #define DN_LAUNCH(AKC, BKC, MASK, EPI, grid, st, a) \
     hipLaunchKernelGGL((dense_mfma_kernel<AKC, BKC, MASK, EPI>), grid, dim3(DN_NW * 64), 0, st, a)
+
+// Dropout arguments of the _drop entry points, checked: on = p_drop > 0 (p_drop = 0 runs the plain instances).
+struct DnDrop {
+    bool on;
+    const unsigned long long* seed; unsigned thresh; float keep_scale; int layer; long row0;
+};
+static int dn_drop_rate(const char* who, float p_drop, DnDrop* d) {
+    *d = DnDrop{false, nullptr, 0u, 1.f, 0, 0};
+    XDFM_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop = %g outside [0, 1)", who, p_drop);
+    d->on = p_drop > 0.f;
+    if (d->on) { d->thresh = xdfm_drop_thresh(p_drop); d->keep_scale = xdfm_drop_keep_scale(p_drop); }
+    return XDFM_OK;
+}
+static int dn_drop_mask_args(const char* who, float p_drop, const unsigned long long* seed, int layer, long row0, DnDrop* d) {
+    if (int rc = dn_drop_rate(who, p_drop, d)) return rc;
+    XDFM_REQUIRE(layer >= 0, "%s: layer = %d", who, layer);
+    XDFM_REQUIRE(row0 >= 0, "%s: row0 = %ld", who, row0);
+    XDFM_REQUIRE(!d->on || seed, "%s: p_drop = %g needs a device seed, seed is NULL", who, p_drop);
+    d->seed = seed; d->layer = layer; d->row0 = row0;
+    return XDFM_OK;
+}
+
+static int dn_fwd(const char* who, const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act,
+                  float* y, long ldy, const DnDrop& drop, void* stream) {
+    XDFM_REQUIRE(x && W && y, "%s: null pointer", who);
+    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
+    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
+    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
+                 who, rows, in, out);
+    XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
+    XDFM_REQUIRE(ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
+    XDFM_REQUIRE(act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU, "%s: act = %d (0 = none, 1 = relu)", who, act);
+    XDFM_REQUIRE(!drop.on || act == XDFM_ACT_RELU, "%s: p_drop > 0 needs act = 1 (relu), act = %d: the backward reads the mask off y > 0",
+                 who, act);
+    DnArgs a{};
+    a.A = x; a.lda = ldx; a.B = W; a.ldb = in; a.C = y; a.ldc = ldy; a.bias = b; a.relu = act == XDFM_ACT_RELU;
+    a.M = rows; a.N = out; a.K = in; a.kper = round_up(in, DN_K);
+    a.seed = drop.seed; a.row0 = drop.row0; a.thresh = drop.thresh; a.layer = drop.layer; a.keep_scale = drop.keep_scale;
+    const dim3 grid(ceil_div(rows, DN_T), ceil_div(out, DN_T), 1);
+    if (drop.on) DN_LAUNCH(true, true, false, DN_EPI_FWD_DROP, grid, (hipStream_t)stream, a);
+    else DN_LAUNCH(true, true, false, DN_EPI_FWD, grid, (hipStream_t)stream, a);
+    return xdfm_check_launch(who);
+}
+
+static int dn_bwd_x(const char* who, const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in,
+                    float* dx, long lddx, const DnDrop& drop, void* stream) {
+    XDFM_REQUIRE(g && W && dx, "%s: null pointer", who);
+    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
+    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
+    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
+                 who, rows, in, out);
+    XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
+    XDFM_REQUIRE(!y || ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
+    XDFM_REQUIRE(lddx >= in, "%s: lddx = %ld < in = %d", who, lddx, in);
+    XDFM_REQUIRE(!drop.on || y, "%s: p_drop > 0 needs y (the layer's dropped output is the mask), y is NULL", who);
+    DnArgs a{};
+    a.A = g; a.Ay = y; a.lda = ldg; a.lday = ldy; a.B = W; a.ldb = in; a.C = dx; a.ldc = lddx;
+    a.M = rows; a.N = in; a.K = out; a.kper = round_up(out, DN_K);
+    a.keep_scale = drop.keep_scale;
+    const dim3 grid(ceil_div(rows, DN_T), ceil_div(in, DN_T), 1);
+    if (drop.on) DN_LAUNCH(true, false, true, DN_EPI_PLAIN_SCALED, grid, (hipStream_t)stream, a);
+    else if (y) DN_LAUNCH(true, false, true, DN_EPI_PLAIN, grid, (hipStream_t)stream, a);
+    else DN_LAUNCH(true, false, false, DN_EPI_PLAIN, grid, (hipStream_t)stream, a);
+    return xdfm_check_launch(who);
+}
+
+static int dn_bwd_w(const char* who, const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in,
+                    int out, float* ws, float* dW, float* db, const DnDrop& drop, void* stream) {
+    XDFM_REQUIRE(g && x && dW, "%s: null pointer", who);
+    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
+    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
+    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
+                 who, rows, in, out);
+    XDFM_REQUIRE(ws, "%s: workspace is NULL (xdfm_dense_bwd_w_ws_elems floats)", who);
+    XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
+    XDFM_REQUIRE(!y || ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
+    XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
+    XDFM_REQUIRE(!drop.on || y, "%s: p_drop > 0 needs y (the layer's dropped output is the mask), y is NULL", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int want = dn_splits(rows);
+    const long kper = round_up(ceil_div(rows, want), DN_K);
+    const int nsplit = ceil_div(rows, kper);             // <= want: what the workspace was sized for
+    const long mn = (long)out * in;
+    DnArgs a{};
+    a.A = g; a.Ay = y; a.lda = ldg; a.lday = ldy; a.B = x; a.ldb = ldx;
+    a.M = out; a.N = in; a.K = rows; a.kper = kper; a.ldc = in;
+    a.keep_scale = drop.keep_scale;
+    if (nsplit == 1) { a.C = dW; a.cslab = 0; a.dbpart = db; }
+    else { a.C = ws; a.cslab = mn; a.dbpart = db ? ws + (long)nsplit * mn : nullptr; }
+    const dim3 grid(ceil_div(out, DN_T), ceil_div(in, DN_T), nsplit);
+    if (drop.on) DN_LAUNCH(false, false, true, DN_EPI_SLAB_SCALED, grid, st, a);
+    else if (y) DN_LAUNCH(false, false, true, DN_EPI_SLAB, grid, st, a);
+    else DN_LAUNCH(false, false, false, DN_EPI_SLAB, grid, st, a);
+    if (nsplit > 1) {
+        const long total = mn + (db ? out : 0);
+        hipLaunchKernelGGL(dense_bwd_w_finish_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, ws, nsplit, mn, (long)out, dW, db);
+    }
+    return xdfm_check_launch(who);
+}
 
 extern "C" {
 
@@ -281,70 +433,59 @@ size_t xdfm_dense_bwd_w_ws_elems(long rows, int in, int out) {
 
 int xdfm_dense_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act, float* y,
                    long ldy, void* stream) {
-    XDFM_REQUIRE(x && W && y, "dense_fwd: null pointer");
-    XDFM_REQUIRE(rows > 0, "dense_fwd: rows = %ld", rows);
-    XDFM_REQUIRE(in > 0, "dense_fwd: in = %d", in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "dense_fwd: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 rows, in, out);
-    XDFM_REQUIRE(ldx >= in, "dense_fwd: ldx = %ld < in = %d", ldx, in);
-    XDFM_REQUIRE(ldy >= out, "dense_fwd: ldy = %ld < out = %d", ldy, out);
-    XDFM_REQUIRE(act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU, "dense_fwd: act = %d (0 = none, 1 = relu)", act);
-    DnArgs a{};
-    a.A = x; a.lda = ldx; a.B = W; a.ldb = in; a.C = y; a.ldc = ldy; a.bias = b; a.relu = act == XDFM_ACT_RELU;
-    a.M = rows; a.N = out; a.K = in; a.kper = round_up(in, DN_K);
-    const dim3 grid(ceil_div(rows, DN_T), ceil_div(out, DN_T), 1);
-    DN_LAUNCH(true, true, false, DN_EPI_FWD, grid, (hipStream_t)stream, a);
-    return xdfm_check_launch("dense_fwd");
+    DnDrop drop;
+    dn_drop_rate("dense_fwd", 0.f, &drop);
+    return dn_fwd("dense_fwd", x, rows, in, ldx, W, out, b, act, y, ldy, drop, stream);
 }
 
 int xdfm_dense_bwd_x(const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in, float* dx,
                      long lddx, void* stream) {
-    XDFM_REQUIRE(g && W && dx, "dense_bwd_x: null pointer");
-    XDFM_REQUIRE(rows > 0, "dense_bwd_x: rows = %ld", rows);
-    XDFM_REQUIRE(in > 0, "dense_bwd_x: in = %d", in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "dense_bwd_x: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 rows, in, out);
-    XDFM_REQUIRE(ldg >= out, "dense_bwd_x: ldg = %ld < out = %d", ldg, out);
-    XDFM_REQUIRE(!y || ldy >= out, "dense_bwd_x: ldy = %ld < out = %d", ldy, out);
-    XDFM_REQUIRE(lddx >= in, "dense_bwd_x: lddx = %ld < in = %d", lddx, in);
-    DnArgs a{};
-    a.A = g; a.Ay = y; a.lda = ldg; a.lday = ldy; a.B = W; a.ldb = in; a.C = dx; a.ldc = lddx;
-    a.M = rows; a.N = in; a.K = out; a.kper = round_up(out, DN_K);
-    const dim3 grid(ceil_div(rows, DN_T), ceil_div(in, DN_T), 1);
-    if (y) DN_LAUNCH(true, false, true, DN_EPI_PLAIN, grid, (hipStream_t)stream, a);
-    else DN_LAUNCH(true, false, false, DN_EPI_PLAIN, grid, (hipStream_t)stream, a);
-    return xdfm_check_launch("dense_bwd_x");
+    DnDrop drop;
+    dn_drop_rate("dense_bwd_x", 0.f, &drop);
+    return dn_bwd_x("dense_bwd_x", g, ldg, y, ldy, rows, out, W, in, dx, lddx, drop, stream);
 }
 
 int xdfm_dense_bwd_w(const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in, int out,
                      float* ws, float* dW, float* db, void* stream) {
-    XDFM_REQUIRE(g && x && dW, "dense_bwd_w: null pointer");
-    XDFM_REQUIRE(rows > 0, "dense_bwd_w: rows = %ld", rows);
-    XDFM_REQUIRE(in > 0, "dense_bwd_w: in = %d", in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "dense_bwd_w: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 rows, in, out);
-    XDFM_REQUIRE(ws, "dense_bwd_w: workspace is NULL (xdfm_dense_bwd_w_ws_elems floats)");
-    XDFM_REQUIRE(ldg >= out, "dense_bwd_w: ldg = %ld < out = %d", ldg, out);
-    XDFM_REQUIRE(!y || ldy >= out, "dense_bwd_w: ldy = %ld < out = %d", ldy, out);
-    XDFM_REQUIRE(ldx >= in, "dense_bwd_w: ldx = %ld < in = %d", ldx, in);
-    hipStream_t st = (hipStream_t)stream;
-    const int want = dn_splits(rows);
-    const long kper = round_up(ceil_div(rows, want), DN_K);
-    const int nsplit = ceil_div(rows, kper);             // <= want: what the workspace was sized for
-    const long mn = (long)out * in;
-    DnArgs a{};
-    a.A = g; a.Ay = y; a.lda = ldg; a.lday = ldy; a.B = x; a.ldb = ldx;
-    a.M = out; a.N = in; a.K = rows; a.kper = kper; a.ldc = in;
-    if (nsplit == 1) { a.C = dW; a.cslab = 0; a.dbpart = db; }
-    else { a.C = ws; a.cslab = mn; a.dbpart = db ? ws + (long)nsplit * mn : nullptr; }
-    const dim3 grid(ceil_div(out, DN_T), ceil_div(in, DN_T), nsplit);
-    if (y) DN_LAUNCH(false, false, true, DN_EPI_SLAB, grid, st, a);
-    else DN_LAUNCH(false, false, false, DN_EPI_SLAB, grid, st, a);
-    if (nsplit > 1) {
-        const long total = mn + (db ? out : 0);
-        hipLaunchKernelGGL(dense_bwd_w_finish_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, ws, nsplit, mn, (long)out, dW, db);
-    }
-    return xdfm_check_launch("dense_bwd_w");
+    DnDrop drop;
+    dn_drop_rate("dense_bwd_w", 0.f, &drop);
+    return dn_bwd_w("dense_bwd_w", g, ldg, y, ldy, x, ldx, rows, in, out, ws, dW, db, drop, stream);
+}
+
+int xdfm_dense_fwd_drop(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act, float* y,
+                        long ldy, float p_drop, const unsigned long long* seed, int layer, long row0, void* stream) {
+    DnDrop drop;
+    if (int rc = dn_drop_mask_args("dense_fwd_drop", p_drop, seed, layer, row0, &drop)) return rc;
+    return dn_fwd("dense_fwd_drop", x, rows, in, ldx, W, out, b, act, y, ldy, drop, stream);
+}
+
+int xdfm_dense_bwd_x_drop(const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in, float* dx,
+                          long lddx, float p_drop, void* stream) {
+    DnDrop drop;
+    if (int rc = dn_drop_rate("dense_bwd_x_drop", p_drop, &drop)) return rc;
+    return dn_bwd_x("dense_bwd_x_drop", g, ldg, y, ldy, rows, out, W, in, dx, lddx, drop, stream);
+}
+
+int xdfm_dense_bwd_w_drop(const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in, int out,
+                          float* ws, float* dW, float* db, float p_drop, void* stream) {
+    DnDrop drop;
+    if (int rc = dn_drop_rate("dense_bwd_w_drop", p_drop, &drop)) return rc;
+    return dn_bwd_w("dense_bwd_w_drop", g, ldg, y, ldy, x, ldx, rows, in, out, ws, dW, db, drop, stream);
+}
+
+int xdfm_dense_dropout_mask(long rows, int out, float p_drop, const unsigned long long* seed, int layer, long row0,
+                            unsigned char* keep, void* stream) {
+    XDFM_REQUIRE(keep, "dense_dropout_mask: null pointer");
+    XDFM_REQUIRE(rows > 0 && rows < (1L << 31), "dense_dropout_mask: rows = %ld", rows);
+    XDFM_REQUIRE(out > 0 && out <= DN_MAX_DIM, "dense_dropout_mask: out = %d", out);
+    DnDrop drop;
+    if (int rc = dn_drop_mask_args("dense_dropout_mask", p_drop, seed, layer, row0, &drop)) return rc;
+    const long blocks = (rows * out + 255) / 256;
+    XDFM_REQUIRE(blocks <= 0x7fffffffL, "dense_dropout_mask: rows = %ld x out = %d cells are more than one launch covers", rows, out);
+    hipLaunchKernelGGL(dense_dropout_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rows, out, drop.seed,
+                       drop.thresh, layer, row0, keep);
+    return xdfm_check_launch("dense_dropout_mask");
 }
 
 }  // extern "C"
+

@@ -85,7 +85,19 @@ __device__ __forceinline__ float xdfm_act_bwd(int act, float a, float g) {
     if (act == XDFM_ACT_SIGMOID) return g * xdfm_sigmoid_slope(a);
     return g;
 }
+// The 32-bit finaliser of the hashed keep masks (attention dropout in attn.hip, DNN-tower dropout in dnn.hip): a
+// counter-based hash of (seed, position), nothing stored.
+__device__ __forceinline__ unsigned drop_mix(unsigned x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
 #endif
+// keep iff hash >= thresh, thresh = min((unsigned)(p * 2^32), 2^32 - 1); kept cells are scaled by the fp32 1 / (1 - p)
+static inline unsigned xdfm_drop_thresh(float p_drop) {
+    const double t = (double)p_drop * 4294967296.0;
+    return t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+}
+static inline float xdfm_drop_keep_scale(float p_drop) { return 1.0f / (1.0f - p_drop); }
 static inline bool xdfm_act_known(int act) { return act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU || act == XDFM_ACT_SIGMOID; }
 
 #define XDFM_REQUIRE(cond, ...) \

@@ -127,6 +127,10 @@ SIGNATURES = {
     "xdfm_dense_fwd": (c_int, [P, c_long, c_int, c_long, P, c_int, P, c_int, P, c_long, P]),
     "xdfm_dense_bwd_x": (c_int, [P, c_long, P, c_long, c_long, c_int, P, c_int, P, c_long, P]),
     "xdfm_dense_bwd_w": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, c_int, P, P, P, P]),
+    "xdfm_dense_fwd_drop": (c_int, [P, c_long, c_int, c_long, P, c_int, P, c_int, P, c_long, c_float, P, c_int, c_long, P]),
+    "xdfm_dense_bwd_x_drop": (c_int, [P, c_long, P, c_long, c_long, c_int, P, c_int, P, c_long, c_float, P]),
+    "xdfm_dense_bwd_w_drop": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, c_int, P, P, P, c_float, P]),
+    "xdfm_dense_dropout_mask": (c_int, [c_long, c_int, c_float, P, c_int, c_long, P, P]),
     "xdfm_l2_reg_fwd": (c_int, [P, P, P, c_int, P, P, P]),
     "xdfm_l2_reg_bwd": (c_int, [P, P, P, c_int, P, P, P, c_int, P]),
 }

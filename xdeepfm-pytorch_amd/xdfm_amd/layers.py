@@ -207,8 +207,10 @@ class DNN(nn.Module):
     six library GEMMs plus the mask and bias-gradient passes, were 7.5 % of the flagship step's time: layers whose
     width is a multiple of 32 run their backward in the fp32-MFMA kernels of csrc/dnn.hip (ops.Dense / ops.DenseReLU,
     `XDFM_DNN_NATIVE`).  Other widths keep hipBLASLt through torch, with the bias gradient by the library's
-    memset-free column sum; either way the step can be captured in a HIP graph.  Dice / PReLU belong to other models of
-    the zoo."""
+    memset-free column sum; either way the step can be captured in a HIP graph.  In training with 0 < dropout_rate < 1 those
+    ReLU layers run their dropout inside the same kernels (ops.DenseReLUDropout, `XDFM_DNN_DROPOUT_NATIVE`): a hashed keep
+    mask, one seed per call in `last_drop_seed`; nn.Dropout stays for every other configuration.  Dice / PReLU belong to
+    other models of the zoo."""
 
     def __init__(self, inputs_dim, hidden_units, activation='relu', l2_reg=0, dropout_rate=0, use_bn=False,
                  init_std=0.0001, dice_dim=3, seed=1024, device='cpu'):
@@ -229,9 +231,19 @@ class DNN(nn.Module):
                 nn.init.normal_(p, mean=0, std=init_std)
         self.to(device)
 
+    last_drop_seed = None        # the seed of the last tower call that ran the native dropout (read by the tests)
+
     def forward(self, x):
+        p = float(self.dropout.p)
+        seed = None              # one per tower call, shared by the layers through their index
         for i, lin in enumerate(self.linears):
             if self.activation == "relu" and not self.use_bn:
+                if self.training and ops.dense_dropout_native(x, lin.weight, lin.bias, p):
+                    # dropout in the dense kernels' epilogue and staging: no mask tensor, no extra launch
+                    if seed is None:
+                        seed = self.last_drop_seed = ops.draw_dropout_seed(x.device)
+                    x = ops.dense_relu_dropout(x, lin.weight, lin.bias, p, seed, i)
+                    continue
                 x = self.dropout(ops.dense_relu(x, lin.weight, lin.bias))
                 continue
             x = ops.dense(x, lin.weight, lin.bias)

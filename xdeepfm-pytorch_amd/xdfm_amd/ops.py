@@ -1033,6 +1033,81 @@ def dense(x, W, b):
     return torch.nn.functional.linear(x, W, b)
 
 
+# XDFM_DNN_DROPOUT_NATIVE (default 1): in training, with 0 < p < 1, a ReLU layer that `dense_native` accepts runs
+# DenseReLUDropout instead of dense_relu + nn.Dropout.  Read once, at import; a module attribute the tests and
+# tools/dnn_probe.py flip, like DNN_NATIVE (which has to be on as well).
+DNN_DROPOUT_NATIVE = _env_switch(os.environ, "XDFM_DNN_DROPOUT_NATIVE")
+
+
+def dense_dropout_native(x, W, b, p):
+    """Does dropout(relu(x W^T + b)) run in the dense kernels?  Both switches on, 0 < p < 1, a bias, and `dense_native`."""
+    return bool(DNN_DROPOUT_NATIVE and DNN_NATIVE and 0.0 < float(p) < 1.0 and b is not None and dense_native(x, W, b))
+
+
+def draw_dropout_seed(device):
+    """The device scalar a hashed keep mask is keyed with, drawn as AttnPool draws its own: from torch's generator
+    (torch.manual_seed repeats a run), on the device (a captured graph draws a new one at every replay)."""
+    return torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=device)
+
+
+class DenseReLUDropout(torch.autograd.Function):
+    """d = dropout(relu(x W^T + b)) in one launch (xdfm_dense_fwd_drop): keep ? relu(z) / (1 - p) : 0 with the keep bit a
+    hash of (seed, layer, row, column).  d > 0 holds exactly where the cell was kept and z > 0, so d is all the backward
+    needs: the two _drop kernels select on d > 0 and scale g by the same 1 / (1 - p) while they stage it.  Saved: x, W, d --
+    no mask, no second activation.  seed: int64 device tensor of one element; layer: the layer's index in its tower."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, p, seed, layer):
+        _need_cuda(x, "x")
+        lib = _lib.load()
+        rows, k = x.shape
+        out = W.shape[0]
+        p = float(p)
+        d = torch.empty(rows, out, dtype=torch.float32, device=x.device)
+        _lib.check(_run("dense_fwd_drop", 0.0, lambda: lib.xdfm_dense_fwd_drop(
+            _ptr(x), rows, k, _ld(x), _ptr(W), out, _ptr(b), ACT_CODES["relu"], _ptr(d), out, p, _ptr(seed), int(layer), 0,
+            _stream())), "dense_fwd_drop")
+        ctx.p = p
+        ctx.save_for_backward(x, W, d)
+        return d
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W, d = ctx.saved_tensors
+        lib = _lib.load()
+        rows, k = x.shape
+        out = W.shape[0]
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
+        if not _rows_ok(g):
+            g = g.contiguous()
+        dx = dW = db = None
+        if need_dx:
+            dx = torch.empty(rows, k, dtype=torch.float32, device=g.device)
+            _lib.check(_run("dense_bwd_x_drop", 0.0, lambda: lib.xdfm_dense_bwd_x_drop(
+                _ptr(g), _ld(g), _ptr(d), _ld(d), rows, out, _ptr(W), k, _ptr(dx), k, ctx.p, _stream())), "dense_bwd_x_drop")
+        if need_dw or need_db:
+            ws = torch.empty(lib.xdfm_dense_bwd_w_ws_elems(rows, k, out), dtype=torch.float32, device=g.device)
+            dW = torch.empty(out, k, dtype=torch.float32, device=g.device)
+            db = torch.empty(out, dtype=torch.float32, device=g.device) if need_db else None
+            _lib.check(_run("dense_bwd_w_drop", 0.0, lambda: lib.xdfm_dense_bwd_w_drop(
+                _ptr(g), _ld(g), _ptr(d), _ld(d), _ptr(x), _ld(x), rows, k, out, _ptr(ws), _ptr(dW), _ptr(db), ctx.p, _stream())),
+                "dense_bwd_w_drop")
+        return dx, dW if need_dw else None, db, None, None, None
+
+
+def dense_relu_dropout(x, W, b, p, seed, layer):
+    """dropout(relu(x W^T + b)) through DenseReLUDropout; the caller has checked `dense_dropout_native` (anything else is an
+    error here, not a fall-back)."""
+    if not (0.0 < float(p) < 1.0):
+        raise ValueError("dense_relu_dropout: p = %r outside (0, 1)" % (p,))
+    if b is None or not dense_native(x, W, b):
+        raise ValueError("dense_relu_dropout: the native dense kernels do not take these operands (fp32 device tensors, "
+                         "contiguous rows, out a multiple of 32, XDFM_DNN_NATIVE on)")
+    if not (seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
+        raise ValueError("dense_relu_dropout: seed must be an int64 device tensor of one element")
+    return DenseReLUDropout.apply(x, W, b, float(p), seed, int(layer))
+
+
 # --------------------------------------------------------------------------------------------- #
 # output head                                                                                    #
 # --------------------------------------------------------------------------------------------- #

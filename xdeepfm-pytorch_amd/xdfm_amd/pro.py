@@ -115,12 +115,29 @@ class SFGDecoder(nn.Module):
         if self.use_label_aware_attention and labels is not None:
             decoder_input = decoder_input * self.label_attention.forward_native(decoder_input, labels)
         x = decoder_input
-        for mod in self.shared_layers:
+        mods = list(self.shared_layers)
+        seed = None                                                 # one per call, shared by the layers through their index
+        fused = False                                               # the previous Linear took its nn.Dropout along
+        for j, mod in enumerate(mods):
             if isinstance(mod, nn.Linear):
-                x = ops.dense_relu(x, mod.weight, mod.bias)         # every Linear of shared_layers is followed by nn.ReLU
+                # every Linear of shared_layers is followed by nn.ReLU and nn.Dropout: the triple is one launch where the
+                # dense kernels take it (layers.DNN.forward's conditions)
+                drop = mods[j + 2] if j + 2 < len(mods) and isinstance(mods[j + 2], nn.Dropout) else None
+                fused = drop is not None and drop.training and ops.dense_dropout_native(x, mod.weight, mod.bias, drop.p)
+                if fused:
+                    if seed is None:
+                        seed = self.last_drop_seed = ops.draw_dropout_seed(x.device)
+                    x = ops.dense_relu_dropout(x, mod.weight, mod.bias, drop.p, seed, j // 3)
+                else:
+                    x = ops.dense_relu(x, mod.weight, mod.bias)
+            elif isinstance(mod, nn.Dropout):
+                x = x if fused else mod(x)
+                fused = False
             elif not isinstance(mod, nn.ReLU):
-                x = mod(x)                                          # nn.Dropout
+                x = mod(x)
         return x
+
+    last_drop_seed = None        # the seed of the last hidden_native call that ran the native dropout (read by the tests)
 
     def forward(self, sparse_embeddings, dense_values, labels=None):
         """The reference's signature (lists of [B,1,D] / [B,1] tensors) -> (dict of [B, V_f] logits, [B, nd]).  This
