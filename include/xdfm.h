@@ -55,6 +55,8 @@
  * of the maxima are recomputed, not passed) -- additions again, the version stays 8.
  * xdfm_dense_fwd_drop, xdfm_dense_bwd_x_drop, xdfm_dense_bwd_w_drop, xdfm_dense_dropout_mask (dropout of the DNN tower inside
  * the dense kernels: a hashed keep mask, read back off the stored output) -- additions, the version stays 8.
+ * xdfm_bn_row_block, xdfm_bn_ws_elems, xdfm_bn_fwd_train, xdfm_bn_fwd_eval, xdfm_bn_bwd, xdfm_bn_bwd_eval (K12: batch norm of a
+ * dense layer's output fused with its activation, csrc/bn.hip) -- additions, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -499,6 +501,44 @@ int xdfm_dense_bwd_w_drop(const float* g, long ldg, const float* y, long ldy, co
                           float* ws, float* dW, float* db, float p_drop, void* stream);
 int xdfm_dense_dropout_mask(long rows, int out, float p_drop, const unsigned long long* seed, int layer, long row0,
                             unsigned char* keep, void* stream);
+
+/* ------------------------------------------------------------------ batch norm + activation of a dense layer (K12, csrc/bn.hip)
+ * replaces: nn.BatchNorm1d, the activation and their autograd in deepctr/layers/core.py:120-134 with use_bn=True.
+ * z [rows][ldz >= cols] fp32 is the dense layer's output; statistics are per column, over the rows.  gamma, beta, save_mean,
+ * save_rstd, running_mean, running_var, dgamma, dbeta: [cols].  y, g, dz: [rows][ld >= cols].  act: XDFM_ACT_*.
+ * xdfm_bn_fwd_train (two launches): every block of xdfm_bn_row_block() rows leaves the pair (mean, M2 = sum (z - mean)^2) of
+ * its rows per column in ws (xdfm_bn_ws_elems(rows, cols) floats' worth of memory, 8-byte aligned: the pairs are kept as
+ * doubles; nothing in it needs initialising); the second launch merges the pairs with Chan's formula in a fixed order -- never
+ * a raw sum of squares -- and writes
+ *     y = act(gamma * (z - mean) * rstd + beta),   rstd = 1 / sqrt(var + eps),  var = M2 / rows (biased),
+ *     save_mean = mean, save_rstd = rstd,
+ *     running_mean = (1 - momentum) * running_mean + momentum * mean,
+ *     running_var  = (1 - momentum) * running_var  + momentum * M2 / (rows - 1)      (unbiased, as nn.BatchNorm1d),
+ * both running vectors updated in place.  rows >= 2.
+ * xdfm_bn_fwd_eval (one launch): the same y with mean = running_mean, rstd = 1 / sqrt(running_var + eps).  rows >= 1.
+ * xdfm_bn_bwd (two launches): with gm = act'(y) * g (relu: y > 0 ? g : 0; sigmoid: g * y * (1 - y); linear: g; never stored)
+ * and xhat = (z - save_mean) * save_rstd, the per-block partial sums of gm and gm * xhat go to ws, then
+ *     dz = gamma * rstd * (gm - sum(gm) / rows - xhat * sum(gm * xhat) / rows),  dbeta = sum(gm),  dgamma = sum(gm * xhat).
+ * dz, dgamma and dbeta may each be NULL: only what is asked for is written, with the same bits.
+ * xdfm_bn_bwd_eval: the backward of xdfm_bn_fwd_eval, whose statistics are constants: mean / rstd [cols] are the caller's
+ * running_mean and 1 / sqrt(running_var + eps); dz = gamma * rstd * gm, dbeta and dgamma as above.  rows >= 1.
+ * No atomics, no zeroed cells, no memset, the same bits on every run; no entry point synchronises or allocates.
+ * XDFM_ERR_INVALID, before any device call: a NULL operand (ws included; or a ws off 8-byte alignment), rows < 1 (< 2 in
+ * training and its backward),
+ * cols < 1, a pitch below cols, an unknown act, eps <= 0, momentum outside [0, 1]. */
+int xdfm_bn_row_block(void);
+size_t xdfm_bn_ws_elems(long rows, int cols);                          /* 0 for rows < 1 or cols < 1 */
+int xdfm_bn_fwd_train(const float* z, long ldz, long rows, int cols, const float* gamma, const float* beta, float eps, float momentum,
+                      int act, float* y, long ldy, float* save_mean, float* save_rstd, float* running_mean, float* running_var,
+                      float* ws, void* stream);
+int xdfm_bn_fwd_eval(const float* z, long ldz, long rows, int cols, const float* gamma, const float* beta, float eps, int act, float* y,
+                     long ldy, const float* running_mean, const float* running_var, void* stream);
+int xdfm_bn_bwd(const float* g, long ldg, const float* y, long ldy, const float* z, long ldz, long rows, int cols, const float* gamma,
+                const float* save_mean, const float* save_rstd, int act, float* dz, long lddz, float* dgamma, float* dbeta, float* ws,
+                void* stream);
+int xdfm_bn_bwd_eval(const float* g, long ldg, const float* y, long ldy, const float* z, long ldz, long rows, int cols,
+                     const float* gamma, const float* mean, const float* rstd, int act, float* dz, long lddz, float* dgamma, float* dbeta,
+                     float* ws, void* stream);
 
 /* ------------------------------------------------------------------ output head: link + loss (K8)
  * z_b = lin_b + <u_b, wu> + <v_b, wv> + bias,  pred = LINK(z),  loss = sum_b LOSS(pred_b, y_b).

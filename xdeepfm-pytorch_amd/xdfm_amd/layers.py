@@ -10,6 +10,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import dist as xdist
 from . import ops
 
 
@@ -209,8 +210,10 @@ class DNN(nn.Module):
     `XDFM_DNN_NATIVE`).  Other widths keep hipBLASLt through torch, with the bias gradient by the library's
     memset-free column sum; either way the step can be captured in a HIP graph.  In training with 0 < dropout_rate < 1 those
     ReLU layers run their dropout inside the same kernels (ops.DenseReLUDropout, `XDFM_DNN_DROPOUT_NATIVE`): a hashed keep
-    mask, one seed per call in `last_drop_seed`; nn.Dropout stays for every other configuration.  Dice / PReLU belong to
-    other models of the zoo."""
+    mask, one seed per call in `last_drop_seed`; nn.Dropout stays for every other configuration.  With use_bn the batch norm
+    and the activation behind each dense layer run in the kernels of csrc/bn.hip (ops.bn_act, `XDFM_DNN_BN_NATIVE`; relu,
+    sigmoid and linear, any width); the nn.BatchNorm1d modules stay the holders of gamma, beta and the buffers.  Dice / PReLU
+    belong to other models of the zoo."""
 
     def __init__(self, inputs_dim, hidden_units, activation='relu', l2_reg=0, dropout_rate=0, use_bn=False,
                  init_std=0.0001, dice_dim=3, seed=1024, device='cpu'):
@@ -247,6 +250,12 @@ class DNN(nn.Module):
                 x = self.dropout(ops.dense_relu(x, lin.weight, lin.bias))
                 continue
             x = ops.dense(x, lin.weight, lin.bias)
+            if self.use_bn and xdist.current() is None and ops.bn_native(x, self.bn[i]):
+                # batch norm + activation in the kernels of csrc/bn.hip: one [rows, out] tensor written instead of three
+                # (DESIGN 4.3d).  Row-parallel training keeps the stock modules: per-shard statistics are a question of
+                # their own (SyncBN).
+                x = self.dropout(ops.bn_act(x, self.bn[i], self.activation, self.training))
+                continue
             if self.use_bn:
                 x = self.bn[i](x)
             if self.activation == "relu":

@@ -1108,6 +1108,102 @@ def dense_relu_dropout(x, W, b, p, seed, layer):
     return DenseReLUDropout.apply(x, W, b, float(p), seed, int(layer))
 
 
+# XDFM_DNN_BN_NATIVE (default 1): a dense layer followed by nn.BatchNorm1d (layers.DNN with use_bn=True) runs its batch norm
+# and its activation in the kernels of csrc/bn.hip instead of nn.BatchNorm1d + torch.relu / torch.sigmoid.  Read once, at
+# import; a module attribute the tests and tools/dnn_bn_probe.py flip, like DNN_NATIVE (of which it is independent: the
+# dense layer in front keeps whatever route `dense_native` gives it).
+DNN_BN_NATIVE = _env_switch(os.environ, "XDFM_DNN_BN_NATIVE")
+
+
+def bn_native(z, bn):
+    """Does act(bn(z)) run the native kernels?  fp32 device tensor z [rows][cols] with contiguous rows; an nn.BatchNorm1d
+    with affine parameters, track_running_stats and a float momentum (what layers.DNN builds), all fp32 on z's device; the
+    XDFM_DNN_BN_NATIVE switch on."""
+    if not (DNN_BN_NATIVE and isinstance(bn, torch.nn.BatchNorm1d) and z.is_cuda and z.dim() == 2 and z.dtype == torch.float32
+            and z.shape[0] >= 1 and z.shape[1] == bn.num_features and _rows_ok(z)):
+        return False
+    if not (bn.affine and bn.track_running_stats and isinstance(bn.momentum, float) and 0.0 <= bn.momentum <= 1.0 and bn.eps > 0):
+        return False
+    return all(t is not None and t.device == z.device and t.dtype == torch.float32 and t.is_contiguous()
+               for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+
+class BatchNormAct(torch.autograd.Function):
+    """y = act(batch_norm(z)) over the rows of z [rows][cols] (deepctr/layers/core.py:120-134 with use_bn): two launches in
+    training (per-block (mean, M2) pairs, then a Chan merge + apply, which also updates running_mean / running_var in
+    place), one in evaluation (running statistics).  Backward: two launches, gm = act'(y) * g formed while g is loaded.
+    Saved: z, y, gamma, mean, rstd -- no normalised copy, no mask, no second activation.  In evaluation the statistics
+    are constants and the backward (xdfm_bn_bwd_eval) has no mean terms."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, running_mean, running_var, eps, momentum, act, training):
+        _need_cuda(z, "z")
+        lib = _lib.load()
+        rows, cols = z.shape
+        dev = z.device
+        y = torch.empty(rows, cols, dtype=torch.float32, device=dev)
+        if training:
+            stats = torch.empty(2, cols, dtype=torch.float32, device=dev)
+            mean, rstd = stats[0], stats[1]
+            ws = torch.empty(lib.xdfm_bn_ws_elems(rows, cols), dtype=torch.float32, device=dev)
+            _lib.check(_run("bn_fwd_train", 0.0, lambda: lib.xdfm_bn_fwd_train(
+                _ptr(z), _ld(z), rows, cols, _ptr(gamma), _ptr(beta), float(eps), float(momentum), int(act), _ptr(y), cols, _ptr(mean),
+                _ptr(rstd), _ptr(running_mean), _ptr(running_var), _ptr(ws), _stream())), "bn_fwd_train")
+        else:
+            _lib.check(_run("bn_fwd_eval", 0.0, lambda: lib.xdfm_bn_fwd_eval(
+                _ptr(z), _ld(z), rows, cols, _ptr(gamma), _ptr(beta), float(eps), int(act), _ptr(y), cols, _ptr(running_mean),
+                _ptr(running_var), _stream())), "bn_fwd_eval")
+            mean, rstd = running_mean, None
+            if any(ctx.needs_input_grad[:3]):
+                mean, rstd = running_mean.clone(), torch.rsqrt(running_var + float(eps))
+        ctx.act, ctx.training = int(act), bool(training)
+        ctx.save_for_backward(z, y, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        z, y, gamma, mean, rstd = ctx.saved_tensors
+        lib = _lib.load()
+        rows, cols = z.shape
+        need_dz, need_dg, need_db = ctx.needs_input_grad[:3]
+        if not _rows_ok(g):
+            g = g.contiguous()
+        dev = g.device
+        dz = torch.empty(rows, cols, dtype=torch.float32, device=dev) if need_dz else None
+        dgamma = torch.empty(cols, dtype=torch.float32, device=dev) if need_dg else None
+        dbeta = torch.empty(cols, dtype=torch.float32, device=dev) if need_db else None
+        if need_dz or need_dg or need_db:
+            ws = torch.empty(lib.xdfm_bn_ws_elems(rows, cols), dtype=torch.float32, device=dev)
+            fn, name = (lib.xdfm_bn_bwd, "bn_bwd") if ctx.training else (lib.xdfm_bn_bwd_eval, "bn_bwd_eval")
+            _lib.check(_run(name, 0.0, lambda: fn(_ptr(g), _ld(g), _ptr(y), _ld(y), _ptr(z), _ld(z), rows, cols, _ptr(gamma), _ptr(mean),
+                                                  _ptr(rstd), ctx.act, _ptr(dz), cols, _ptr(dgamma), _ptr(dbeta), _ptr(ws), _stream())), name)
+        return dz, dgamma, dbeta, None, None, None, None, None, None
+
+
+def bn_act(z, bn, act, training):
+    """act(bn(z)) for an nn.BatchNorm1d `bn` that stays the holder of gamma, beta and the running statistics (state_dict keys
+    unchanged).  Where `bn_native` holds: BatchNormAct, with num_batches_tracked incremented on the device in training (a
+    captured step replays it).  Elsewhere: the stock sequence, bn(z) then torch.relu / torch.sigmoid."""
+    code = activation_code(act)
+    if bn_native(z, bn):
+        return _bn_act_native(z, bn, code, bool(training))
+    x = bn(z)
+    if code == ACT_CODES["relu"]:
+        return torch.relu(x)
+    if code == ACT_CODES["sigmoid"]:
+        return torch.sigmoid(x)
+    return x
+
+
+def _bn_act_native(z, bn, code, training):
+    """The native branch of bn_act (a function of its own so that tests and tools can count its calls)."""
+    if training:
+        if z.shape[0] < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (z.size(),))
+        bn.num_batches_tracked.add_(1)
+    return BatchNormAct.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), float(bn.momentum), code, training)
+
+
 # --------------------------------------------------------------------------------------------- #
 # output head                                                                                    #
 # --------------------------------------------------------------------------------------------- #
