@@ -57,6 +57,9 @@
  * the dense kernels: a hashed keep mask, read back off the stored output) -- additions, the version stays 8.
  * xdfm_bn_row_block, xdfm_bn_ws_elems, xdfm_bn_fwd_train, xdfm_bn_fwd_eval, xdfm_bn_bwd, xdfm_bn_bwd_eval (K12: batch norm of a
  * dense layer's output fused with its activation, csrc/bn.hip) -- additions, the version stays 8.
+ * xdfm_dense_prelu_fwd, xdfm_dense_prelu_bwd_x, xdfm_dense_prelu_bwd_w, xdfm_dense_prelu_bwd_w_ws_elems (the dense kernels with a
+ * PReLU of one scalar slope: dnn_activation='prelu') and xdfm_prelu_ws_elems, xdfm_prelu_fwd, xdfm_prelu_bwd (K13: the same
+ * PReLU elementwise, csrc/prelu.hip) -- additions, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -501,6 +504,46 @@ int xdfm_dense_bwd_w_drop(const float* g, long ldg, const float* y, long ldy, co
                           float* ws, float* dW, float* db, float p_drop, void* stream);
 int xdfm_dense_dropout_mask(long rows, int out, float p_drop, const unsigned long long* seed, int layer, long row0,
                             unsigned char* keep, void* stream);
+/* The same layer followed by nn.PReLU() (deepctr/layers/core.py:104-134 with activation='prelu'): one scalar slope per layer,
+ * torch's prelu.  With z = x W^T + b the pre-activation:
+ *     y = z > 0 ? z : alpha * z,     gz = z > 0 ? g : alpha * g (one fp32 rounding),     dalpha = sum over z <= 0 of g * z;
+ * a cell with z == 0 takes the alpha branch and adds 0 to dalpha.  alpha: a DEVICE scalar every kernel reads (the optimizer
+ * moves it, and a replayed graph sees the new value); any finite value -- 0, 1 and negative slopes included, so neither the sign
+ * nor the value of z can be read off y: the backward takes z, which the forward stores next to y.
+ * xdfm_dense_prelu_fwd (one launch): y [rows][ldy >= out] and z [rows][ldz >= out]; z = NULL (evaluation) stores y only,
+ * the same bits.  y == z is invalid.
+ * xdfm_dense_prelu_bwd_x: dx = gz W; gz is formed while g is staged and never stored.
+ * xdfm_dense_prelu_bwd_w: dW = gz^T x, db = column sums of gz (NULL: not wanted) with the splits, the slabs and the pairwise
+ * finish of xdfm_dense_bwd_w -- the same bits as that call given a materialised gz.  dalpha (one float, NULL: not wanted): the
+ * blocks that leave the bias partials also leave one partial per (64-wide tile of out, split), the products g * z and
+ * every sum in double; the finish launch adds them in a fixed order and rounds once to fp32 (it runs for a single split too).
+ * No atomics, no zeroed cells, the same bits on every run.  ws: xdfm_dense_prelu_bwd_w_ws_elems floats, 8-byte aligned (the
+ * partials of dalpha are doubles); nothing in it needs initialising.
+ * XDFM_ERR_INVALID, before any device call: what the plain entry points refuse, a NULL alpha or z (backward), y == z, ldz < out,
+ * a NULL or misaligned workspace. */
+size_t xdfm_dense_prelu_bwd_w_ws_elems(long rows, int in, int out);    /* 0 outside xdfm_dense_supported */
+int xdfm_dense_prelu_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, const float* alpha,
+                         float* y, long ldy, float* z, long ldz, void* stream);
+int xdfm_dense_prelu_bwd_x(const float* g, long ldg, const float* z, long ldz, const float* alpha, long rows, int out, const float* W,
+                           int in, float* dx, long lddx, void* stream);
+int xdfm_dense_prelu_bwd_w(const float* g, long ldg, const float* z, long ldz, const float* alpha, const float* x, long ldx, long rows,
+                           int in, int out, float* ws, float* dW, float* db, float* dalpha, void* stream);
+
+/* ------------------------------------------------------------------ elementwise PReLU, one scalar slope (K13, csrc/prelu.hip)
+ * replaces: aten::_prelu_kernel, _prelu_kernel_backward and the `sum` behind it (a memset inside a captured step) for the
+ * layers the fused calls above do not take: widths that are no multiple of 32, a batch norm in front, the library GEMM route.
+ * u, y, g, du: [rows][ld >= cols] fp32, any rows >= 1, cols >= 1 and any pitch; alpha: a device scalar, as above.
+ * xdfm_prelu_fwd (one launch): y = u > 0 ? u : alpha * u.
+ * xdfm_prelu_bwd (two launches at most): du = u > 0 ? g : alpha * g and dalpha = sum over u <= 0 of g * u, under the rules of
+ * xdfm_dense_prelu_bwd_w: one partial per block in ws (xdfm_prelu_ws_elems floats, 8-byte aligned: doubles), products and sums
+ * in double, a one-block second launch that adds them in a fixed order and rounds once.  du or dalpha may be NULL (not both):
+ * the other keeps its bits; without dalpha there is one launch and ws is not read.
+ * XDFM_ERR_INVALID, before any device call: a NULL operand, du and dalpha both NULL, rows < 1, cols < 1, a pitch below cols,
+ * with dalpha a NULL or misaligned workspace. */
+size_t xdfm_prelu_ws_elems(long rows, int cols);                       /* 0 for rows < 1 or cols < 1 */
+int xdfm_prelu_fwd(const float* u, long ldu, long rows, int cols, const float* alpha, float* y, long ldy, void* stream);
+int xdfm_prelu_bwd(const float* g, long ldg, const float* u, long ldu, long rows, int cols, const float* alpha, float* du, long lddu,
+                   float* dalpha, float* ws, void* stream);
 
 /* ------------------------------------------------------------------ batch norm + activation of a dense layer (K12, csrc/bn.hip)
  * replaces: nn.BatchNorm1d, the activation and their autograd in deepctr/layers/core.py:120-134 with use_bn=True.

@@ -33,6 +33,14 @@
 // column): d > 0 holds exactly where the cell was kept AND z > 0, so the layer's output is its own mask.  The two backward
 // kernels already select on y > 0 while they stage g; their SCALED instances multiply the selected value by the same s.
 // No mask is stored or regenerated, no launch is added either way.
+//
+// PReLU (the _prelu entry points; nn.PReLU() behind every layer, one scalar slope alpha per layer, read from device memory by
+// every kernel: the optimizer moves it and a replayed graph must see the new value).  The forward's epilogue stores
+// y = z > 0 ? z : alpha * z and, for the backward, the pre-activation z itself: alpha may be 0, 1 or negative, so neither
+// the sign nor the value of z can be read off y.  The two backward kernels form gz = z > 0 ? g : alpha * g while they stage
+// g (one rounding, never stored).  The slope's gradient, sum of g * z over the cells with z <= 0, is a by-product of the dW
+// kernel as the bias gradient is: the blocks that leave the bias partials also leave one partial per (tile of out, split),
+// products and sums in double, and the finish launch adds them in a fixed order and rounds once.
 #include "xdfm_internal.h"
 
 #define DN_T 64                    // tile edge (rows and columns of C per workgroup)
@@ -57,6 +65,10 @@ struct DnArgs {
     long row0;                                           //   row r of this call is row row0 + r of the mask
     unsigned thresh; int layer;                          //   keep iff hash >= thresh
     float keep_scale;                                    // 1 / (1 - p): DROP epilogue and the SCALED stagings of g
+    // PReLU (read by the PRELU instances only)
+    const float* alpha;                                  // device scalar: the layer's slope
+    float* Z; long ldz;                                  // forward: the pre-activation goes here too (NULL: y only)
+    double* dapart;                                      // dW: block (x, y = 0, z) leaves its sum of g * z [z <= 0] at dapart[z * gridDim.x + x]
 };
 
 // Keep bit of cell (layer, row, col): three rounds of drop_mix, the shape of the attention's key (attn.hip, drop_row_key).
@@ -79,7 +91,9 @@ __device__ __forceinline__ int dn_lds(int p, int m) { return p * DN_PLANE + (m <
 // otherwise (m contiguous, src[k * ld + m]):    lanes run along m, wave q stages plane q.
 // SCALED (with MASK): a live value is multiplied by gscale, one rounding -- the gradient through a dropout layer whose
 // kept cells are the y > 0 ones.
-template <bool KC, bool MASK, bool SCALED = false>
+// PRELU (with MASK; y then holds the pre-activation z and gscale the slope): a live value with z <= 0 is multiplied by the
+// slope, one rounding; PRELU == 2 also adds its g * z to *da, product and sum in double.
+template <bool KC, bool MASK, bool SCALED = false, int PRELU = 0>
 struct DnStage {
     float v[DN_E], y[DN_E];
     long off[DN_E], offy[DN_E];    // KC: row offsets of the (clamped) rows; otherwise [0]: the (clamped) column
@@ -141,13 +155,22 @@ struct DnStage {
         }
     }
     // returns the sum of the staged values in element order (the bias gradient's share of this thread)
-    __device__ __forceinline__ float store(float* __restrict__ tile, float gscale = 1.f) {
+    __device__ __forceinline__ float store(float* __restrict__ tile, float gscale = 1.f, double* da = nullptr) {
         const int t = threadIdx.x;
+        static_assert(!PRELU || (MASK && !SCALED), "the PReLU stagings read z where the ReLU ones read y");
 #pragma unroll
         for (int e = 0; e < DN_E; ++e) {
-            const bool live = (ok >> e & 1u) && (!MASK || y[e] > 0.f);
-            if (SCALED) v[e] = live ? v[e] * gscale : 0.f;
-            else v[e] = live ? v[e] : 0.f;
+            if constexpr (PRELU != 0) {
+                const bool in = ok >> e & 1u;
+                if constexpr (PRELU == 2) {
+                    if (in && y[e] <= 0.f) *da = fma((double)v[e], (double)y[e], *da);
+                }
+                v[e] = in ? (y[e] > 0.f ? v[e] : gscale * v[e]) : 0.f;
+            } else {
+                const bool live = (ok >> e & 1u) && (!MASK || y[e] > 0.f);
+                if (SCALED) v[e] = live ? v[e] * gscale : 0.f;
+                else v[e] = live ? v[e] : 0.f;
+            }
         }
         if (KC) {
             const int k = t & 31, p = (k >> 3) * 2 + (k & 1);
@@ -164,8 +187,10 @@ struct DnStage {
     }
 };
 
-// the last three are the dropout instances of the first three: the forward's DROP epilogue, dX and dW with g scaled
-enum { DN_EPI_FWD = 0, DN_EPI_PLAIN = 1, DN_EPI_SLAB = 2, DN_EPI_FWD_DROP = 3, DN_EPI_PLAIN_SCALED = 4, DN_EPI_SLAB_SCALED = 5 };
+// 3 .. 5 are the dropout instances of the first three: the forward's DROP epilogue, dX and dW with g scaled; 6 .. 8 the PReLU
+// ones: the forward's epilogue that stores y and z, dX and dW with gz formed from z and the slope (dW: the slope's gradient too)
+enum { DN_EPI_FWD = 0, DN_EPI_PLAIN = 1, DN_EPI_SLAB = 2, DN_EPI_FWD_DROP = 3, DN_EPI_PLAIN_SCALED = 4, DN_EPI_SLAB_SCALED = 5,
+       DN_EPI_FWD_PRELU = 6, DN_EPI_PLAIN_PRELU = 7, DN_EPI_SLAB_PRELU = 8 };
 
 template <bool AKC, bool BKC, bool MASK, int EPI>
 __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
@@ -178,12 +203,16 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
     const long kend = kbeg + a.kper < a.K ? kbeg + a.kper : a.K;
     const int steps = (int)((kend - kbeg + DN_K - 1) / DN_K);
 
-    constexpr bool FWD = EPI == DN_EPI_FWD || EPI == DN_EPI_FWD_DROP;
-    constexpr bool SLAB = EPI == DN_EPI_SLAB || EPI == DN_EPI_SLAB_SCALED;
+    constexpr bool FWD = EPI == DN_EPI_FWD || EPI == DN_EPI_FWD_DROP || EPI == DN_EPI_FWD_PRELU;
+    constexpr bool SLAB = EPI == DN_EPI_SLAB || EPI == DN_EPI_SLAB_SCALED || EPI == DN_EPI_SLAB_PRELU;
     constexpr bool SCALED = EPI == DN_EPI_PLAIN_SCALED || EPI == DN_EPI_SLAB_SCALED;
+    constexpr int PRELU = EPI == DN_EPI_SLAB_PRELU ? 2 : (EPI == DN_EPI_PLAIN_PRELU ? 1 : 0);      // of the staging of g
     static_assert(!SCALED || MASK, "g is scaled where the mask is open");
-    const float gscale = SCALED ? a.keep_scale : 1.f;
-    DnStage<AKC, MASK, SCALED> sa;
+    float gscale = 1.f;
+    if constexpr (SCALED) gscale = a.keep_scale;
+    if constexpr (PRELU != 0 || EPI == DN_EPI_FWD_PRELU) gscale = *a.alpha;
+    double da = 0.0;                                   // PRELU == 2: this thread's share of the slope's gradient
+    DnStage<AKC, MASK, SCALED, PRELU> sa;
     DnStage<BKC, false> sb;
     sa.init(a.lda, a.lday, m0, a.M);
     sb.init(a.ldb, 0, n0, a.N);
@@ -194,7 +223,7 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
 
     sa.load(a.A, a.Ay, a.lda, a.lday, kbeg, kend);
     sb.load(a.B, nullptr, a.ldb, 0, kbeg, kend);
-    bsum += sa.store(lds, gscale);
+    bsum += sa.store(lds, gscale, &da);
     sb.store(lds + DN_TILE);
     __syncthreads();
     for (int it = 0; it < steps; ++it) {
@@ -216,7 +245,7 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
         }
         if (more) {
             float* nxt = lds + ((it + 1) & 1) * 2 * DN_TILE;
-            bsum += sa.store(nxt, gscale);
+            bsum += sa.store(nxt, gscale, &da);
             sb.store(nxt + DN_TILE);
         }
         __syncthreads();
@@ -249,6 +278,10 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
                 v += bv;
                 if (a.relu) v = v < 0.f ? 0.f : v;
             }
+            if constexpr (EPI == DN_EPI_FWD_PRELU) {
+                if (a.Z) a.Z[row * a.ldz + col] = v;
+                v = v > 0.f ? v : gscale * v;
+            }
             if (EPI == DN_EPI_FWD_DROP) {
                 // this lane owns one cell of each of its 16 rows: one row key per row
                 const unsigned rk = dn_drop_row_key(layer_key, seed, a.row0 + row);
@@ -267,15 +300,22 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
                 a.dbpart[(long)blockIdx.z * a.M + m0 + t] = ((lds[t] + lds[64 + t]) + (lds[128 + t] + lds[192 + t])) +
                                                             ((lds[256 + t] + lds[320 + t]) + (lds[384 + t] + lds[448 + t]));
         }
+        if constexpr (EPI == DN_EPI_SLAB_PRELU) {
+            // the same blocks saw every cell of g and z of their (tile of out, split) exactly once
+            if (a.dapart && blockIdx.y == 0) {         // uniform over the workgroup
+                __syncthreads();
+                const double s = xdfm_block_sum_f64(da, (double*)lds);
+                if (t == 0) a.dapart[(long)blockIdx.z * gridDim.x + blockIdx.x] = s;
+            }
+        }
     }
 }
 
 // dW[e] = sum over the splits of slab[z][e], db[c] likewise, over a fixed pairwise tree: eight splits at a time, then the
 // (at most DN_MAX_SPLIT / 8) sums of eight.  A running sum in split order rounds once per split at the magnitude of the total:
 // at 29 splits the bias gradient's error was 3 ulp, three times that of a pairwise column sum of the same values.
-__global__ __launch_bounds__(256) void dense_bwd_w_finish_kernel(const float* __restrict__ ws, int nsplit, long mn, long m,
-                                                                 float* __restrict__ dW, float* __restrict__ db) {
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+__device__ __forceinline__ void dn_finish_elem(long e, const float* __restrict__ ws, int nsplit, long mn, long m,
+                                               float* __restrict__ dW, float* __restrict__ db) {
     const long total = mn + (db ? m : 0);
     if (e >= total) return;
     const float* p = e < mn ? ws + e : ws + (long)nsplit * mn + (e - mn);
@@ -298,6 +338,27 @@ __global__ __launch_bounds__(256) void dense_bwd_w_finish_kernel(const float* __
     const float sum = (q[0] + q[1]) + (q[2] + q[3]);
     if (e < mn) dW[e] = sum;
     else db[e - mn] = sum;
+}
+__global__ __launch_bounds__(256) void dense_bwd_w_finish_kernel(const float* __restrict__ ws, int nsplit, long mn, long m,
+                                                                 float* __restrict__ dW, float* __restrict__ db) {
+    dn_finish_elem((long)blockIdx.x * 256 + threadIdx.x, ws, nsplit, mn, m, dW, db);
+}
+// The PReLU layer's finish: blocks [0, eblocks) are the finish above (none with a single split, whose dW and db are final);
+// one more block adds the npart partials of the slope's gradient -- thread t those of index t, t + 256, ... in order, then
+// xdfm_block_sum_f64 -- in double and rounds once.
+__global__ __launch_bounds__(256) void dense_prelu_bwd_w_finish_kernel(const float* __restrict__ ws, int nsplit, long mn, long m,
+                                                                       float* __restrict__ dW, float* __restrict__ db, unsigned eblocks,
+                                                                       const double* __restrict__ dapart, int npart,
+                                                                       float* __restrict__ dalpha) {
+    if (blockIdx.x < eblocks) {                        // uniform over the workgroup
+        dn_finish_elem((long)blockIdx.x * 256 + threadIdx.x, ws, nsplit, mn, m, dW, db);
+        return;
+    }
+    __shared__ double sm[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < npart; i += 256) s += dapart[i];
+    s = xdfm_block_sum_f64(s, sm);
+    if (threadIdx.x == 0) *dalpha = (float)s;
 }
 
 static inline bool dn_supported(long rows, long in, long out) {
@@ -422,7 +483,112 @@ static int dn_bwd_w(const char* who, const float* g, long ldg, const float* y, l
     return xdfm_check_launch(who);
 }
 
+// ---- PReLU layer
+// floats of the dW workspace in front of the doubles (the slabs and bias partials of xdfm_dense_bwd_w, rounded up to an
+// even count: the base is 8-byte aligned)
+static inline size_t dn_prelu_ws_floats(int splits, long in, long out) {
+    const size_t n = (size_t)splits * ((size_t)out * in + out);
+    return n + (n & 1);
+}
+
+static int dn_prelu_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, const float* alpha,
+                        float* y, long ldy, float* z, long ldz, void* stream) {
+    const char* who = "dense_prelu_fwd";
+    XDFM_REQUIRE(x && W && y && alpha, "%s: null pointer", who);
+    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
+    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
+    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
+                 who, rows, in, out);
+    XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
+    XDFM_REQUIRE(ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
+    XDFM_REQUIRE(!z || ldz >= out, "%s: ldz = %ld < out = %d", who, ldz, out);
+    XDFM_REQUIRE(y != z, "%s: y == z (the backward needs the pre-activation apart from the output)", who);
+    DnArgs a{};
+    a.A = x; a.lda = ldx; a.B = W; a.ldb = in; a.C = y; a.ldc = ldy; a.bias = b; a.relu = 0;
+    a.M = rows; a.N = out; a.K = in; a.kper = round_up(in, DN_K);
+    a.alpha = alpha; a.Z = z; a.ldz = ldz;
+    const dim3 grid(ceil_div(rows, DN_T), ceil_div(out, DN_T), 1);
+    DN_LAUNCH(true, true, false, DN_EPI_FWD_PRELU, grid, (hipStream_t)stream, a);
+    return xdfm_check_launch(who);
+}
+
+static int dn_prelu_bwd_x(const float* g, long ldg, const float* z, long ldz, const float* alpha, long rows, int out, const float* W,
+                          int in, float* dx, long lddx, void* stream) {
+    const char* who = "dense_prelu_bwd_x";
+    XDFM_REQUIRE(g && z && alpha && W && dx, "%s: null pointer", who);
+    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
+    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
+    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
+                 who, rows, in, out);
+    XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
+    XDFM_REQUIRE(ldz >= out, "%s: ldz = %ld < out = %d", who, ldz, out);
+    XDFM_REQUIRE(lddx >= in, "%s: lddx = %ld < in = %d", who, lddx, in);
+    DnArgs a{};
+    a.A = g; a.Ay = z; a.lda = ldg; a.lday = ldz; a.B = W; a.ldb = in; a.C = dx; a.ldc = lddx;
+    a.M = rows; a.N = in; a.K = out; a.kper = round_up(out, DN_K);
+    a.alpha = alpha;
+    const dim3 grid(ceil_div(rows, DN_T), ceil_div(in, DN_T), 1);
+    DN_LAUNCH(true, false, true, DN_EPI_PLAIN_PRELU, grid, (hipStream_t)stream, a);
+    return xdfm_check_launch(who);
+}
+
+static int dn_prelu_bwd_w(const float* g, long ldg, const float* z, long ldz, const float* alpha, const float* x, long ldx, long rows,
+                          int in, int out, float* ws, float* dW, float* db, float* dalpha, void* stream) {
+    const char* who = "dense_prelu_bwd_w";
+    XDFM_REQUIRE(g && z && alpha && x && dW, "%s: null pointer", who);
+    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
+    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
+    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
+                 who, rows, in, out);
+    XDFM_REQUIRE(ws, "%s: workspace is NULL (xdfm_dense_prelu_bwd_w_ws_elems floats)", who);
+    XDFM_REQUIRE(((size_t)ws & 7) == 0, "%s: workspace not 8-byte aligned", who);
+    XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
+    XDFM_REQUIRE(ldz >= out, "%s: ldz = %ld < out = %d", who, ldz, out);
+    XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
+    hipStream_t st = (hipStream_t)stream;
+    const int want = dn_splits(rows);
+    const long kper = round_up(ceil_div(rows, want), DN_K);
+    const int nsplit = ceil_div(rows, kper);             // <= want: what the workspace was sized for
+    const long mn = (long)out * in;
+    const int mtiles = ceil_div(out, DN_T);
+    double* dapart = dalpha ? (double*)(ws + dn_prelu_ws_floats(nsplit, in, out)) : nullptr;
+    DnArgs a{};
+    a.A = g; a.Ay = z; a.lda = ldg; a.lday = ldz; a.B = x; a.ldb = ldx;
+    a.M = out; a.N = in; a.K = rows; a.kper = kper; a.ldc = in;
+    a.alpha = alpha; a.dapart = dapart;
+    if (nsplit == 1) { a.C = dW; a.cslab = 0; a.dbpart = db; }
+    else { a.C = ws; a.cslab = mn; a.dbpart = db ? ws + (long)nsplit * mn : nullptr; }
+    const dim3 grid(mtiles, ceil_div(in, DN_T), nsplit);
+    DN_LAUNCH(false, false, true, DN_EPI_SLAB_PRELU, grid, st, a);
+    const unsigned eblocks = nsplit > 1 ? (unsigned)ceil_div(mn + (db ? out : 0), 256) : 0u;
+    if (eblocks || dalpha)
+        hipLaunchKernelGGL(dense_prelu_bwd_w_finish_kernel, dim3(eblocks + (dalpha ? 1u : 0u)), dim3(256), 0, st, ws, nsplit, mn,
+                           (long)out, dW, db, eblocks, dapart, nsplit * mtiles, dalpha);
+    return xdfm_check_launch(who);
+}
+
 extern "C" {
+
+size_t xdfm_dense_prelu_bwd_w_ws_elems(long rows, int in, int out) {
+    if (!dn_supported(rows, in, out)) return 0;
+    const int splits = dn_splits(rows);
+    return dn_prelu_ws_floats(splits, in, out) + (size_t)2 * splits * ceil_div(out, DN_T);       // one double per (tile of out, split)
+}
+
+int xdfm_dense_prelu_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, const float* alpha,
+                         float* y, long ldy, float* z, long ldz, void* stream) {
+    return dn_prelu_fwd(x, rows, in, ldx, W, out, b, alpha, y, ldy, z, ldz, stream);
+}
+
+int xdfm_dense_prelu_bwd_x(const float* g, long ldg, const float* z, long ldz, const float* alpha, long rows, int out, const float* W,
+                           int in, float* dx, long lddx, void* stream) {
+    return dn_prelu_bwd_x(g, ldg, z, ldz, alpha, rows, out, W, in, dx, lddx, stream);
+}
+
+int xdfm_dense_prelu_bwd_w(const float* g, long ldg, const float* z, long ldz, const float* alpha, const float* x, long ldx, long rows,
+                           int in, int out, float* ws, float* dW, float* db, float* dalpha, void* stream) {
+    return dn_prelu_bwd_w(g, ldg, z, ldz, alpha, x, ldx, rows, in, out, ws, dW, db, dalpha, stream);
+}
 
 int xdfm_dense_supported(long rows, int in, int out) { return dn_supported(rows, in, out) ? 1 : 0; }
 

@@ -85,6 +85,18 @@ __device__ __forceinline__ float xdfm_act_bwd(int act, float a, float g) {
     if (act == XDFM_ACT_SIGMOID) return g * xdfm_sigmoid_slope(a);
     return g;
 }
+// Sum of one double per thread over the workgroup (whole waves, at most 16), the same bits in every thread and on every run:
+// a xor tree inside each wave, then the waves' sums in index order.  sm: one double of LDS per wave that nobody else is using
+// (a barrier lies between its last use and this call).
+__device__ __forceinline__ double xdfm_block_sum_f64(double v, double* sm) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double s = sm[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s += sm[w];
+    return s;
+}
 // The 32-bit finaliser of the hashed keep masks (attention dropout in attn.hip, DNN-tower dropout in dnn.hip): a
 // counter-based hash of (seed, position), nothing stored.
 __device__ __forceinline__ unsigned drop_mix(unsigned x) {

@@ -131,6 +131,13 @@ SIGNATURES = {
     "xdfm_dense_bwd_x_drop": (c_int, [P, c_long, P, c_long, c_long, c_int, P, c_int, P, c_long, c_float, P]),
     "xdfm_dense_bwd_w_drop": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, c_int, P, P, P, c_float, P]),
     "xdfm_dense_dropout_mask": (c_int, [c_long, c_int, c_float, P, c_int, c_long, P, P]),
+    "xdfm_dense_prelu_bwd_w_ws_elems": (c_size_t, [c_long, c_int, c_int]),
+    "xdfm_dense_prelu_fwd": (c_int, [P, c_long, c_int, c_long, P, c_int, P, P, P, c_long, P, c_long, P]),
+    "xdfm_dense_prelu_bwd_x": (c_int, [P, c_long, P, c_long, P, c_long, c_int, P, c_int, P, c_long, P]),
+    "xdfm_dense_prelu_bwd_w": (c_int, [P, c_long, P, c_long, P, P, c_long, c_long, c_int, c_int, P, P, P, P, P]),
+    "xdfm_prelu_ws_elems": (c_size_t, [c_long, c_int]),
+    "xdfm_prelu_fwd": (c_int, [P, c_long, c_long, c_int, P, P, c_long, P]),
+    "xdfm_prelu_bwd": (c_int, [P, c_long, P, c_long, c_long, c_int, P, P, c_long, P, P, P]),
     "xdfm_bn_row_block": (c_int, []),
     "xdfm_bn_ws_elems": (c_size_t, [c_long, c_int]),
     "xdfm_bn_fwd_train": (c_int, [P, c_long, c_long, c_int, P, P, c_float, c_float, c_int, P, c_long, P, P, P, P, P, P]),

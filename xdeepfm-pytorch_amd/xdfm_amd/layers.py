@@ -204,7 +204,7 @@ class CINAttentionV2(_CINBase):
 
 
 class DNN(nn.Module):
-    """ReLU / linear MLP (deepctr/layers/core.py:67-134).  Its GEMMs are far below 2 % of the step's FLOPs but, run as
+    """ReLU / linear / sigmoid / PReLU MLP (deepctr/layers/core.py:67-134).  Its GEMMs are far below 2 % of the step's FLOPs but, run as
     six library GEMMs plus the mask and bias-gradient passes, were 7.5 % of the flagship step's time: layers whose
     width is a multiple of 32 run their backward in the fp32-MFMA kernels of csrc/dnn.hip (ops.Dense / ops.DenseReLU,
     `XDFM_DNN_NATIVE`).  Other widths keep hipBLASLt through torch, with the bias gradient by the library's
@@ -212,15 +212,23 @@ class DNN(nn.Module):
     ReLU layers run their dropout inside the same kernels (ops.DenseReLUDropout, `XDFM_DNN_DROPOUT_NATIVE`): a hashed keep
     mask, one seed per call in `last_drop_seed`; nn.Dropout stays for every other configuration.  With use_bn the batch norm
     and the activation behind each dense layer run in the kernels of csrc/bn.hip (ops.bn_act, `XDFM_DNN_BN_NATIVE`; relu,
-    sigmoid and linear, any width); the nn.BatchNorm1d modules stay the holders of gamma, beta and the buffers.  Dice / PReLU
-    belong to other models of the zoo."""
+    sigmoid and linear, any width); the nn.BatchNorm1d modules stay the holders of gamma, beta and the buffers.
+    activation='prelu' is the reference's: `activation_layers`, a ModuleList of nn.PReLU() (one slope per layer, 0.25, in the
+    l2_reg_dnn group like the reference's), holds the slopes; without batch norm a layer runs the fused dense + PReLU kernels
+    (ops.dense_prelu, `XDFM_DNN_PRELU_NATIVE`), otherwise -- other widths, behind batch norm, the switch off -- the
+    elementwise kernels of csrc/prelu.hip (ops.prelu) behind `ops.dense` / the batch norm; dropout with prelu stays nn.Dropout.
+    'dice' stays refused: the reference's own tower fails on it (Dice(hidden, dice_dim=3) asserts a 3-D input and gets the
+    tower's 2-D one)."""
 
     def __init__(self, inputs_dim, hidden_units, activation='relu', l2_reg=0, dropout_rate=0, use_bn=False,
                  init_std=0.0001, dice_dim=3, seed=1024, device='cpu'):
         super().__init__()
         if len(hidden_units) == 0:
             raise ValueError("hidden_units is empty!!")
-        if not isinstance(activation, str) or activation.lower() not in ("relu", "linear", "sigmoid"):
+        if isinstance(activation, str) and activation.lower() == "dice":
+            raise NotImplementedError("DNN activation 'dice' is refused: the reference's own tower fails on it (it builds "
+                                      "Dice(hidden, dice_dim=3), whose forward asserts a 3-D input and gets the tower's 2-D one)")
+        if not isinstance(activation, str) or activation.lower() not in ("relu", "linear", "sigmoid", "prelu"):
             raise NotImplementedError("DNN activation %r is outside the xDeepFM path" % (activation,))
         self.activation = activation.lower()
         self.dropout_rate, self.seed, self.l2_reg, self.use_bn = dropout_rate, seed, l2_reg, use_bn
@@ -229,6 +237,9 @@ class DNN(nn.Module):
         self.linears = nn.ModuleList([nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1)])
         if use_bn:
             self.bn = nn.ModuleList([nn.BatchNorm1d(dims[i + 1]) for i in range(len(dims) - 1)])
+        if self.activation == "prelu":
+            # the reference's holders and state_dict keys (activation_layers.{i}.weight, [1], 0.25); their forward is not used
+            self.activation_layers = nn.ModuleList([nn.PReLU() for _ in range(len(dims) - 1)])
         for name, p in self.linears.named_parameters():
             if 'weight' in name:
                 nn.init.normal_(p, mean=0, std=init_std)
@@ -248,6 +259,19 @@ class DNN(nn.Module):
                     x = ops.dense_relu_dropout(x, lin.weight, lin.bias, p, seed, i)
                     continue
                 x = self.dropout(ops.dense_relu(x, lin.weight, lin.bias))
+                continue
+            if self.activation == "prelu":
+                alpha = self.activation_layers[i].weight
+                if not self.use_bn:
+                    # y and the pre-activation out of one launch, the slope's gradient out of the dW kernel
+                    x = self.dropout(ops.dense_prelu(x, lin.weight, lin.bias, alpha))
+                    continue
+                x = ops.dense(x, lin.weight, lin.bias)
+                if xdist.current() is None and ops.bn_native(x, self.bn[i]):
+                    x = ops.bn_act(x, self.bn[i], "linear", self.training)
+                else:
+                    x = self.bn[i](x)
+                x = self.dropout(ops.prelu(x, alpha))
                 continue
             x = ops.dense(x, lin.weight, lin.bias)
             if self.use_bn and xdist.current() is None and ops.bn_native(x, self.bn[i]):

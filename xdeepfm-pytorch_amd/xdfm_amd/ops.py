@@ -1108,6 +1108,140 @@ def dense_relu_dropout(x, W, b, p, seed, layer):
     return DenseReLUDropout.apply(x, W, b, float(p), seed, int(layer))
 
 
+# XDFM_DNN_PRELU_NATIVE: a dense layer followed by nn.PReLU() (layers.DNN with activation='prelu', no batch norm) runs
+# DensePReLU -- the fused kernels of csrc/dnn.hip, forward included -- where `dense_prelu_native` holds; XDFM_DNN_NATIVE has to
+# be on as well.  0: the library GEMMs of `dense` followed by the native elementwise op (`prelu`, csrc/prelu.hip).  Either way
+# a GPU fp32 tower never runs torch's prelu_backward, whose `sum` puts a memset into a captured step.  Read once, at import; a
+# module attribute the tests and tools/dnn_prelu_probe.py flip, like DNN_NATIVE.  Default 1: the fused route is not slower
+# at either flagship layer (61.8 against 65.3 us, 45.9 against 49.2 us forward + backward) and ties in the step within its
+# spread (40 graph nodes against 46): profiles/dnn_prelu_probe.md.
+DNN_PRELU_NATIVE = _env_switch(os.environ, "XDFM_DNN_PRELU_NATIVE")
+
+
+def _alpha_ok(alpha, ref):
+    """One contiguous fp32 slope on ref's device (the weight of nn.PReLU())."""
+    return (isinstance(alpha, torch.Tensor) and alpha.is_cuda and alpha.device == ref.device and alpha.dtype == torch.float32
+            and alpha.numel() == 1 and alpha.is_contiguous())
+
+
+def dense_prelu_native(x, W, b, alpha):
+    """Does prelu(x W^T + b, alpha) run the fused kernels?  Both switches on, a bias, one fp32 device slope, and `dense_native`."""
+    return bool(DNN_PRELU_NATIVE and DNN_NATIVE and b is not None and _alpha_ok(alpha, x) and dense_native(x, W, b))
+
+
+class DensePReLU(torch.autograd.Function):
+    """y = prelu(x W^T + b, alpha) with one scalar slope, in the fp32-MFMA kernels of csrc/dnn.hip: one forward launch that
+    stores y and, when a gradient will be asked for, the pre-activation z (alpha may be 0, 1 or negative: y says neither the
+    sign nor the value of z); the two backward kernels form gz = z > 0 ? g : alpha * g while they stage g, and the slope's
+    gradient comes out of the weight-gradient kernel as the bias gradient does (double partials, a fixed-order finish).
+    Saved: x, W, z, alpha.  The kernels read alpha from device memory: a replayed graph sees the optimizer's update."""
+
+    @staticmethod
+    def forward(ctx, x, W, b, alpha):
+        _need_cuda(x, "x")
+        lib = _lib.load()
+        rows, k = x.shape
+        out = W.shape[0]
+        y = torch.empty(rows, out, dtype=torch.float32, device=x.device)
+        z = torch.empty(rows, out, dtype=torch.float32, device=x.device) if any(ctx.needs_input_grad) else None
+        _lib.check(_run("dense_prelu_fwd", 0.0, lambda: lib.xdfm_dense_prelu_fwd(
+            _ptr(x), rows, k, _ld(x), _ptr(W), out, _ptr(b), _ptr(alpha), _ptr(y), out, _ptr(z), out, _stream())), "dense_prelu_fwd")
+        ctx.save_for_backward(x, W, z, alpha)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W, z, alpha = ctx.saved_tensors
+        lib = _lib.load()
+        rows, k = x.shape
+        out = W.shape[0]
+        need_dx, need_dw, need_db, need_da = ctx.needs_input_grad
+        if not _rows_ok(g):
+            g = g.contiguous()
+        dev = g.device
+        dx = dW = db = da = None
+        if need_dx:
+            dx = torch.empty(rows, k, dtype=torch.float32, device=dev)
+            _lib.check(_run("dense_prelu_bwd_x", 0.0, lambda: lib.xdfm_dense_prelu_bwd_x(
+                _ptr(g), _ld(g), _ptr(z), out, _ptr(alpha), rows, out, _ptr(W), k, _ptr(dx), k, _stream())), "dense_prelu_bwd_x")
+        if need_dw or need_db or need_da:
+            # the slope's gradient is a by-product of this kernel, as the bias gradient is: one call whatever the combination
+            ws = torch.empty(lib.xdfm_dense_prelu_bwd_w_ws_elems(rows, k, out), dtype=torch.float32, device=dev)
+            dW = torch.empty(out, k, dtype=torch.float32, device=dev)
+            db = torch.empty(out, dtype=torch.float32, device=dev) if need_db else None
+            da = torch.empty(alpha.shape, dtype=torch.float32, device=dev) if need_da else None
+            _lib.check(_run("dense_prelu_bwd_w", 0.0, lambda: lib.xdfm_dense_prelu_bwd_w(
+                _ptr(g), _ld(g), _ptr(z), out, _ptr(alpha), _ptr(x), _ld(x), rows, k, out, _ptr(ws), _ptr(dW), _ptr(db), _ptr(da),
+                _stream())), "dense_prelu_bwd_w")
+        return dx, dW if need_dw else None, db, da
+
+
+def _dense_prelu_fused(x, W, b, alpha):
+    """The fused branch of dense_prelu (a function of its own so that tests and tools can count its calls)."""
+    return DensePReLU.apply(x, W, b, alpha)
+
+
+def dense_prelu(x, W, b, alpha):
+    """prelu(x W^T + b, alpha): DensePReLU where `dense_prelu_native` holds, else `dense` followed by `prelu`."""
+    if dense_prelu_native(x, W, b, alpha):
+        return _dense_prelu_fused(x, W, b, alpha)
+    return prelu(dense(x, W, b), alpha)
+
+
+def prelu_native(u, alpha):
+    """Does prelu(u, alpha) run the elementwise kernels of csrc/prelu.hip?  A non-empty fp32 2-D device tensor with contiguous
+    rows and one fp32 slope on its device.  No switch: the alternative is torch's prelu_backward and its memset."""
+    return bool(isinstance(u, torch.Tensor) and u.is_cuda and u.dim() == 2 and u.dtype == torch.float32 and u.shape[0] >= 1
+                and u.shape[1] >= 1 and _rows_ok(u) and _alpha_ok(alpha, u))
+
+
+class PReLU(torch.autograd.Function):
+    """y = u > 0 ? u : alpha * u with one scalar slope (csrc/prelu.hip): one launch forward; backward one launch for du and,
+    when the slope wants its gradient, per-block double partials of sum g * u [u <= 0] and a one-block finish.  Saved: u, alpha."""
+
+    @staticmethod
+    def forward(ctx, u, alpha):
+        _need_cuda(u, "u")
+        lib = _lib.load()
+        rows, cols = u.shape
+        y = torch.empty(rows, cols, dtype=torch.float32, device=u.device)
+        _lib.check(_run("prelu_fwd", 0.0, lambda: lib.xdfm_prelu_fwd(_ptr(u), _ld(u), rows, cols, _ptr(alpha), _ptr(y), cols, _stream())),
+                   "prelu_fwd")
+        ctx.save_for_backward(u, alpha)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        u, alpha = ctx.saved_tensors
+        lib = _lib.load()
+        rows, cols = u.shape
+        need_du, need_da = ctx.needs_input_grad
+        if not (need_du or need_da):
+            return None, None
+        if not _rows_ok(g):
+            g = g.contiguous()
+        dev = g.device
+        du = torch.empty(rows, cols, dtype=torch.float32, device=dev) if need_du else None
+        da = torch.empty(alpha.shape, dtype=torch.float32, device=dev) if need_da else None
+        ws = torch.empty(lib.xdfm_prelu_ws_elems(rows, cols), dtype=torch.float32, device=dev) if need_da else None
+        _lib.check(_run("prelu_bwd", 0.0, lambda: lib.xdfm_prelu_bwd(_ptr(g), _ld(g), _ptr(u), _ld(u), rows, cols, _ptr(alpha), _ptr(du), cols,
+                                                                     _ptr(da), _ptr(ws), _stream())), "prelu_bwd")
+        return du, da
+
+
+def _prelu_native(u, alpha):
+    """The native branch of prelu (a function of its own so that tests and tools can count its calls)."""
+    return PReLU.apply(u, alpha)
+
+
+def prelu(u, alpha):
+    """torch's prelu with one slope: the elementwise kernels where `prelu_native` holds; everything else (CPU, float64, other
+    ranks) is torch.nn.functional.prelu."""
+    if prelu_native(u, alpha):
+        return _prelu_native(u, alpha)
+    return torch.nn.functional.prelu(u, alpha)
+
+
 # XDFM_DNN_BN_NATIVE (default 1): a dense layer followed by nn.BatchNorm1d (layers.DNN with use_bn=True) runs its batch norm
 # and its activation in the kernels of csrc/bn.hip instead of nn.BatchNorm1d + torch.relu / torch.sigmoid.  Read once, at
 # import; a module attribute the tests and tools/dnn_bn_probe.py flip, like DNN_NATIVE (of which it is independent: the

@@ -74,6 +74,8 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--dnn_hidden_units", type=str, default=None, help="default: the model class's own (256,256; pro light 128,64)")
     p.add_argument("--cin_activation", type=str, default="relu", choices=["relu", "linear", "sigmoid"],
                    help="activation of the CIN levels (the reference's scripts hard-code relu)")
+    p.add_argument("--dnn_activation", type=str, default="relu", choices=["relu", "linear", "sigmoid", "prelu"],
+                   help="activation of the DNN tower (the reference's scripts leave the models' default, relu)")
     p.add_argument("--cin_num_heads", type=int, default=4)
     p.add_argument("--cin_attn_dropout", type=float, default=0.0)
     p.add_argument("--cin_use_layer_norm", action="store_true", default=True)
@@ -221,7 +223,8 @@ def build_model(args, cols):
     """The model the chosen reference script builds (xdftrain.py:421-430, xdftrain_attn.py:394-425,
     xdftrain_pro.py:305-327), from this package's drop-in classes."""
     common = dict(task="binary", l2_reg_embedding=args.l2_reg_embedding, l2_reg_dnn=args.l2_reg_dnn,
-                  dnn_dropout=args.dnn_dropout, cin_activation=args.cin_activation, device=args.device)
+                  dnn_dropout=args.dnn_dropout, cin_activation=args.cin_activation, dnn_activation=args.dnn_activation,
+                  device=args.device)
     if args.cin_layer_size:
         common["cin_layer_size"] = tuple(int(v) for v in args.cin_layer_size.split(","))
     if args.dnn_hidden_units:
