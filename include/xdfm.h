@@ -118,7 +118,19 @@ int xdfm_device_count(void);                /* <0: HIP error code negated */
  * "last_fwd_inst", "last_bwx_inst", "last_bww_inst" = the template instance of that launch, T * 1000 + NW * 100 + NT * 10 + S:
  * T = row tiles per wave of the forward (MT 2 / 4 / 8), h-blocks per tile of dX (HBT 2 / 4 / 8 / 16), 4 for dW; NW = waves per
  * workgroup (4 / 8); NT = MFMA terms per product (3 f16x3, 1 bf16); S = 1 for the folded level-0 kernel.  0 when the call ran
- * the mode-0 kernel, -1 before the first call.  Example: 8831 = forward, MT 8, 8 waves, f16x3, folded level 0. */
+ * the mode-0 kernel, -1 before the first call.  Example: 8831 = forward, MT 8, 8 waves, f16x3, folded level 0.
+ * "last_fwd_f32", "last_bwx_f32", "last_bww_f32" = the same for the mode-0 (v_mfma_f32_32x32x2_f32) kernels: the template
+ * instance the last xdfm_cin_level_fwd / _bwd_x(_ex) / _bwd_w call launched, 0 when it ran an f16x3 / bf16 kernel, -1 before
+ * the first call; a call that returns an error before its launch leaves them alone.
+ *   last_fwd_f32 = MT * 1000 + NF * 100 + MPT: MT = row tiles of 32 per wave (1 / 2 / 4 / 8, by H), NF = column fragments of 32
+ *      per wave (2 with "fwd_nf" 2 at MT 4, else 1), MPT = 13 / 11 for the straight-line kernel of m = 25, 26 / 21, 22 at
+ *      MT >= 4, 0 for the generic kernel.  Example: 4213 = MT 4, two fragments, m = 26.
+ *   last_bwx_f32 = HS4 * 10 + JB: HS4 = float4 groups along h (1 .. 32, the power of two >= H / 8), JB = chains a wave
+ *      interleaves (2 with "dbg" bit 32, an even m and 4 <= HS4 <= 16, else 1).  Example: 161.
+ *   last_bww_f32 = S * 1000 + MT * 100 + KV * 10 + slab: S = n-splits launched, MT = row tiles per wave (1 / 2 / 4, by H or
+ *      "bww_mt"), KV = 1 register-staged kernel ("dbg" bit 8), 2 dword LDS-DMA, 3 dwordx4 LDS-DMA (MT 4, N % 4 == 0, 16-byte
+ *      aligned operands, not "dbg" bit 16), slab = 1 per-split slabs summed in order / 0 atomic epilogue ("bww_slab").
+ *      Example: 32431 = 32 n-splits, MT 4, dwordx4 LDS-DMA, slabs. */
 int xdfm_set_option(const char* key, int value);
 int xdfm_get_option(const char* key);
 /* Ticket board: `board` = a DEVICE array of `slots` >= 1040 unsigned ints, zeroed once by the caller and kept alive, registered

@@ -39,7 +39,8 @@ def test_abi_version_and_error_text():
     assert lib.xdfm_set_option(b"no_such_key", 1) == 1
     assert lib.xdfm_set_option(b"fwd_nf", 2) == 0 and lib.xdfm_get_option(b"fwd_nf") == 2
     assert lib.xdfm_set_option(b"fwd_nf", 1) == 0
-    for probe in (b"last_fwd_inst", b"last_bwx_inst", b"last_bww_inst"):       # instance probes are known keys
+    for probe in (b"last_fwd_inst", b"last_bwx_inst", b"last_bww_inst", b"last_fwd_f32", b"last_bwx_f32",
+                  b"last_bww_f32"):                                             # instance probes are known keys
         old = lib.xdfm_get_option(probe)
         assert lib.xdfm_set_option(probe, old) == 0
 

@@ -709,7 +709,9 @@ static int launch_bwd_x(const float* dOut, const float* xp, const float* x0, con
     if (xdfm_opt(OPT_DBG) & 4) lds = 80 * 1024;
     // optional: two interleaved chains per wave (even m, H <= 128).  Measured 110 vs 112 TFLOP/s for the
     // single dependent chain at config 2, so it stays off by default (A/B knob: dbg bit 5).
-    if (HS4 <= 16 && HS4 >= 4 && m % 2 == 0 && (xdfm_opt(OPT_DBG) & 32))
+    const bool two = HS4 <= 16 && HS4 >= 4 && m % 2 == 0 && (xdfm_opt(OPT_DBG) & 32);
+    xdfm_opt_note(OPT_LAST_BWX_F32, f32_bwx_code(HS4, two ? 2 : 1));
+    if (two)
         hipLaunchKernelGGL((cin_bwd_x_kernel<HS4, 2>), dim3(ceil_div(N, 128)), dim3(256), lds, st, dOut, xp, x0, Wz, H,
                            Hp, m, N, IB, dxp, dx0, flags);
     else
@@ -732,15 +734,18 @@ static int launch_bwd_w(const float* dOut, const float* xp, const float* x0, int
     if (xdfm_opt(OPT_DBG) & 8) {      // v1: register staging, single LDS buffer (atomics only)
         if (slab) return xdfm_fail(XDFM_ERR_INVALID, "cin_level_bwd_w: dbg 8 needs bww_slab=0");
         const size_t lds = (size_t)(32 * MT + 4 * (32 + JT)) * BWW_PITCH * sizeof(float);
+        xdfm_opt_note(OPT_LAST_BWW_F32, f32_bww_code(MT, 1, false, g.nsplit));
         hipLaunchKernelGGL((cin_bwd_w_kernel<MT, JT>), dim3(g.gx, g.nsplit), dim3(256), lds, st, dOut, xp, x0, H, Hp, m,
                            N, g.IB, g.JP, g.TPH, g.n_per_split, g.Hpad, g.IPAD, ws);
     } else if (MT == 4 && N % 4 == 0 && !(xdfm_opt(OPT_DBG) & 16) &&
                ((((size_t)dOut) | ((size_t)xp) | ((size_t)x0)) & 15) == 0) {
         const size_t lds = (size_t)2 * (32 * MT + 4 * (32 + 8)) * 32 * sizeof(float);
+        xdfm_opt_note(OPT_LAST_BWW_F32, f32_bww_code(MT, 3, slab, g.nsplit));
         hipLaunchKernelGGL((cin_bwd_w_dma4_kernel<MT, JT>), dim3(g.gx, g.nsplit), dim3(256), lds, st, dOut, xp, x0, H, Hp,
                            m, N, g.IB, g.JP, g.TPH, g.n_per_split, g.Hpad, g.IPAD, ws, stride);
     } else {
         const size_t lds = (size_t)2 * (32 * MT + 4 * (32 + JT)) * 32 * sizeof(float);
+        xdfm_opt_note(OPT_LAST_BWW_F32, f32_bww_code(MT, 2, slab, g.nsplit));
         hipLaunchKernelGGL((cin_bwd_w_dma_kernel<MT, JT>), dim3(g.gx, g.nsplit), dim3(256), lds, st, dOut, xp, x0, H, Hp,
                            m, N, g.IB, g.JP, g.TPH, g.n_per_split, g.Hpad, g.IPAD, ws, stride);
     }
@@ -836,7 +841,7 @@ int xdfm_cin_level_bwd_x_ex(const float* dOut, const float* xp, const float* x0,
     XDFM_REQUIRE(H > 0 && H <= 256 && Hp > 0 && m > 0 && N > 0, "cin_level_bwd_x: bad shape H=%d (<=256) Hp=%d m=%d",
                  H, Hp, m);
     hipStream_t st = (hipStream_t)stream;
-    if (x3_bwx_usable(H, Hp, m)) { xdfm_opt_note(OPT_LAST_BWX, xdfm_opt(OPT_CIN_MATH)); return x3_level_bwd_x(x3_dout_plain(dOut), xp, x0, Wz, H, Hp, m, N, dxp, dx0, flags, st); }
+    if (x3_bwx_usable(H, Hp, m)) { xdfm_opt_note(OPT_LAST_BWX, xdfm_opt(OPT_CIN_MATH)); xdfm_opt_note(OPT_LAST_BWX_F32, 0); return x3_level_bwd_x(x3_dout_plain(dOut), xp, x0, Wz, H, Hp, m, N, dxp, dx0, flags, st); }
     xdfm_opt_note(OPT_LAST_BWX, 0);
     xdfm_opt_note(OPT_LAST_BWX_INST, 0);
     xdfm_opt_note(OPT_LAST_SYM, xdfm_opt(OPT_LAST_SYM) & ~2);
@@ -872,7 +877,7 @@ int xdfm_cin_level_bwd_w(const float* dOut, const float* xp, const float* x0, in
     XDFM_REQUIRE(dOut && xp && x0 && ws && dW, "cin_level_bwd_w: null pointer");
     XDFM_REQUIRE(H > 0 && Hp > 0 && m > 0 && N > 0, "cin_level_bwd_w: bad shape H=%d Hp=%d m=%d", H, Hp, m);
     hipStream_t st = (hipStream_t)stream;
-    if (x3_bww_usable(dOut, xp, x0, H, N)) { xdfm_opt_note(OPT_LAST_BWW, xdfm_opt(OPT_CIN_MATH)); return x3_level_bwd_w(dOut, xp, x0, H, Hp, m, N, ws, dW, false, st); }
+    if (x3_bww_usable(dOut, xp, x0, H, N)) { xdfm_opt_note(OPT_LAST_BWW, xdfm_opt(OPT_CIN_MATH)); xdfm_opt_note(OPT_LAST_BWW_F32, 0); return x3_level_bwd_w(dOut, xp, x0, H, Hp, m, N, ws, dW, false, st); }
     xdfm_opt_note(OPT_LAST_BWW, 0);
     xdfm_opt_note(OPT_LAST_BWW_INST, 0);
     xdfm_opt_note(OPT_LAST_SYM, xdfm_opt(OPT_LAST_SYM) & ~4);
@@ -956,6 +961,7 @@ int xdfm_cin_level_bwd_x_src(const unsigned* mask, long mask_ld, const float* dH
     const X3DoutSrc S = {nullptr, mask, mask_ld, hid_rows > 0 ? dHid : nullptr, hid_rows, dir_rows > 0 ? dDir : nullptr, dir_mode, lddir,
                          dir_off, dir0, dir_rows, logD, h0};
     xdfm_opt_note(OPT_LAST_BWX, xdfm_opt(OPT_CIN_MATH));
+    xdfm_opt_note(OPT_LAST_BWX_F32, 0);
     return x3_level_bwd_x(S, xp, x0, Wz, H, Hp, m, N, dxp, dx0, flags, (hipStream_t)stream);
 }
 
@@ -965,6 +971,7 @@ int xdfm_cin_level_bwd_w_prepared(const float* dOut, const float* xp, const floa
     XDFM_REQUIRE(H > 0 && Hp > 0 && m > 0 && N > 0, "cin_level_bwd_w: bad shape H=%d Hp=%d m=%d", H, Hp, m);
     XDFM_REQUIRE(x3_bww_usable(dOut, xp, x0, H, N), "cin_level_bwd_w_prepared: no f16x3 / bf16 dW kernel for this call (H=%d)", H);
     xdfm_opt_note(OPT_LAST_BWW, xdfm_opt(OPT_CIN_MATH));
+    xdfm_opt_note(OPT_LAST_BWW_F32, 0);
     return x3_level_bwd_w(dOut, xp, x0, H, Hp, m, N, ws, dW, true, (hipStream_t)stream);
 }
 

@@ -383,6 +383,7 @@ static int launch_fwd_mp(const float* xp, const float* x0, const float* Wf, cons
     size_t lds = (size_t)4 * FWD_IC * 32 * NF * sizeof(float);
     if (xdfm_opt(OPT_DBG) & 4) lds = 80 * 1024;
     dim3 grid(ceil_div(N, 128L * NF), MB);
+    xdfm_opt_note(OPT_LAST_FWD_F32, f32_fwd_code(MT, NF, MPT));
     hipLaunchKernelGGL((cin_fwd_mp_kernel<MT, NF, MPT>), grid, dim3(256), lds, st, xp, x0, Wf, bias, H, Hp, m, N, TP,
                        act, out, xdfm_opt(OPT_DBG));
     return xdfm_check_launch("cin_level_fwd");
@@ -408,6 +409,7 @@ static int launch_fwd(const float* xp, const float* x0, const float* Wf, const f
     const size_t lds = (size_t)4 * (2 * MP + FWD_IC) * 32 * NF * sizeof(float);
     if (lds > 160 * 1024) return xdfm_fail(XDFM_ERR_INVALID, "cin_level_fwd: m=%d needs %zu B of LDS", m, lds);
     dim3 grid(ceil_div(N, 128L * NF), MB);
+    xdfm_opt_note(OPT_LAST_FWD_F32, f32_fwd_code(MT, NF, 0));
     hipLaunchKernelGGL((cin_fwd_kernel<MT, NF>), grid, dim3(256), lds, st, xp, x0, Wf, bias, H, Hp, m, N, TP,
                        Tpad, T, act, out, xdfm_opt(OPT_DBG));
     return xdfm_check_launch("cin_level_fwd");
@@ -457,7 +459,7 @@ int xdfm_cin_level_fwd(const float* xp, const float* x0, const float* Wf, const 
     XDFM_REQUIRE(H > 0 && Hp > 0 && m > 0 && N > 0, "cin_level_fwd: bad shape H=%d Hp=%d m=%d N=%ld", H, Hp, m, N);
     XDFM_REQUIRE(xdfm_act_known(act), "cin_level_fwd: unsupported activation %d", act);
     hipStream_t st = (hipStream_t)stream;
-    if (x3_fwd_usable(H, Hp, m)) { xdfm_opt_note(OPT_LAST_FWD, xdfm_opt(OPT_CIN_MATH)); return x3_level_fwd(xp, x0, Wf, bias, H, Hp, m, N, act, out, x3_fwd_epi_plain(H), st); }
+    if (x3_fwd_usable(H, Hp, m)) { xdfm_opt_note(OPT_LAST_FWD, xdfm_opt(OPT_CIN_MATH)); xdfm_opt_note(OPT_LAST_FWD_F32, 0); return x3_level_fwd(xp, x0, Wf, bias, H, Hp, m, N, act, out, x3_fwd_epi_plain(H), st); }
     xdfm_opt_note(OPT_LAST_FWD, 0);
     xdfm_opt_note(OPT_LAST_FWD_INST, 0);
     xdfm_opt_note(OPT_LAST_SYM, xdfm_opt(OPT_LAST_SYM) & ~1);
@@ -493,6 +495,7 @@ int xdfm_cin_level_fwd_ex(const float* xp, const float* x0, const float* Wf, con
     while ((1 << logD) < D) ++logD;
     const X3FwdEpi epi = {keep_rows, res, ldres, res_off, res ? dir0 : H, logD, mask, mask_ld};
     xdfm_opt_note(OPT_LAST_FWD, xdfm_opt(OPT_CIN_MATH));
+    xdfm_opt_note(OPT_LAST_FWD_F32, 0);
     return x3_level_fwd(xp, x0, Wf, bias, H, Hp, m, N, act, out, epi, (hipStream_t)stream);
 }
 

@@ -35,10 +35,18 @@ enum {
     OPT_LAST_FWD_INST,   // read-only probes: template instance of the last f16x3 / bf16 forward / dX / dW launch (x3_inst_code),
     OPT_LAST_BWX_INST,   //   0 when the call ran the fp32-MFMA kernel, -1 before the first call
     OPT_LAST_BWW_INST,
+    OPT_LAST_FWD_F32,    // read-only probes: template instance of the last fp32-MFMA forward / dX / dW launch (f32_*_code below),
+    OPT_LAST_BWX_F32,    //   0 when the call ran an f16x3 / bf16 kernel, -1 before the first call
+    OPT_LAST_BWW_F32,
     OPT_COUNT
 };
 // value of the instance probes: row tiles (forward MT, dX HBT, dW MT) * 1000 + waves * 100 + MFMA terms * 10 + folded level 0
 static inline int x3_inst_code(int T, int NW, int NT, bool SYM) { return T * 1000 + NW * 100 + NT * 10 + (SYM ? 1 : 0); }
+// values of the fp32-MFMA instance probes.  forward: MPT = 0 for the generic cin_fwd_kernel; dW: KV = 1 cin_bwd_w_kernel (v1),
+// 2 dword-DMA, 3 dwordx4-DMA, `slab` = 1 per-split slabs / 0 atomic epilogue, nsplit = the n-splits launched (gridDim.y)
+static inline int f32_fwd_code(int MT, int NF, int MPT) { return MT * 1000 + NF * 100 + MPT; }
+static inline int f32_bwx_code(int HS4, int JB) { return HS4 * 10 + JB; }
+static inline int f32_bww_code(int MT, int KV, bool slab, int nsplit) { return nsplit * 1000 + MT * 100 + KV * 10 + (slab ? 1 : 0); }
 
 // Ticket board (api.hip, xdfm_set_ticket_board): a small zeroed device array the host registers once per device.  A kernel
 // that leaves per-block partials takes a ticket when a block is done; the block that draws the last one sums the
