@@ -60,6 +60,8 @@
  * xdfm_dense_prelu_fwd, xdfm_dense_prelu_bwd_x, xdfm_dense_prelu_bwd_w, xdfm_dense_prelu_bwd_w_ws_elems (the dense kernels with a
  * PReLU of one scalar slope: dnn_activation='prelu') and xdfm_prelu_ws_elems, xdfm_prelu_fwd, xdfm_prelu_bwd (K13: the same
  * PReLU elementwise, csrc/prelu.hip) -- additions, the version stays 8.
+ * xdfm_bn_stats, xdfm_bn_fwd_apply_sync, xdfm_bn_bwd_sums, xdfm_bn_bwd_apply_sync (K12 split around an all-gather: batch norm
+ * over the global batch of a row-parallel step) -- additions, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -580,7 +582,28 @@ int xdfm_prelu_bwd(const float* g, long ldg, const float* u, long ldu, long rows
  * No atomics, no zeroed cells, no memset, the same bits on every run; no entry point synchronises or allocates.
  * XDFM_ERR_INVALID, before any device call: a NULL operand (ws included; or a ws off 8-byte alignment), rows < 1 (< 2 in
  * training and its backward),
- * cols < 1, a pitch below cols, an unknown act, eps <= 0, momentum outside [0, 1]. */
+ * cols < 1, a pitch below cols, an unknown act, eps <= 0, momentum outside [0, 1].
+ *
+ * Synchronised batch norm (row-parallel training: statistics over the global batch, as torch's SyncBatchNorm).  Each
+ * direction of the training batch norm is split where the other ranks' numbers are needed; the caller runs one all-gather in
+ * between.  The rules above hold for all four entry points.
+ * xdfm_bn_stats (two launches): pair double[2][cols] = (mean, M2) of this rank's rows (rows >= 1), per-block pairs merged
+ * with Chan's formula in the order xdfm_bn_fwd_train uses; ws as for xdfm_bn_fwd_train.
+ * xdfm_bn_fwd_apply_sync (one launch): all is device memory double[world][1 + 2 * cols], per rank its count, its means, its
+ * M2s (the count followed by the rank's pair: what the all-gather delivers).  The triples are merged with Chan's formula in
+ * doubles in rank order 0 .. world - 1, a rank whose count is 0 (one that holds only a stand-in row) is skipped; n = the sum
+ * of the counts, which the caller keeps >= 2 (the count is device data: it is not validated here).  y, save_mean, save_rstd
+ * and both running vectors are as xdfm_bn_fwd_train writes them with rows = n: var = M2 / n, running_var takes M2 / (n - 1),
+ * each running element updated in place by exactly one block.  The y of a stand-in row uses the global statistics.
+ * xdfm_bn_bwd_sums (two launches): sums double[2][cols] = (sum gm, sum gm * xhat) over this rank's rows (rows >= 1), per-block
+ * partials added in a fixed order; gm formed while g is loaded; ws as for xdfm_bn_bwd.
+ * xdfm_bn_bwd_apply_sync (one launch): all is double[world][2 * cols], the ranks' sums; S1, S2 = their sums in rank order;
+ *     dz = gamma * rstd * (gm - S1 / n_total - xhat * S2 / n_total),
+ * dbeta, dgamma = this rank's own sums (row `rank` of all) rounded to fp32: the caller's all-reduce SUM of the dense
+ * gradients makes them global.  rows_counted is rows, or 0 for a rank that holds only a stand-in row: every element of its
+ * dz is an exact zero (its own sums are zero, the other ranks' are not).  dz, dgamma and dbeta may each be NULL.
+ * XDFM_ERR_INVALID, before any device call, as above and: world < 1, rank outside [0, world), n_total < 2, rows_counted
+ * neither rows nor 0, pair / sums / all off 8-byte alignment. */
 int xdfm_bn_row_block(void);
 size_t xdfm_bn_ws_elems(long rows, int cols);                          /* 0 for rows < 1 or cols < 1 */
 int xdfm_bn_fwd_train(const float* z, long ldz, long rows, int cols, const float* gamma, const float* beta, float eps, float momentum,
@@ -594,6 +617,15 @@ int xdfm_bn_bwd(const float* g, long ldg, const float* y, long ldy, const float*
 int xdfm_bn_bwd_eval(const float* g, long ldg, const float* y, long ldy, const float* z, long ldz, long rows, int cols,
                      const float* gamma, const float* mean, const float* rstd, int act, float* dz, long lddz, float* dgamma, float* dbeta,
                      float* ws, void* stream);
+int xdfm_bn_stats(const float* z, long ldz, long rows, int cols, double* pair, float* ws, void* stream);
+int xdfm_bn_fwd_apply_sync(const float* z, long ldz, long rows, int cols, const double* all, int world, const float* gamma,
+                           const float* beta, float eps, float momentum, int act, float* y, long ldy, float* save_mean,
+                           float* save_rstd, float* running_mean, float* running_var, void* stream);
+int xdfm_bn_bwd_sums(const float* g, long ldg, const float* y, long ldy, const float* z, long ldz, long rows, int cols,
+                     const float* save_mean, const float* save_rstd, int act, double* sums, float* ws, void* stream);
+int xdfm_bn_bwd_apply_sync(const float* g, long ldg, const float* y, long ldy, const float* z, long ldz, long rows, long rows_counted,
+                           int cols, const double* all, int world, int rank, long n_total, const float* gamma, const float* save_mean,
+                           const float* save_rstd, int act, float* dz, long lddz, float* dgamma, float* dbeta, void* stream);
 
 /* ------------------------------------------------------------------ output head: link + loss (K8)
  * z_b = lin_b + <u_b, wu> + <v_b, wv> + bias,  pred = LINK(z),  loss = sum_b LOSS(pred_b, y_b).

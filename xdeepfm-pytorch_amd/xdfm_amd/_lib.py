@@ -144,6 +144,11 @@ SIGNATURES = {
     "xdfm_bn_fwd_eval": (c_int, [P, c_long, c_long, c_int, P, P, c_float, c_int, P, c_long, P, P, P]),
     "xdfm_bn_bwd": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, P, P, P, c_int, P, c_long, P, P, P, P]),
     "xdfm_bn_bwd_eval": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, P, P, P, c_int, P, c_long, P, P, P, P]),
+    "xdfm_bn_stats": (c_int, [P, c_long, c_long, c_int, P, P, P]),
+    "xdfm_bn_fwd_apply_sync": (c_int, [P, c_long, c_long, c_int, P, c_int, P, P, c_float, c_float, c_int, P, c_long, P, P, P, P, P]),
+    "xdfm_bn_bwd_sums": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_int, P, P, c_int, P, P, P]),
+    "xdfm_bn_bwd_apply_sync": (c_int, [P, c_long, P, c_long, P, c_long, c_long, c_long, c_int, P, c_int, c_int, c_long, P, P, P, c_int, P,
+                                       c_long, P, P, P]),
     "xdfm_l2_reg_fwd": (c_int, [P, P, P, c_int, P, P, P]),
     "xdfm_l2_reg_bwd": (c_int, [P, P, P, c_int, P, P, P, c_int, P]),
 }

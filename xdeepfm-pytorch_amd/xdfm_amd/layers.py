@@ -247,6 +247,12 @@ class DNN(nn.Module):
 
     last_drop_seed = None        # the seed of the last tower call that ran the native dropout (read by the tests)
 
+    def takes_bn_sync(self, dp):
+        """Will this tower's forward under the context `dp` hold a collective (ops.bn_act_sync)?  What `ops.bn_sync_native`
+        will say for its layers, judged without an input: such a step cannot sit in a captured graph."""
+        return bool(self.use_bn and ops.DNN_BN_SYNC and ops.DNN_BN_NATIVE and isinstance(dp, xdist.RowParallel)
+                    and all(b.weight is not None and b.weight.is_cuda for b in self.bn))
+
     def forward(self, x):
         p = float(self.dropout.p)
         seed = None              # one per tower call, shared by the layers through their index
@@ -267,18 +273,26 @@ class DNN(nn.Module):
                     x = self.dropout(ops.dense_prelu(x, lin.weight, lin.bias, alpha))
                     continue
                 x = ops.dense(x, lin.weight, lin.bias)
-                if xdist.current() is None and ops.bn_native(x, self.bn[i]):
+                dp = xdist.current()
+                if dp is None and ops.bn_native(x, self.bn[i]):
                     x = ops.bn_act(x, self.bn[i], "linear", self.training)
+                elif ops.bn_sync_native(x, self.bn[i], dp):
+                    x = ops.bn_act_sync(x, self.bn[i], "linear", self.training, dp)
                 else:
                     x = self.bn[i](x)
                 x = self.dropout(ops.prelu(x, alpha))
                 continue
             x = ops.dense(x, lin.weight, lin.bias)
-            if self.use_bn and xdist.current() is None and ops.bn_native(x, self.bn[i]):
+            dp = xdist.current() if self.use_bn else None
+            if self.use_bn and dp is None and ops.bn_native(x, self.bn[i]):
                 # batch norm + activation in the kernels of csrc/bn.hip: one [rows, out] tensor written instead of three
-                # (DESIGN 4.3d).  Row-parallel training keeps the stock modules: per-shard statistics are a question of
-                # their own (SyncBN).
+                # (DESIGN 4.3d).  Row-parallel training keeps the stock modules over each rank's shard unless
+                # XDFM_DNN_BN_SYNC asks for the statistics of the global batch (below).
                 x = self.dropout(ops.bn_act(x, self.bn[i], self.activation, self.training))
+                continue
+            if self.use_bn and ops.bn_sync_native(x, self.bn[i], dp):
+                # row-parallel, opt-in: the same kernels split around one all-gather each way (ops.bn_act_sync)
+                x = self.dropout(ops.bn_act_sync(x, self.bn[i], self.activation, self.training, dp))
                 continue
             if self.use_bn:
                 x = self.bn[i](x)

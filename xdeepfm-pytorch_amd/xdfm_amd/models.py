@@ -563,6 +563,10 @@ class BaseModel(nn.Module):
     def _can_split_step(self, dp, fuse):
         if dp is None or fuse is None:
             return False
+        # a tower with synchronised batch norm (XDFM_DNN_BN_SYNC) holds collectives in its forward and backward: no
+        # collective-free first half to capture, the step runs by the eager branch below
+        if any(isinstance(mod, DNN) and mod.takes_bn_sync(dp) for mod in self.modules()):
+            return False
         self._gather_plan()
         return bool(getattr(self, "_fused_linear", False))
 

@@ -1338,6 +1338,114 @@ def _bn_act_native(z, bn, code, training):
     return BatchNormAct.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), float(bn.momentum), code, training)
 
 
+# XDFM_DNN_BN_SYNC (default 0): under row-parallel training (xdfm_amd/dist.py) the batch norm of the DNN tower takes its mean
+# and variance over the GLOBAL batch, as torch's SyncBatchNorm does, in the native kernels: N ranks then equal one process
+# on the global batch and the running statistics of a checkpoint are those of the whole batch.  Off, a row-parallel tower
+# keeps the stock nn.BatchNorm1d over each rank's shard, as before.  Opt-in because it changes what a row-parallel run with
+# dnn_use_bn=True computes, adds two small collectives per batch-norm layer and direction, and keeps the row-parallel step
+# out of the captured graph (a collective sits inside the tower).  Read once, at import, like its neighbours.
+DNN_BN_SYNC = _env_switch(os.environ, "XDFM_DNN_BN_SYNC", False)
+
+
+def bn_sync_native(z, bn, dp):
+    """Does act(bn(z)) run the synchronised native kernels?  The XDFM_DNN_BN_SYNC switch on, `bn_native(z, bn)`, and `dp` a
+    dist.RowParallel context (anything else -- no context, an object of another kind -- keeps the caller's other routes)."""
+    if not DNN_BN_SYNC or dp is None:
+        return False
+    from . import dist as xdist
+    return isinstance(dp, xdist.RowParallel) and bn_native(z, bn)
+
+
+def _bn_sync_count(z, dp):
+    """Rows of this rank that belong to the global batch: all of z's, or 0 for a rank that holds only a stand-in row
+    (dist.RowParallel.shard).  Without a preceding shard() every row counts."""
+    if dp._n_global is not None and dp.local_sizes()[dp.rank] == 0:
+        return 0
+    return int(z.shape[0])
+
+
+class BatchNormActSync(torch.autograd.Function):
+    """BatchNormAct in training mode with the statistics of the global batch of a row-parallel step.  Forward: this rank's
+    (mean, M2) pair (xdfm_bn_stats), ONE all-gather of [count | means | M2s] doubles, then the Chan merge of the ranks'
+    triples in rank order + apply (xdfm_bn_fwd_apply_sync), which also updates the running statistics -- from the same
+    gathered bytes on every rank, so the replicas' buffers stay bit-identical.  Backward: this rank's two column sums
+    (xdfm_bn_bwd_sums), ONE all-gather, then dz over the global sums (xdfm_bn_bwd_apply_sync); dgamma and dbeta are this
+    rank's own sums, which the flat all-reduce of the dense gradients makes global like every other dense weight's.  A
+    rank that holds only a stand-in row contributes count 0 and gets exact zeros for dz."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, running_mean, running_var, eps, momentum, act, dp, count):
+        _need_cuda(z, "z")
+        lib = _lib.load()
+        rows, cols = z.shape
+        dev = z.device
+        ws = torch.empty(lib.xdfm_bn_ws_elems(rows, cols), dtype=torch.float32, device=dev)
+        mine = torch.empty(1, 1 + 2 * cols, dtype=torch.float64, device=dev)
+        mine[0, 0] = float(count)
+        pair = mine[0, 1:]
+        _lib.check(_run("bn_stats", 0.0, lambda: lib.xdfm_bn_stats(_ptr(z), _ld(z), rows, cols, _ptr(pair), _ptr(ws), _stream())),
+                   "bn_stats")
+        gathered = dp.all_gather_rows(mine)
+        # the counts follow from the sharding alone, but they are read off the gathered buffer: what every rank checks is
+        # what the kernel will merge, and all ranks take the same decision after the same collective
+        n_total = int(round(float(gathered[:, 0].sum().item())))
+        if n_total < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s over %d ranks"
+                             % (tuple(z.size()), dp.world))
+        y = torch.empty(rows, cols, dtype=torch.float32, device=dev)
+        stats = torch.empty(2, cols, dtype=torch.float32, device=dev)
+        mean, rstd = stats[0], stats[1]
+        _lib.check(_run("bn_fwd_apply_sync", 0.0, lambda: lib.xdfm_bn_fwd_apply_sync(
+            _ptr(z), _ld(z), rows, cols, _ptr(gathered), dp.world, _ptr(gamma), _ptr(beta), float(eps), float(momentum), int(act),
+            _ptr(y), cols, _ptr(mean), _ptr(rstd), _ptr(running_mean), _ptr(running_var), _stream())), "bn_fwd_apply_sync")
+        ctx.act, ctx.dp, ctx.counted, ctx.n_total = int(act), dp, rows if count else 0, n_total
+        ctx.save_for_backward(z, y, gamma, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        z, y, gamma, mean, rstd = ctx.saved_tensors
+        lib = _lib.load()
+        dp = ctx.dp
+        rows, cols = z.shape
+        need_dz, need_dg, need_db = ctx.needs_input_grad[:3]
+        if not _rows_ok(g):
+            g = g.contiguous()
+        dev = g.device
+        # the collective runs whatever this rank needs: every rank joins it
+        ws = torch.empty(lib.xdfm_bn_ws_elems(rows, cols), dtype=torch.float32, device=dev)
+        mine = torch.empty(1, 2 * cols, dtype=torch.float64, device=dev)
+        _lib.check(_run("bn_bwd_sums", 0.0, lambda: lib.xdfm_bn_bwd_sums(
+            _ptr(g), _ld(g), _ptr(y), _ld(y), _ptr(z), _ld(z), rows, cols, _ptr(mean), _ptr(rstd), ctx.act, _ptr(mine), _ptr(ws),
+            _stream())), "bn_bwd_sums")
+        gathered = dp.all_gather_rows(mine)
+        dz = torch.empty(rows, cols, dtype=torch.float32, device=dev) if need_dz else None
+        dgamma = torch.empty(cols, dtype=torch.float32, device=dev) if need_dg else None
+        dbeta = torch.empty(cols, dtype=torch.float32, device=dev) if need_db else None
+        if need_dz or need_dg or need_db:
+            _lib.check(_run("bn_bwd_apply_sync", 0.0, lambda: lib.xdfm_bn_bwd_apply_sync(
+                _ptr(g), _ld(g), _ptr(y), _ld(y), _ptr(z), _ld(z), rows, ctx.counted, cols, _ptr(gathered), dp.world, dp.rank,
+                ctx.n_total, _ptr(gamma), _ptr(mean), _ptr(rstd), ctx.act, _ptr(dz), cols, _ptr(dgamma), _ptr(dbeta), _stream())),
+                "bn_bwd_apply_sync")
+        return dz, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def bn_act_sync(z, bn, act, training, dp):
+    """act(bn(z)) with the statistics of the global batch of the row-parallel context `dp` (callers test `bn_sync_native`
+    first).  Training: BatchNormActSync, num_batches_tracked incremented on the device as in `_bn_act_native`; fewer than two
+    rows in the global batch raise the stock module's ValueError on every rank, after the gather all of them have joined.
+    Evaluation: the running statistics are identical on all replicas, so it is BatchNormAct's evaluation branch
+    (xdfm_bn_fwd_eval / xdfm_bn_bwd_eval) with no collective."""
+    code = activation_code(act)
+    if not training:
+        return BatchNormAct.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), float(bn.momentum), code,
+                                  False)
+    y = BatchNormActSync.apply(z, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), float(bn.momentum), code, dp,
+                               _bn_sync_count(z, dp))
+    bn.num_batches_tracked.add_(1)
+    return y
+
+
 # --------------------------------------------------------------------------------------------- #
 # output head                                                                                    #
 # --------------------------------------------------------------------------------------------- #
