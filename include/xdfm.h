@@ -62,6 +62,8 @@
  * PReLU elementwise, csrc/prelu.hip) -- additions, the version stays 8.
  * xdfm_bn_stats, xdfm_bn_fwd_apply_sync, xdfm_bn_bwd_sums, xdfm_bn_bwd_apply_sync (K12 split around an all-gather: batch norm
  * over the global batch of a row-parallel step) -- additions, the version stays 8.
+ * xdfm_head_fwd_w, xdfm_head_bwd_w (K8 with one weight per example: sample_weight / class_weight of fit()) -- additions, the
+ * version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -642,7 +644,24 @@ int xdfm_bn_bwd_apply_sync(const float* g, long ldg, const float* y, long ldy, c
  * (|pred - y|, gradient sign with sgn(0) = 0, as torch.sign).  The backward reads pred and y only.  The _ex entry
  * points return XDFM_ERR_INVALID, before any device call and with both values in the message, for a link outside
  * {0, 1}, a loss outside {0, 1, 2} and for (identity, bce), which does not exist.  xdfm_head_fwd / xdfm_head_bwd
- * are the _ex calls with (XDFM_LINK_SIGMOID, XDFM_LOSS_BCE). */
+ * are the _ex calls with (XDFM_LINK_SIGMOID, XDFM_LOSS_BCE).
+ *
+ * Example weights (xdfm_head_fwd_w / xdfm_head_bwd_w; the `sample_weight` / `class_weight` of fit()): the _ex
+ * arguments plus w [B] fp32 or NULL, in front of the stream.
+ *   forward   loss = sum_b fl(w_b * LOSS(pred_b, y_b)), rows, blocks and the 128-partial tree in the order of the
+ *             unweighted call; pred does not depend on w.
+ *   backward  g_b = fl(w_b * g) with g the unweighted row gradient d loss / d z of the table in csrc/reg.hip; dlin,
+ *             du, dv, d wu, d wv and d bias are formed from g_b as in the unweighted call.
+ *   value     roundings                                                    beside the unweighted call
+ *   term      fl(w_b * term): the product is never fused into the sum      + 1 per row
+ *   g_b       fl(w_b * g)                                                  + 1 per row (6 / 4 / 3 / 1 for the mse,
+ *                                                                            mae rows of the table; bce likewise + 1)
+ * The kernel does not look at the range of w: a row with w_b = 0 and a finite pred adds an exact zero to the loss
+ * and to every gradient (a NaN or infinite term times zero is NaN, as in IEEE arithmetic); a negative or non-finite
+ * weight is the caller's to refuse (fit() does).  w == NULL is the _ex call, bit for bit and launch for launch: the
+ * unweighted kernel instances are the ones _ex launches, the weighted ones are instances of their own.  Refused
+ * with XDFM_ERR_INVALID before any device call: whatever _ex refuses, and a w that is not 4-byte aligned (the
+ * message names w). */
 enum { XDFM_LINK_SIGMOID = 0, XDFM_LINK_IDENTITY = 1 };
 enum { XDFM_LOSS_BCE = 0, XDFM_LOSS_MSE = 1, XDFM_LOSS_MAE = 2 };
 size_t xdfm_head_ws_elems(int Ku, int Kv);
@@ -657,6 +676,12 @@ int xdfm_head_fwd_ex(const float* lin, const float* u, const float* wu, int Ku, 
 int xdfm_head_bwd_ex(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
                      const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
                      float* ws, int link, int loss, void* stream);
+int xdfm_head_fwd_w(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
+                    const float* bias, const float* y, int B, float* pred, float* loss_out, float* ws, int link, int loss,
+                    const float* w, void* stream);
+int xdfm_head_bwd_w(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
+                    const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
+                    float* ws, int link, int loss, const float* w, void* stream);
 
 /* ------------------------------------------------------------------ Adam (K7)
  * replaces: torch.optim.Adam.step() (deepctr/models/basemodel.py:452).  The embedding / linear tables carry

@@ -268,6 +268,12 @@ int xdfm_relu_bwd_colsum(const float* g, const float* y, long rows, int cols, lo
 // exact, so g costs 5 / 3 / 2 / 0 roundings: d and gl * s for mse, the two of pq and the last product for the sigmoid
 // link.  The term is added to the running sum; the compiler may fuse d * d into that add (one rounding fewer).  The
 // backward reads pred and y only: for the identity link pred IS z.
+//
+// With one weight per example (the WT instances; xdfm_head_fwd_w / xdfm_head_bwd_w, w [B]) the row's term and the row's g
+// are multiplied by w[b] first, each product rounded on its own (head_wmul):
+//   any link  any loss   term -> fl(w * term)   g -> fl(w * g)            one rounding more than the row above
+// Everything after g (dlin, du, dv, the column sums, dbias) and the order of every sum are those of the unweighted
+// instances; w is not range-checked here (w = 0 and a finite pred: exact zeros).
 #define HEAD_BLOCKS 128
 #define HEAD_THREADS 256
 enum { HEAD_SIGMOID = XDFM_LINK_SIGMOID, HEAD_IDENTITY = XDFM_LINK_IDENTITY };
@@ -303,6 +309,13 @@ __device__ __forceinline__ float head_g(float gl, float p, float t) {
     }
 }
 
+// fl(w * x) as a product of its own: contraction is switched off here, so the compiler cannot fold the example weight
+// into the add (or the fma) that consumes the product -- the weighted sums are sums of ROUNDED weighted terms
+__device__ __forceinline__ float head_wmul(float w, float x) {
+#pragma clang fp contract(off)
+    return w * x;
+}
+
 __device__ __forceinline__ float head_row_dot(const float* __restrict__ x, const float* __restrict__ w, int K, int lane) {
     float s = 0.f;
     for (int k = lane; k < K; k += 64) s = fmaf(x[k], w[k], s);
@@ -330,12 +343,13 @@ __device__ __forceinline__ float head_row_dot_vec(const float* __restrict__ x, c
 }
 
 // rows strided over all 16-lane groups of the grid; per-block partial loss -> part[blockIdx.x]
-template <bool VEC, int LINK, int LOSS>
+// WT: an example weight w[b] multiplies the row's term (one more rounding) before it joins the running sum
+template <bool VEC, int LINK, int LOSS, bool WT = false>
 __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(
     const float* __restrict__ lin, const float* __restrict__ u, const float* __restrict__ wu, int Ku,
     const float* __restrict__ v, const float* __restrict__ wv, int Kv, const float* __restrict__ bias,
     const float* __restrict__ y, int B, float* __restrict__ pred, float* __restrict__ part, float* __restrict__ loss,
-    unsigned* __restrict__ ticket) {
+    unsigned* __restrict__ ticket, const float* __restrict__ w = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float bv = bias ? bias[0] : 0.f;
     float acc = 0.f;
@@ -349,7 +363,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(
             const float t = y[b];
             if (sub == 0) {
                 pred[b] = p;
-                acc += head_term<LOSS>(p, t);
+                if constexpr (WT) acc += head_wmul(w[b], head_term<LOSS>(p, t));
+                else acc += head_term<LOSS>(p, t);
             }
         }
         acc += __shfl_xor(acc, 16);
@@ -363,7 +378,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(
             const float t = y[b];
             if (lane == 0) {
                 pred[b] = p;
-                acc += head_term<LOSS>(p, t);
+                if constexpr (WT) acc += head_wmul(w[b], head_term<LOSS>(p, t));
+                else acc += head_term<LOSS>(p, t);
             }
         }
     }
@@ -396,12 +412,14 @@ __global__ __launch_bounds__(HEAD_BLOCKS) void head_fwd_finish_kernel(const floa
 
 // g_b = gloss * dLOSS/dz (head_g);  dlin_b = g_b;  du[b][k] = g_b wu[k];  dv likewise;
 // per-block partials of dwu[k] = sum_b g_b u[b][k], dwv[k], dbias = sum_b g_b  -> part[blk][Ku + Kv + 1]
-template <int LINK, int LOSS>
+// WT: g_b = fl(w[b] * head_g) -- the weighted row gradient, everything after it unchanged
+template <int LINK, int LOSS, bool WT = false>
 __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(
     const float* __restrict__ pred, const float* __restrict__ y, const float* __restrict__ gloss,
     const float* __restrict__ u, const float* __restrict__ wu, int Ku, const float* __restrict__ v,
     const float* __restrict__ wv, int Kv, int B, float* __restrict__ dlin, float* __restrict__ du,
-    float* __restrict__ dv, float* __restrict__ part, float* __restrict__ grads, unsigned* __restrict__ ticket) {
+    float* __restrict__ dv, float* __restrict__ part, float* __restrict__ grads, unsigned* __restrict__ ticket,
+    const float* __restrict__ w = nullptr) {
     extern __shared__ float sm[];                 // [4 waves][Ku + Kv + 1]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int KT = Ku + Kv + 1;
@@ -411,7 +429,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(
     float gsum = 0.f;
     for (int b = blockIdx.x * 4 + wave; b < B; b += HEAD_BLOCKS * 4) {
         const float p = pred[b], t = y[b];
-        const float g = head_g<LINK, LOSS>(gl, p, t);
+        float g = head_g<LINK, LOSS>(gl, p, t);
+        if constexpr (WT) g = head_wmul(w[b], g);
         if (lane == 0 && dlin) dlin[b] = g;
         gsum += g;
         if (u) {
@@ -441,12 +460,13 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(
 // loads / stores issued back to back; every lane keeps the partial column sums of its own columns in registers
 // (reduced over the wave's 4 row groups by shuffles at the end, over the 4 waves through LDS) -- the scalar
 // kernel above walks its rows one after the other with an LDS read-modify-write per element
-template <int LINK, int LOSS>
+template <int LINK, int LOSS, bool WT = false>
 __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_vec_kernel(
     const float* __restrict__ pred, const float* __restrict__ y, const float* __restrict__ gloss,
     const float* __restrict__ u, const float* __restrict__ wu, int Ku, const float* __restrict__ v,
     const float* __restrict__ wv, int Kv, int B, float* __restrict__ dlin, float* __restrict__ du,
-    float* __restrict__ dv, float* __restrict__ part, float* __restrict__ grads, unsigned* __restrict__ ticket) {
+    float* __restrict__ dv, float* __restrict__ part, float* __restrict__ grads, unsigned* __restrict__ ticket,
+    const float* __restrict__ w = nullptr) {
     extern __shared__ float sm[];                 // [4 waves][Ku + Kv + 1]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane & 15, grp = lane >> 4;
@@ -464,7 +484,8 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_vec_kernel(
     float gsum = 0.f;
     for (int b = (blockIdx.x * 4 + wave) * 4 + grp; b < B; b += HEAD_BLOCKS * 16) {
         const float p = pred[b], t = y[b];
-        const float g = head_g<LINK, LOSS>(gl, p, t);
+        float g = head_g<LINK, LOSS>(gl, p, t);
+        if constexpr (WT) g = head_wmul(w[b], g);
         if (sub == 0) { if (dlin) dlin[b] = g; gsum += g; }
         float4 xu[8], xv[8];
 #pragma unroll
@@ -544,9 +565,10 @@ static int head_mode_check(const char* what, int link, int loss) {
         default: CALL(HEAD_IDENTITY, HEAD_MAE); break;                                   \
     }
 
-int xdfm_head_fwd_ex(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
-                     const float* bias, const float* y, int B, float* pred, float* loss_out, float* ws, int link, int loss,
-                     void* stream) {
+// w == nullptr: the unweighted instances, launched exactly as before the weights existed
+static int head_fwd_launch(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
+                           const float* bias, const float* y, int B, float* pred, float* loss_out, float* ws, int link, int loss,
+                           const float* w, void* stream) {
     XDFM_REQUIRE(y && pred && loss_out && ws && B > 0, "head_fwd: bad arguments");
     XDFM_REQUIRE((!u || (wu && Ku > 0)) && (!v || (wv && Kv > 0)) && Ku >= 0 && Kv >= 0, "head_fwd: bad operand shapes");
     if (int rc = head_mode_check("head_fwd", link, loss)) return rc;
@@ -555,17 +577,30 @@ int xdfm_head_fwd_ex(const float* lin, const float* u, const float* wu, int Ku, 
     const bool vec = ku % 4 == 0 && kv % 4 == 0 && ku <= 512 && kv <= 512 &&
                      ((((size_t)u) | ((size_t)v) | ((size_t)wu) | ((size_t)wv)) & 15) == 0;
     unsigned* ticket = xdfm_ticket(TK_HEAD_FWD);
+#define HEAD_FWD_GO(VEC, LINK, LOSS, WT)                                                                                     \
+    hipLaunchKernelGGL((head_fwd_kernel<VEC, LINK, LOSS, WT>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), 0, st, lin, u, wu, ku,  \
+                       v, wv, kv, bias, y, B, pred, ws, loss_out, ticket, w)
 #define HEAD_FWD_LAUNCH(LINK, LOSS)                                                                                          \
-    if (vec)                                                                                                                 \
-        hipLaunchKernelGGL((head_fwd_kernel<true, LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), 0, st, lin, u, wu, ku, \
-                           v, wv, kv, bias, y, B, pred, ws, loss_out, ticket);                                               \
-    else                                                                                                                     \
-        hipLaunchKernelGGL((head_fwd_kernel<false, LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), 0, st, lin, u, wu,   \
-                           ku, v, wv, kv, bias, y, B, pred, ws, loss_out, ticket)
+    if (w) { if (vec) HEAD_FWD_GO(true, LINK, LOSS, true); else HEAD_FWD_GO(false, LINK, LOSS, true); }                      \
+    else   { if (vec) HEAD_FWD_GO(true, LINK, LOSS, false); else HEAD_FWD_GO(false, LINK, LOSS, false); }
     HEAD_DISPATCH(HEAD_FWD_LAUNCH)
 #undef HEAD_FWD_LAUNCH
+#undef HEAD_FWD_GO
     if (!ticket) hipLaunchKernelGGL(head_fwd_finish_kernel, dim3(1), dim3(HEAD_BLOCKS), 0, st, ws, loss_out);
     return xdfm_check_launch("head_fwd");
+}
+
+int xdfm_head_fwd_ex(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
+                     const float* bias, const float* y, int B, float* pred, float* loss_out, float* ws, int link, int loss,
+                     void* stream) {
+    return head_fwd_launch(lin, u, wu, Ku, v, wv, Kv, bias, y, B, pred, loss_out, ws, link, loss, nullptr, stream);
+}
+
+int xdfm_head_fwd_w(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
+                    const float* bias, const float* y, int B, float* pred, float* loss_out, float* ws, int link, int loss,
+                    const float* w, void* stream) {
+    XDFM_REQUIRE((((size_t)w) & 3) == 0, "head_fwd_w: w=%p is not 4-byte aligned", (const void*)w);
+    return head_fwd_launch(lin, u, wu, Ku, v, wv, Kv, bias, y, B, pred, loss_out, ws, link, loss, w, stream);
 }
 
 int xdfm_head_fwd(const float* lin, const float* u, const float* wu, int Ku, const float* v, const float* wv, int Kv,
@@ -574,9 +609,9 @@ int xdfm_head_fwd(const float* lin, const float* u, const float* wu, int Ku, con
 }
 
 /* grads: [Ku + Kv + 1] = dwu | dwv | dbias */
-int xdfm_head_bwd_ex(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
-                     const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
-                     float* ws, int link, int loss, void* stream) {
+static int head_bwd_launch(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
+                           const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
+                           float* ws, int link, int loss, const float* w, void* stream) {
     XDFM_REQUIRE(pred && y && gloss && grads && ws && B > 0, "head_bwd: bad arguments");
     XDFM_REQUIRE((!u || (wu && du && Ku > 0)) && (!v || (wv && dv && Kv > 0)), "head_bwd: bad operand shapes");
     const int ku = u ? Ku : 0, kv = v ? Kv : 0, KT = ku + kv + 1;
@@ -587,17 +622,30 @@ int xdfm_head_bwd_ex(const float* pred, const float* y, const float* gloss, cons
     const bool vec = ku % 4 == 0 && kv % 4 == 0 && ku <= 512 && kv <= 512 &&
                      ((((size_t)u) | ((size_t)v) | ((size_t)wu) | ((size_t)wv) | ((size_t)du) | ((size_t)dv)) & 15) == 0;
     unsigned* ticket = xdfm_ticket(TK_HEAD_BWD);
+#define HEAD_BWD_GO(KERNEL, LINK, LOSS, WT)                                                                                  \
+    hipLaunchKernelGGL((KERNEL<LINK, LOSS, WT>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), lds, st, pred, y, gloss, u, wu, ku,  \
+                       v, wv, kv, B, dlin, du, dv, ws, grads, ticket, w)
 #define HEAD_BWD_LAUNCH(LINK, LOSS)                                                                                          \
-    if (vec)                                                                                                                 \
-        hipLaunchKernelGGL((head_bwd_vec_kernel<LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), lds, st, pred, y, gloss, \
-                           u, wu, ku, v, wv, kv, B, dlin, du, dv, ws, grads, ticket);                                        \
-    else                                                                                                                     \
-        hipLaunchKernelGGL((head_bwd_kernel<LINK, LOSS>), dim3(HEAD_BLOCKS), dim3(HEAD_THREADS), lds, st, pred, y, gloss, u,  \
-                           wu, ku, v, wv, kv, B, dlin, du, dv, ws, grads, ticket)
+    if (w) { if (vec) HEAD_BWD_GO(head_bwd_vec_kernel, LINK, LOSS, true); else HEAD_BWD_GO(head_bwd_kernel, LINK, LOSS, true); }   \
+    else   { if (vec) HEAD_BWD_GO(head_bwd_vec_kernel, LINK, LOSS, false); else HEAD_BWD_GO(head_bwd_kernel, LINK, LOSS, false); }
     HEAD_DISPATCH(HEAD_BWD_LAUNCH)
 #undef HEAD_BWD_LAUNCH
+#undef HEAD_BWD_GO
     if (!ticket) hipLaunchKernelGGL(head_bwd_finish_kernel, dim3(ceil_div(KT, 256)), dim3(256), 0, st, ws, KT, grads);
     return xdfm_check_launch("head_bwd");
+}
+
+int xdfm_head_bwd_ex(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
+                     const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
+                     float* ws, int link, int loss, void* stream) {
+    return head_bwd_launch(pred, y, gloss, u, wu, Ku, v, wv, Kv, B, dlin, du, dv, grads, ws, link, loss, nullptr, stream);
+}
+
+int xdfm_head_bwd_w(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,
+                    const float* v, const float* wv, int Kv, int B, float* dlin, float* du, float* dv, float* grads,
+                    float* ws, int link, int loss, const float* w, void* stream) {
+    XDFM_REQUIRE((((size_t)w) & 3) == 0, "head_bwd_w: w=%p is not 4-byte aligned", (const void*)w);
+    return head_bwd_launch(pred, y, gloss, u, wu, Ku, v, wv, Kv, B, dlin, du, dv, grads, ws, link, loss, w, stream);
 }
 
 int xdfm_head_bwd(const float* pred, const float* y, const float* gloss, const float* u, const float* wu, int Ku,

@@ -77,6 +77,8 @@ SIGNATURES = {
     "xdfm_head_bwd": (c_int, [P, P, P, P, P, c_int, P, P, c_int, c_int, P, P, P, P, P, P]),
     "xdfm_head_fwd_ex": (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, P, P, P, c_int, c_int, P]),
     "xdfm_head_bwd_ex": (c_int, [P, P, P, P, P, c_int, P, P, c_int, c_int, P, P, P, P, P, c_int, c_int, P]),
+    "xdfm_head_fwd_w": (c_int, [P, P, P, c_int, P, P, c_int, P, P, c_int, P, P, P, c_int, c_int, P, P]),
+    "xdfm_head_bwd_w": (c_int, [P, P, P, P, P, c_int, P, P, c_int, c_int, P, P, P, P, P, c_int, c_int, P, P]),
     "xdfm_adam_step_ws_elems": (c_size_t, [c_int]),
     "xdfm_adam_step": (c_int, [P, c_int, c_double, c_double, c_double, c_double, P, P, P]),
     "xdfm_adam_step_lr": (c_int, [P, c_int, c_double, P, c_double, c_double, c_double, P, P, P]),

@@ -12,7 +12,8 @@ Guards:
     stack (ROCm 7.2, gfx950) a memset node is not ordered against its neighbouring kernel nodes
     (tools/graph_memset_probe.py: ATen's sum(0) inside a graph is wrong in 3 of 4 replays).  The library
     itself issues no memset on this path and `ops.Dense` keeps ATen's semaphore memset out of the step;
-  * the graph is keyed on the batch shape and on a signature of everything that is baked into it
+  * the graph is keyed on the batch shape, on whether the step takes example weights (a static buffer beside the
+    inputs' then, refilled before every replay) and on a signature of everything that is baked into it
     (parameter storage, requires_grad pattern, optimizer hyper-parameters, loss function, train flags); a
     change re-captures;
   * anything unexpected (capture error, unsupported optimizer, row-parallel run, profiling hooks)
@@ -44,10 +45,11 @@ def census(graph: "torch.cuda.CUDAGraph"):
 
 
 class _Entry(object):
-    __slots__ = ("sig", "eager", "graph", "sx", "sy", "out", "nodes", "extra", "log", "grads")
+    __slots__ = ("sig", "eager", "graph", "sx", "sy", "sw", "out", "nodes", "extra", "log", "grads")
 
     def __init__(self, sig):
         self.sig, self.eager, self.graph, self.sx, self.sy, self.out, self.nodes = sig, 0, None, None, None, None, 0
+        self.sw = None          # static example weights of a step captured with them (the key says which kind this is)
         # what the model's `_loss_forward` left in `_step_extra` / `_step_log` during the capture: tensors of THIS graph
         self.extra = self.log = None
         # row-parallel: (parameter, gradient tensor) as the captured first half left them -- the eager second half reads
@@ -87,9 +89,10 @@ class GraphedStep(object):
         return (id(opt), getattr(opt, "generation", 0), hyper, ptrs, req, id(m.loss_func), m.training, id(m.aux_loss),
                 _lib.get_option("cin_math"))
 
-    def eligible(self, x, y):
+    def eligible(self, x, y, sw=None):
         m = self.model
         if self.disabled or not (x.is_cuda and y.is_cuda) or ops.PROFILE is not None or not torch.is_grad_enabled() \
+                or not (sw is None or (sw.is_cuda and sw.dtype == torch.float32)) \
                 or not getattr(m, "_optim_capturable", False):
             return False
         dp = xdist.current()
@@ -102,15 +105,15 @@ class GraphedStep(object):
         n = dp._n_global
         return n is not None and n % dp.world == 0 and x.shape[0] == n // dp.world
 
-    def __call__(self, x, y):
+    def __call__(self, x, y, sw=None):
         m = self.model
-        if not self.eligible(x, y):
-            return m._train_step_eager(x, y)
+        if not self.eligible(x, y, sw):
+            return m._train_step_eager(x, y, sw)
         if hasattr(m.optim, "sync_lr"):
             m.optim.sync_lr()              # outside any capture: the device scalar K7 reads follows param_groups["lr"]
         dp = xdist.current()
         key = (tuple(x.shape), tuple(y.shape), x.dtype, y.dtype, x.device.index, self._signature(),
-               None if dp is None else dp.world)
+               None if dp is None else dp.world, None if sw is None else tuple(sw.shape))
         ent = self.entries.get(key)
         if ent is None:
             if len(self.entries) >= MAX_GRAPHS:             # each graph owns the activations of one step
@@ -119,11 +122,13 @@ class GraphedStep(object):
         if ent.graph is None:
             if ent.eager < EAGER_STEPS_BEFORE_CAPTURE:
                 ent.eager += 1
-                return self._eager_on_side_stream(x, y)
-            if not self._capture(ent, x, y):
-                return m._train_step_eager(x, y)
+                return self._eager_on_side_stream(x, y, sw)
+            if not self._capture(ent, x, y, sw):
+                return m._train_step_eager(x, y, sw)
         ent.sx.copy_(x)
         ent.sy.copy_(y)
+        if sw is not None:
+            ent.sw.copy_(sw)
         if dp is None and hasattr(m.optim, "note_replay"):
             m.optim.note_replay()          # deferred table update: periodic flush, step count (the step's Python does not run)
         ent.graph.replay()
@@ -141,7 +146,7 @@ class GraphedStep(object):
             return m._split_step_second(y_pred, loss, stash, m._l2_fusion())
         return ent.out
 
-    def _eager_on_side_stream(self, x, y):
+    def _eager_on_side_stream(self, x, y, sw=None):
         """The warm-up steps run on the stream the capture will use (the pattern torch documents for whole-step
         capture): autograd then creates the parameters' AccumulateGrad nodes on that stream, never on the
         legacy default stream, which must not take part in a capture."""
@@ -150,31 +155,32 @@ class GraphedStep(object):
         cur = torch.cuda.current_stream(x.device)
         self.stream.wait_stream(cur)
         with torch.cuda.stream(self.stream):
-            out = self.model._train_step_eager(x, y)
+            out = self.model._train_step_eager(x, y, sw)
         cur.wait_stream(self.stream)
         for t in out:
             t.record_stream(cur)
         return out
 
-    def _capture(self, ent, x, y):
+    def _capture(self, ent, x, y, sw=None):
         m = self.model
         gc.collect()                       # destroy unreachable graphs / pools now, not inside the capture
         gc_was_enabled = gc.isenabled()
         gc.disable()
         try:
             ent.sx, ent.sy = x.clone(), y.clone()
+            ent.sw = None if sw is None else sw.clone()
             torch.cuda.current_stream().synchronize()
             g = torch.cuda.CUDAGraph(keep_graph=True)
             if self.stream is None:
                 self.stream = torch.cuda.Stream(device=x.device)
             if xdist.current() is None:
                 with torch.cuda.graph(g, stream=self.stream):
-                    out = m._train_step_eager(ent.sx, ent.sy)
+                    out = m._train_step_eager(ent.sx, ent.sy, ent.sw)
             else:
                 # thread_local: the process group's watchdog thread polls events while we capture; it must not be
                 # able to invalidate the capture (nothing it touches is part of it)
                 with torch.cuda.graph(g, stream=self.stream, capture_error_mode="thread_local"):
-                    out = m._split_step_first(ent.sx, ent.sy)
+                    out = m._split_step_first(ent.sx, ent.sy, ent.sw)
             n, n_memset, n_other = census(g)
             if n_memset or n_other:
                 raise RuntimeError("captured train step holds %d memset and %d unexpected nodes of %d"
@@ -188,7 +194,7 @@ class GraphedStep(object):
         except Exception as exc:      # noqa: BLE001 -- any failure means: keep training eagerly
             warnings.warn("xdfm: HIP-graph capture of the train step failed (%s); continuing with eager launches" % (exc,))
             self.disabled = True
-            ent.graph = ent.sx = ent.sy = ent.out = ent.extra = ent.log = ent.grads = None
+            ent.graph = ent.sx = ent.sy = ent.sw = ent.out = ent.extra = ent.log = ent.grads = None
             if m._plan is not None:
                 m._plan.reg_defer = None
             return False

@@ -146,6 +146,43 @@ class Linear(nn.Module):
         return lin
 
 
+def example_weights(y, sample_weight=None, class_weight=None, task="binary"):
+    """The weight vector of `fit(sample_weight=, class_weight=)`: float32 [n], row i the weight of example i, or None when
+    neither is given.  Checked once, on the host: `sample_weight` is one finite, non-negative weight per example (1-D or
+    [n,1]); `class_weight` is {0: a, 1: b} with finite, non-negative values, for task 'binary' with labels that are
+    exactly 0 or 1.  The effective weight is sample_weight * class_weight[y], formed here in float32 -- the kernels see
+    one vector and no classes.  Anything else is a ValueError."""
+    if sample_weight is None and class_weight is None:
+        return None
+    labels = np.asarray(y)
+    n = labels.shape[0]
+    w = np.ones((n,), dtype=np.float32)
+    if sample_weight is not None:
+        sw = np.asarray(sample_weight)
+        if sw.dtype.kind not in "fiub" or not (sw.ndim == 1 or (sw.ndim == 2 and sw.shape[1] == 1)):
+            raise ValueError("sample_weight must be a numeric 1-D array (or [n,1]), got dtype %s shape %s" % (sw.dtype, sw.shape))
+        sw = sw.reshape(-1)
+        if sw.shape[0] != n:
+            raise ValueError("sample_weight has %d entries for %d examples" % (sw.shape[0], n))
+        with np.errstate(over="ignore"):               # a weight beyond fp32 becomes inf and is refused below
+            w = sw.astype(np.float32)
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("sample_weight must be finite and non-negative (also after the cast to float32)")
+    if class_weight is not None:
+        if task != "binary":
+            raise ValueError("class_weight needs task='binary', the model's task is %r" % (task,))
+        if not isinstance(class_weight, dict) or set(class_weight.keys()) != {0, 1}:
+            raise ValueError("class_weight must be a dict {0: weight, 1: weight}, got %r" % (class_weight,))
+        cw = np.asarray([class_weight[0], class_weight[1]], dtype=np.float32)
+        if not np.all(np.isfinite(cw)) or np.any(cw < 0):
+            raise ValueError("class_weight values must be finite and non-negative, got %r" % (class_weight,))
+        flat = labels.reshape(-1)
+        if flat.shape[0] != n or not np.all((flat == 0) | (flat == 1)):
+            raise ValueError("class_weight needs one label per example, each exactly 0 or 1")
+        w = w * cw[flat.astype(np.int64)]
+    return np.ascontiguousarray(w, dtype=np.float32)
+
+
 class BaseModel(nn.Module):
     _VARLEN = True      # the model's input stage pools VarLenSparseFeat columns (K1v); xDeepFMPro's does not
 
@@ -436,19 +473,26 @@ class BaseModel(nn.Module):
             total = torch.zeros((1,), device=self.device)
         return total.reshape(1)
 
-    def train_on_batch(self, x, y):
+    def train_on_batch(self, x, y, sample_weight=None):
         """One optimisation step = the body of the reference's batch loop (basemodel.py:245-262):
         forward, BCE(sum) + L2 (+ aux), backward, optimizer step.  Returns (y_pred, data_loss,
         total_loss) as device tensors -- no host synchronisation.  On a GPU, from the third step of a
         batch shape on, the step is replayed from a captured HIP graph (xdfm_amd/graphstep.py); the
-        returned tensors are then the graph's static outputs, valid until the next call."""
+        returned tensors are then the graph's static outputs, valid until the next call.
+        `sample_weight` ([B] or [B,1] float32 on the device of `y`, or None): the data loss becomes
+        sum_b w_b loss(pred_b, y_b) (the native head takes the vector, K8); the L2 term is not weighted."""
         step = self.__dict__.get("_graphed_step")
         if step is None:
             from .graphstep import GraphedStep
             step = self.__dict__["_graphed_step"] = GraphedStep(self)
-        return step(x, y)
+        if sample_weight is None:
+            return step(x, y)
+        if sample_weight.numel() != x.shape[0] or sample_weight.dim() > 2:
+            raise ValueError("sample_weight must hold one weight per row of x ([B] or [B,1]), got shape %s"
+                             % (tuple(sample_weight.shape),))
+        return step(x, y, sample_weight)
 
-    def _fused_head(self, x, y):
+    def _fused_head(self, x, y, sw=None):
         """(y_pred, summed data loss) through one launch (ops.Head) when the model is of the xDeepFM family (it has
         `head_inputs`) and its task and compiled loss have a native head (ops.head_mode: binary / regression with
         binary_crossentropy / mse / mae, except regression + binary_crossentropy); None otherwise."""
@@ -461,11 +505,14 @@ class BaseModel(nn.Module):
         lin, cin_out, dnn_out = self.head_inputs(x)
         return ops.Head.apply(y, out.bias if out.use_bias else None, lin,
                               cin_out, self.cin_linear.weight if cin_out is not None else None,
-                              dnn_out, self.dnn_linear.weight if dnn_out is not None else None, *mode)
+                              dnn_out, self.dnn_linear.weight if dnn_out is not None else None, *mode,
+                              *(() if sw is None else (sw.float(),)))
 
-    def _loss_forward(self, x, y):
-        """(y_pred, data loss): forward + loss of the reference's batch loop (basemodel.py:250-254)."""
-        head = self._fused_head(x, y)
+    def _loss_forward(self, x, y, sw=None):
+        """(y_pred, data loss): forward + loss of the reference's batch loop (basemodel.py:250-254).  With example
+        weights `sw` the loss is sum_b sw_b loss(pred_b, y_b): by the native head, or (stock tail) by the loss function
+        with reduction='none'."""
+        head = self._fused_head(x, y) if sw is None else self._fused_head(x, y, sw)
         if head is not None:
             y_pred, loss = head
             return y_pred, loss.reshape(())
@@ -473,7 +520,11 @@ class BaseModel(nn.Module):
         loss_func = self.loss_func
         if isinstance(loss_func, list):
             assert len(loss_func) == self.num_tasks, "the length of `loss_func` should be equal with `self.num_tasks`"
+            if sw is not None:
+                raise NotImplementedError("sample_weight with a list of losses")
             loss = sum(loss_func[i](y_pred[:, i], y[:, i], reduction='sum') for i in range(self.num_tasks))
+        elif sw is not None:
+            loss = (sw.reshape(-1).to(y_pred.dtype) * loss_func(y_pred.reshape(-1), y.reshape(-1), reduction='none')).sum()
         else:
             loss = loss_func(y_pred, y.squeeze(), reduction='sum')
         return y_pred, loss
@@ -521,16 +572,16 @@ class BaseModel(nn.Module):
             hit = self.__dict__["_unit_grad_cache"] = (key, torch.ones_like(loss))
         return hit[1]
 
-    def _split_step_first(self, x, y):
+    def _split_step_first(self, x, y, sw=None):
         with self._own_step_scope():
-            return self._split_step_first_body(x, y)
+            return self._split_step_first_body(x, y, sw)
 
-    def _split_step_first_body(self, x, y):
+    def _split_step_first_body(self, x, y, sw=None):
         self.optim.zero_grad()
         plan = self._gather_plan()
         plan.stash = []
         try:
-            y_pred, loss = self._loss_forward(x, y)
+            y_pred, loss = self._loss_forward(x, y) if sw is None else self._loss_forward(x, y, sw)
             root = loss if self._aux_unset else loss + self.aux_loss
             root = self._with_step_extra(root)
             root.backward(self._unit_grad(root))
@@ -570,20 +621,20 @@ class BaseModel(nn.Module):
         self._gather_plan()
         return bool(getattr(self, "_fused_linear", False))
 
-    def _train_step_eager(self, x, y):
+    def _train_step_eager(self, x, y, sw=None):
         with self._own_step_scope():
-            out = self._train_step_eager_body(x, y)
+            out = self._train_step_eager_body(x, y, sw)
         self._drop_table_grads()
         return out
 
-    def _train_step_eager_body(self, x, y):
+    def _train_step_eager_body(self, x, y, sw=None):
         dp = xdist.current()
         fuse = self._l2_fusion()
         if self._can_split_step(dp, fuse):
-            y_pred, loss, stash = self._split_step_first(x, y)
+            y_pred, loss, stash = self._split_step_first(x, y, sw)
             return self._split_step_second(y_pred, loss, stash, fuse)
         self.optim.zero_grad()
-        y_pred, loss = self._loss_forward(x, y)
+        y_pred, loss = self._loss_forward(x, y) if sw is None else self._loss_forward(x, y, sw)
         if fuse is not None:
             # gradient and value of the L2 term come from K7 (added after the gradient all-reduce when row-parallel:
             # the term is identical on every replica and must count once)
@@ -727,11 +778,15 @@ class BaseModel(nn.Module):
 
     # ------------------------------------------------------------------ fit / evaluate / predict
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, initial_epoch=0, validation_split=0.,
-            validation_data=None, shuffle=True, callbacks=None):
+            validation_data=None, shuffle=True, callbacks=None, sample_weight=None, class_weight=None):
         """Training loop with the observable behaviour of basemodel.py:137-309: same batch order for a
-        given torch seed (the stock DataLoader draws it), BCE(sum) + L2, History keys, callbacks."""
+        given torch seed (the stock DataLoader draws it), BCE(sum) + L2, History keys, callbacks.
+        `sample_weight` / `class_weight` (see `example_weights`): the data loss of a step is sum_b w_b loss_b.  The
+        History `loss` stays (sum of weighted data loss + L2) / sample_num -- the reference's normaliser, not sum(w).
+        Training metrics, `evaluate`, `predict` and a third item of `validation_data` take no weights."""
         if isinstance(x, dict):
             x = [x[name] for name in self.feature_index]
+        w_all = example_weights(y, sample_weight, class_weight, getattr(self.out, "task", None))
         do_validation = False
         val_x, val_y = [], []
         if validation_data:
@@ -752,8 +807,11 @@ class BaseModel(nn.Module):
             split_at = int(n0 * (1. - validation_split))
             x, val_x = _slice(x, 0, split_at), _slice(x, split_at)
             y, val_y = _slice(y, 0, split_at), _slice(y, split_at)
+            if w_all is not None:
+                w_all = w_all[:split_at]       # the validation part's weights are dropped: validation is unweighted
 
         X_all, Y_all = self._resident(x, y)
+        W_all = None if w_all is None else torch.from_numpy(w_all).to(X_all.device)    # resident with X / Y
         if batch_size is None:
             batch_size = 256
         self.train()
@@ -791,13 +849,18 @@ class BaseModel(nn.Module):
                 for start in (bar if bar is not None else it):
                     xb = self._rows(X_all, order, start, start + global_bs)
                     yb = self._rows(Y_all, order, start, start + global_bs)
+                    wb = None if W_all is None else self._rows(W_all, order, start, start + global_bs)
                     if dp is not None:
                         self._global_batch_labels(yb)
                         xb, yb = dp.shard(xb), dp.shard(yb)
+                        wb = None if wb is None else dp.shard(wb)
                         self.__dict__["_row_weight"] = dp.row_weight()
                     xd = xb.to(self.device)
                     yd = yb.to(self.device)
-                    y_pred, loss, total_loss = self.train_on_batch(xd, yd)
+                    if wb is None:
+                        y_pred, loss, total_loss = self.train_on_batch(xd, yd)
+                    else:
+                        y_pred, loss, total_loss = self.train_on_batch(xd, yd, wb.to(self.device))
                     if dp is not None and dp.row_weight() == 0.0:
                         # stand-in row of a rank without rows in this (tail) batch: contributes nothing
                         total_loss = total_loss - loss

@@ -1475,10 +1475,13 @@ class Head(torch.autograd.Function):
     LOSS(pred, y): cin_linear / dnn_linear + logit sum (deepctr/models/xdeepfm.py:95-105) + PredictionLayer
     (core.py:150-160) + the summed loss of the batch loop (basemodel.py:254; F.binary_cross_entropy, F.mse_loss or
     F.l1_loss with reduction='sum'), two launches each way (K8).  `link` / `loss` are the pairs of head_mode().  `pred`
-    is returned for metrics and is not differentiable here (the model's train step differentiates the loss only)."""
+    is returned for metrics and is not differentiable here (the model's train step differentiates the loss only).
+    `w` ([B] or [B,1] float32 on the device, or None): one weight per example, loss = sum w_b LOSS(pred_b, y_b) through
+    xdfm_head_fwd_w / _bwd_w; it is kept for the backward and has no gradient.  Without it the _ex entry points run, as
+    they always did."""
 
     @staticmethod
-    def forward(ctx, y, bias, lin, u, wu, v, wv, link=LINK_SIGMOID, loss=LOSS_BCE):
+    def forward(ctx, y, bias, lin, u, wu, v, wv, link=LINK_SIGMOID, loss=LOSS_BCE, w=None):
         lib = _lib.load()
         yv = y.reshape(-1).contiguous()
         B = yv.numel()
@@ -1493,12 +1496,21 @@ class Head(torch.autograd.Function):
         for t, k in ((u, Ku), (v, Kv)):
             if t is not None and (t.dim() != 2 or t.shape[0] != B):
                 raise ValueError("xdfm head: operands must be [B, K]")
+        if w is not None:
+            if w.dtype != torch.float32 or w.device != dev or w.numel() != B or w.dim() > 2:
+                raise ValueError("xdfm head: w must be a float32 [B] or [B,1] tensor on the device of y")
+            w = w.reshape(-1).contiguous()
         pred = torch.empty(B, dtype=torch.float32, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.xdfm_head_ws_elems(Ku, Kv), dtype=torch.float32, device=dev)
-        _lib.check(lib.xdfm_head_fwd_ex(_ptr(linv), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, _ptr(bias), _ptr(yv), B,
-                                        _ptr(pred), _ptr(out), _ptr(ws), int(link), int(loss), _stream()), "head_fwd")
-        ctx.save_for_backward(pred, yv, u, wu, v, wv)
+        if w is None:
+            _lib.check(lib.xdfm_head_fwd_ex(_ptr(linv), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, _ptr(bias), _ptr(yv), B,
+                                            _ptr(pred), _ptr(out), _ptr(ws), int(link), int(loss), _stream()), "head_fwd")
+        else:
+            _lib.check(lib.xdfm_head_fwd_w(_ptr(linv), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, _ptr(bias), _ptr(yv), B,
+                                           _ptr(pred), _ptr(out), _ptr(ws), int(link), int(loss), _ptr(w), _stream()),
+                       "head_fwd_w")
+        ctx.save_for_backward(pred, yv, u, wu, v, wv, w)
         ctx.cfg = (bias is not None, lin is not None, tuple(lin.shape) if lin is not None else None, Ku, Kv)
         ctx.mode = (int(link), int(loss))
         ctx.mark_non_differentiable(pred)
@@ -1508,9 +1520,9 @@ class Head(torch.autograd.Function):
     @staticmethod
     def backward(ctx, _gpred, gloss):
         if gloss is None:
-            return (None,) * 9
+            return (None,) * 10
         lib = _lib.load()
-        pred, yv, u, wu, v, wv = ctx.saved_tensors
+        pred, yv, u, wu, v, wv, w = ctx.saved_tensors
         has_bias, has_lin, lin_shape, Ku, Kv = ctx.cfg
         B = pred.numel()
         dev = pred.device
@@ -1521,13 +1533,18 @@ class Head(torch.autograd.Function):
         grads = torch.empty(Ku + Kv + 1, **f32)
         ws = torch.empty(lib.xdfm_head_ws_elems(Ku, Kv), **f32)
         gl = gloss.reshape(1).contiguous()
-        _lib.check(lib.xdfm_head_bwd_ex(_ptr(pred), _ptr(yv), _ptr(gl), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, B,
-                                        _ptr(dlin), _ptr(du), _ptr(dv), _ptr(grads), _ptr(ws), ctx.mode[0], ctx.mode[1],
-                                        _stream()), "head_bwd")
+        if w is None:
+            _lib.check(lib.xdfm_head_bwd_ex(_ptr(pred), _ptr(yv), _ptr(gl), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, B,
+                                            _ptr(dlin), _ptr(du), _ptr(dv), _ptr(grads), _ptr(ws), ctx.mode[0], ctx.mode[1],
+                                            _stream()), "head_bwd")
+        else:
+            _lib.check(lib.xdfm_head_bwd_w(_ptr(pred), _ptr(yv), _ptr(gl), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, B,
+                                           _ptr(dlin), _ptr(du), _ptr(dv), _ptr(grads), _ptr(ws), ctx.mode[0], ctx.mode[1],
+                                           _ptr(w), _stream()), "head_bwd_w")
         return (None, grads[Ku + Kv:Ku + Kv + 1] if has_bias else None,
                 dlin.view(lin_shape) if has_lin else None,
                 du, grads[:Ku].view(1, Ku) if u is not None else None,
-                dv, grads[Ku:Ku + Kv].view(1, Kv) if v is not None else None, None, None)
+                dv, grads[Ku:Ku + Kv].view(1, Kv) if v is not None else None, None, None, None)
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -416,7 +416,11 @@ class BaseModelSFG(BaseModel):
         that row adds nothing to the SFG term either."""
         return float(self.__dict__.get("_row_weight", 1.0))
 
-    def train_on_batch(self, x, y):
+    def train_on_batch(self, x, y, sample_weight=None):
+        if sample_weight is not None:
+            # the SFG term has a normaliser of its own (the positives of the batch): what a weight means there is undecided
+            raise NotImplementedError("sample_weight is not supported by %s: its SFG term is normalised on its own; "
+                                      "train it without example weights" % type(self).__name__)
         self._sfg_bind_normaliser(x, y)
         try:
             return super().train_on_batch(x, y)

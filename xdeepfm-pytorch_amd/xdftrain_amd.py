@@ -55,6 +55,11 @@ SCRIPT_DEFAULTS = {
 }
 
 
+def _class_weight(args):
+    cw = getattr(args, "class_weight", None)
+    return None if cw is None else {0: float(cw[0]), 1: float(cw[1])}
+
+
 def parse_args(argv=None, model=None, script=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--data_path", type=str, default=None)
@@ -88,6 +93,9 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--dnn_dropout", type=float, default=0.0)
     p.add_argument("--learning_rate", type=float, default=0.001)
     p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adagrad", "sgd", "rmsprop"])
+    p.add_argument("--class_weight", type=float, nargs=2, default=None, metavar=("W0", "W1"),
+                   help="weights of the negative and the positive examples in the training loss, e.g. 1 4 for a log whose "
+                        "negatives were down-sampled (fit(class_weight={0: W0, 1: W1})); default: none")
     p.add_argument("--epochs", type=int, default=None)
     p.add_argument("--batch_size", type=int, default=None)
     p.add_argument("--pred_batch_size", type=int, default=None)
@@ -300,7 +308,8 @@ def main(argv=None, model=None, script=None):
     config = {k: (list(v) if isinstance(v, tuple) else v) for k, v in vars(args).items()}
     if final:
         hist = model.fit({k: xtr[k] for k in names}, train_t["label"].reshape(-1, 1), batch_size=args.batch_size,
-                         epochs=args.epochs, verbose=args.verbose, validation_split=0.0, shuffle=True)
+                         epochs=args.epochs, verbose=args.verbose, validation_split=0.0, shuffle=True,
+                         class_weight=_class_weight(args))
         if rank == 0:
             history = {k: [float(v) for v in vals] for k, vals in hist.history.items()}
             torch.save(model.state_dict(), os.path.join(args.out_dir, stem + "_full_weights.pth"))
@@ -318,7 +327,7 @@ def main(argv=None, model=None, script=None):
             cbs.append(EarlyStopping(monitor="val_auc", patience=args.patience, mode="max", verbose=1))
         hist = model.fit({k: xtr[k] for k in names}, train_t["label"], batch_size=args.batch_size, epochs=args.epochs,
                          verbose=args.verbose, validation_data=({k: xva[k] for k in names}, val_t["label"]),
-                         shuffle=True, callbacks=cbs)
+                         shuffle=True, callbacks=cbs, class_weight=_class_weight(args))
         if rank == 0:
             if os.path.exists(best):
                 model.load_state_dict(torch.load(best, weights_only=True))
