@@ -64,6 +64,8 @@
  * over the global batch of a row-parallel step) -- additions, the version stays 8.
  * xdfm_head_fwd_w, xdfm_head_bwd_w (K8 with one weight per example: sample_weight / class_weight of fit()) -- additions, the
  * version stays 8.
+ * xdfm_varlen_pool_bwd / _bwd_rows: an XDFM_POOL_MAX field now sends the gradient of an all-masked sequence to the recorded
+ * (masked) position instead of dropping it -- a correction of the values, no struct or signature changed, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -217,7 +219,9 @@ int xdfm_varlen_pool_fwd(const float* X, long ldx, int B, const xdfm_varlen_fiel
                          unsigned char* argpos, int* err_flag, void* stream);
 /* Backward: dense [vocab][D] and [vocab][1] gradients, no float atomics, bit-identical from run to run.  An expand kernel
  * writes one row gradient per position for B * Tmax pseudo-examples (Tmax = largest maxlen; g for sum, g / (len + 1e-8f) for
- * mean, g at the recorded position for max, zeros at masked and padded positions), then K2's exact segmented reduce
+ * mean, both at the valid positions only; for max g at the recorded position whether or not it is valid -- an all-masked sequence
+ * sends its gradient to the row its first maximum looked up, row 0 under the id != 0 mask, as autograd of the reference's
+ * torch.max over w - (1 - mask) * 1e9 does; zeros everywhere else), then K2's exact segmented reduce
  * (xdfm_embed_scatter_bwd_marked) adds them to d_flat in chunks of 4096 pseudo-examples, in ascending order.
  * d_emb_fm / d_dnn_in / d_lin: the gradients of the three outputs of the forward (same layouts; each may be NULL; ld_lin = row
  * stride of d_lin, 0 = 1); the pooled row's gradient is d_emb_fm + d_dnn_in (one fp32 add).
@@ -238,7 +242,8 @@ int xdfm_varlen_pool_bwd(const float* X, long ldx, int B, const xdfm_varlen_fiel
  * XDFM_POOL_MAX fields the position of the first maximum is recomputed from the tables in `fields` by the forward's own walk
  * (same validity, masked positions as w - 1e9f, ties to the lowest position) -- call it BEFORE the tables are updated.  Then
  * xdfm_varlen_pool_bwd's expand and reduce run over the R rows: same d_flat / tab_off / lin_off / cols / vocab, same bits as
- * that call on the same rows in the same order; an all-zero row adds nothing.  An id outside [0, vocab), at any position,
+ * that call on the same rows in the same order; an all-zero row with zero gradients adds nothing (a max field adds its
+ * gradient, an exact zero, to row 0).  An id outside [0, vocab), at any position,
  * raises err_flag (device int[1] or NULL) and is clamped.  ws: xdfm_varlen_pool_bwd_rows_ws_elems floats, 16-byte aligned. */
 size_t xdfm_varlen_pool_bwd_rows_ws_elems(long R, int F, int D, int Tmax);
 int xdfm_varlen_pool_bwd_rows(const float* X, long ldx, int R, const xdfm_varlen_field* fields,

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/varlen_pool_<mode>.npz and varlen_model_{xdeepfm,attn}.npz by RUNNING THE REFERENCE on
+"""Generate tests/golden/varlen_pool_<mode>.npz, varlen_pool_max_empty.npz and varlen_model_{xdeepfm,attn}.npz by RUNNING THE REFERENCE on
 multi-valued columns (VarLenSparseFeat: deepctr/inputs.py:141-155, :213-227; deepctr/layers/sequence.py:9-77).
 
 make_golden.py's import recipe is reused.  The files are data only.
 
 varlen_pool_<mode>.npz: the reference's own SequencePoolingLayer on rows looked up in a random [V, D] table, for both mask
 kinds (`zero`: mask = id != 0; `len`: mask = t < length; max has no `len` golden, the reference raises there), with the gradient of the table for a random upstream gradient.
+Their max sequences all hold a valid item; varlen_pool_max_empty.npz is the zero-mask max case with empty sequences.
+A file whose arrays come out as they are stored is left untouched (an .npz carries its writing time).
 
 varlen_model_*.npz: the whole reference model on 3 SparseFeat, 3 VarLenSparseFeat (mean / zero mask, sum / length column,
 max / zero mask) and 2 DenseFeat: initial state_dict after the constructor alone, y_pred and every gradient of step 1 on the
@@ -30,7 +32,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import make_golden as mg                      # noqa: E402  (registers the reference's deepctr package)
-from make_golden import _np, _save            # noqa: E402
+from make_golden import _np                   # noqa: E402
 from deepctr.inputs import SparseFeat, DenseFeat, VarLenSparseFeat, build_input_features   # noqa: E402
 from deepctr.layers.sequence import SequencePoolingLayer        # noqa: E402
 from deepctr.models.xdeepfm import xDeepFM                      # noqa: E402
@@ -39,6 +41,21 @@ from deepctr.models.xdeepfm_attn import xDeepFMAttention        # noqa: E402
 LR = 1e-3                                     # compile("adam")'s default; see the module docstring
 D = 4
 B = 6
+
+
+def _save(name, **arrays):
+    """Writes name.npz unless the file is there and already holds exactly these arrays: an .npz carries the time it was
+    written, so rewriting equal data would still change the committed bytes."""
+    path = os.path.join(HERE, name + ".npz")
+    if os.path.exists(path):
+        with np.load(path, allow_pickle=False) as z:
+            old = {k: z[k] for k in z.files}
+        if list(old) == list(arrays) and all(
+                old[k].dtype == np.asarray(v).dtype and np.array_equal(old[k], np.asarray(v), equal_nan=old[k].dtype.kind == "f")
+                for k, v in arrays.items()):
+            print("kept  %-34s (same arrays, file untouched)" % (name + ".npz"))
+            return
+    mg._save(name, **arrays)
 
 
 def gen_pool():
@@ -80,6 +97,37 @@ def gen_pool():
             arrays["pooled_" + kind] = _np(out)
             arrays["dtable_" + kind] = _np(w.grad)
         _save("varlen_pool_" + mode, **arrays)
+
+
+def gen_pool_max_empty():
+    """varlen_pool_max_empty.npz: max pooling under the zero mask with EMPTY sequences (1, 4 and 8), which gen_pool leaves
+    out.  hist = emb - (1 - mask) * 1e9 and torch.max(hist, dim=1) (sequence.py:65-68): an all-masked sequence pools to
+    w[0] - 1e9, and autograd sends its gradient to the first maximum, position 0, which looked row 0 up -- dtable[0] is not
+    zero.  The same lookup through a [V, 1] table with an upstream gradient of its own is stored too (lin_*): the linear
+    logit pools that table the same way."""
+    Bp, T, V = 9, 5, 6
+    rng = np.random.default_rng(14)
+    g = torch.Generator().manual_seed(int(rng.integers(1 << 30)))
+    table, upstream = torch.randn(V, D, generator=g), torch.randn(Bp, D, generator=g)
+    lin_table, lin_upstream = torch.randn(V, 1, generator=g), torch.randn(Bp, 1, generator=g)
+    n_valid = rng.integers(1, T, Bp)
+    n_valid[0] = T                            # a full row
+    n_valid[[1, 4, 8]] = 0                    # the empty ones
+    ids = np.zeros((Bp, T), np.float32)
+    for r in range(Bp):
+        ids[r, :n_valid[r]] = rng.integers(1, V, n_valid[r])
+    ids[2] = (2, 0, 2, 0, 0)                  # the same id twice, around a masked position
+    idx = torch.from_numpy(ids).long()
+    arrays = dict(mode=np.array("max"), table=_np(table), upstream=_np(upstream), ids=ids, lin_table=_np(lin_table),
+                  lin_upstream=_np(lin_upstream))
+    for pre, tab, up in (("", table, upstream), ("lin_", lin_table, lin_upstream)):
+        w = tab.clone().requires_grad_(True)
+        out = SequencePoolingLayer(mode="max", supports_masking=True)([w[idx], idx != 0]).reshape(Bp, tab.shape[1])
+        out.backward(up)
+        arrays[pre + "pooled"], arrays[pre + "dtable"] = _np(out), _np(w.grad)
+    empty = (ids == 0).all(1)
+    assert list(np.flatnonzero(empty)) == [1, 4, 8] and np.all(arrays["dtable"][0] != 0) and np.all(arrays["lin_dtable"][0] != 0)
+    _save("varlen_pool_max_empty", **arrays)
 
 
 def columns():
@@ -204,4 +252,5 @@ def gen_models():
 if __name__ == "__main__":
     torch.set_num_threads(4)
     gen_pool()
+    gen_pool_max_empty()
     gen_models()

@@ -249,17 +249,28 @@ def test_permuting_the_rows(D, maxlens):
 
 @pytest.mark.parametrize("D,maxlens", [(4, (5, 5, 5)), (16, (255, 255, 255))], ids=["D4-T5", "D16-T255"])
 def test_pad_rows_add_exactly_nothing(D, maxlens):
-    """Rows of zeros (ids 0, length 0) -- here even with gradients that are not zero, which the exchange never ships."""
+    """Rows of zeros (ids 0, length 0) with zero gradients, as the exchange pads a ragged rank: every gradient is exactly
+    zero -- the max field treats a pad row as the empty sequence it is and adds its gradient, an exact zero, to row 0.
+    With gradients that are not zero, which the exchange never ships, the sum and mean fields still add nothing, and the
+    max field hands them to row 0 as for any empty sequence."""
     dev = _dev()
     c = Rows(D, maxlens, seed=11)
     rng = np.random.default_rng(2)
     n, m = NPAD, SLOT0 + c.F
     X = np.zeros((n, c.ncols), np.float32)
     d = Device(c, dev)
-    got = d.rows(X, rng.standard_normal((m, n, D)).astype(np.float32), rng.standard_normal((n, m * D + 3)).astype(np.float32),
-                 rng.standard_normal(n).astype(np.float32))
+    got = d.rows(X, np.zeros((m, n, D), np.float32), np.zeros((n, m * D + 3), np.float32), np.zeros(n, np.float32))
     for g in got:
         assert torch.count_nonzero(g).item() == 0
+    de, dd = rng.standard_normal((m, n, D)).astype(np.float32), rng.standard_normal((n, m * D + 3)).astype(np.float32)
+    dl = rng.standard_normal(n).astype(np.float32)
+    got = d.rows(X, de, dd, dl)
+    for k in (0, 1, c.F, c.F + 1):                               # sum and mean: tables and linear tables
+        assert torch.count_nonzero(got[k]).item() == 0
+    for k in (2, c.F + 2):                                       # max: row 0 and nothing else
+        assert torch.count_nonzero(got[k][0]).item() == got[k][0].numel() and torch.count_nonzero(got[k][1:]).item() == 0
+    _check_vs_float64(c, got, X=X, ups=[c.upstream(f, de, dd) for f in range(c.F)], d_lin=dl)
+    _same_bits(got, d.contiguous(X, de, dd, dl), "rows vs contiguous, pad rows")
     assert int(d.flag.item()) == 0
 
 

@@ -112,3 +112,23 @@ def test_float64_helper_reproduces_the_reference_pooling(mode):
         wantg = g["dtable_" + kind]
         np.testing.assert_allclose(dt, wantg, rtol=1e-6, atol=1e-6 * np.abs(wantg).max())
         assert np.all(wantg[n == 0] == 0)
+
+
+def test_float64_helper_reproduces_the_reference_on_empty_max_sequences():
+    """The case the other pooling goldens leave out: max under the zero mask with all-masked sequences (1, 4 and 8 of
+    varlen_pool_max_empty.npz).  The reference pools them to w[0] - 1e9 and autograd hands their gradient to position 0,
+    i.e. to table row 0 -- through the [V, D] table and through the [V, 1] table of the linear logit alike.  Pooled values
+    compare exactly, the table gradient at the bar of the test above."""
+    g = load_golden("varlen_pool_max_empty")
+    ids = g["ids"]
+    assert list(np.flatnonzero((ids == 0).all(1))) == [1, 4, 8] and list(ids[2]) == [2, 0, 2, 0, 0] and np.all(ids[0] != 0)
+    for pre in ("", "lin_"):
+        table, up, want, wantg = g[pre + "table"], g[pre + "upstream"], g[pre + "pooled"], g[pre + "dtable"]
+        assert np.all(wantg[0] != 0)                       # the golden does exercise the case
+        pooled, _, pos = vr.pool(ids, None, table, "max")
+        np.testing.assert_array_equal(pooled, want)
+        np.testing.assert_array_equal(pooled[[1, 4, 8]], np.broadcast_to(table[0] - np.float32(1e9), (3, table.shape[1])))
+        assert np.all(pos[[1, 4, 8]] == 0)
+        dt, _, n = vr.pool_grad(ids, None, table, "max", up)
+        np.testing.assert_allclose(dt, wantg, rtol=1e-6, atol=1e-6 * np.abs(wantg).max())
+        assert n[0] >= 3 and np.all(wantg[n == 0] == 0)

@@ -45,7 +45,11 @@ def pool(ids, lengths, table, mode):
 
 def pool_grad(ids, lengths, table, mode, upstream):
     """(dtable [V, D] float64, sum of |addends| [V, D], number of addends per row [V]) for the upstream gradient [B, D] of
-    the pooled rows: g for sum, g / divisor for mean, g at the first maximum for max, nothing at masked positions."""
+    the pooled rows: g for sum and g / divisor for mean at the valid positions, nothing at masked ones; for max g at the
+    position of the first maximum WHETHER OR NOT that position is valid, as autograd of torch.max over emb - (1 - mask) * 1e9
+    (sequence.py:65-68) sends it: an all-masked sequence hands its gradient to the row its winning masked position looked up
+    (row 0 under the zero mask).  n counts, for max, every valid position and every position that won a column, so it is
+    an upper bound of the addends and 0 only for rows that receive nothing."""
     table = np.asarray(table)
     V, D = table.shape
     idx = np.clip(np.asarray(ids).astype(np.int64), 0, V - 1)
@@ -57,12 +61,16 @@ def pool_grad(ids, lengths, table, mode, upstream):
         coef = (coef.astype(np.float32) / divisor(ids, lengths).astype(np.float32)[:, None, None]).astype(np.float64)   # an fp32 division per addend
     elif mode == "max":
         _, _, pos = pool(ids, lengths, table, "max")
-        coef = coef * (np.arange(T)[None, :, None] == pos[:, None, :])
-    coef = coef * valid[:, :, None]
+        won = np.arange(T)[None, :, None] == pos[:, None, :]
+        coef = coef * won
+        counted = valid | won.any(2)
+    if mode != "max":
+        coef = coef * valid[:, :, None]
+        counted = valid
     dt, ab, n = np.zeros((V, D)), np.zeros((V, D)), np.zeros(V, np.int64)
     np.add.at(dt, idx.reshape(-1), coef.reshape(-1, D))
     np.add.at(ab, idx.reshape(-1), np.abs(coef).reshape(-1, D))
-    np.add.at(n, idx.reshape(-1), valid.reshape(-1).astype(np.int64))
+    np.add.at(n, idx.reshape(-1), counted.reshape(-1).astype(np.int64))
     return dt, ab, n
 
 

@@ -10,7 +10,8 @@
 // floats of the same table row.  Results go straight to their three consumers: the CIN input in FM layout (field slot
 // slot0 + f), the DNN input row, the linear logit (added to what K1 wrote).
 // Backward: no float atomics.  An expand kernel writes one row gradient per (example, position) -- B * Tmax
-// pseudo-examples per field, zeros where masked or padded -- and K2's exact segmented reduce adds them up by id
+// pseudo-examples per field; zeros where padded up to Tmax, where masked (sum, mean) and everywhere but the recorded position
+// (max: that position gets g even when it is masked, as on an empty sequence) -- and K2's exact segmented reduce adds them up by id
 // (embed.hip): a pure function of the multiset of rows per chunk, chunks in ascending order, bit-identical from run to run.
 #include "xdfm_internal.h"
 
@@ -140,9 +141,12 @@ __global__ __launch_bounds__(VL_THREADS) void varlen_pool_expand_kernel(
     if (!dst) return;
     float val = 0.f;
     if (inside) {
-        const long len = (fd.len_col >= 0 || fd.combiner == XDFM_POOL_MEAN) ? vl_length(xrow, fd) : 0;   // the count is the mean's divisor only
-        const bool valid = fd.len_col >= 0 ? (long)t < len : (long)idv != 0;
-        if (valid) {
+        const long len = (fd.combiner != XDFM_POOL_MAX && (fd.len_col >= 0 || fd.combiner == XDFM_POOL_MEAN)) ? vl_length(xrow, fd) : 0;   // the count is the mean's divisor only
+        // sum, mean: the valid positions.  max: the recorded position, valid or not -- torch.max over emb - (1 - mask) * 1e9
+        // (sequence.py:65-68) sends the gradient to its first maximum, which on an all-masked sequence is a masked position
+        const bool take = fd.combiner == XDFM_POOL_MAX ? (int)argpos[((long)b * F + f) * W + d] == t
+                                                       : (fd.len_col >= 0 ? (long)t < len : (long)idv != 0);
+        if (take) {
             float g;
             if (is_lin) {
                 g = d_lin ? d_lin[(long)b * ld_lin] : 0.f;
@@ -152,9 +156,7 @@ __global__ __launch_bounds__(VL_THREADS) void varlen_pool_expand_kernel(
                 const float gd = d_dnn_in ? d_dnn_in[(long)b * ld_dnn + dnn_off + (long)f * D + d] : 0.f;
                 g = ge + gd;                       // one fp32 add, as autograd's accumulation of the two uses of the pooled row
             }
-            if (fd.combiner == XDFM_POOL_SUM) val = g;
-            else if (fd.combiner == XDFM_POOL_MEAN) val = g / ((float)len + 1e-8f);
-            else val = (int)argpos[((long)b * F + f) * W + d] == t ? g : 0.f;
+            val = fd.combiner == XDFM_POOL_MEAN ? g / ((float)len + 1e-8f) : g;
         }
     }
     *dst = val;
