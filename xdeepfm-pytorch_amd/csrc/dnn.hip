@@ -383,14 +383,24 @@ __global__ __launch_bounds__(256) void dense_dropout_mask_kernel(long rows, int 
 
 #define DN_LAUNCH(AKC, BKC, MASK, EPI, grid, st, a) \
     hipLaunchKernelGGL((dense_mfma_kernel<AKC, BKC, MASK, EPI>), grid, dim3(DN_NW * 64), 0, st, a)
+// The instances, instantiated here so that the code object's layout does not follow the order of the launches below.
+#define DN_INSTANCE(AKC, BKC, MASK, EPI) template __global__ void dense_mfma_kernel<AKC, BKC, MASK, EPI>(DnArgs)
+DN_INSTANCE(true, true, false, DN_EPI_FWD_DROP);     DN_INSTANCE(true, true, false, DN_EPI_FWD);
+DN_INSTANCE(true, false, true, DN_EPI_PLAIN_SCALED); DN_INSTANCE(true, false, true, DN_EPI_PLAIN);
+DN_INSTANCE(true, false, false, DN_EPI_PLAIN);
+DN_INSTANCE(false, false, true, DN_EPI_SLAB_SCALED); DN_INSTANCE(false, false, true, DN_EPI_SLAB);
+DN_INSTANCE(false, false, false, DN_EPI_SLAB);
+DN_INSTANCE(true, true, false, DN_EPI_FWD_PRELU);    DN_INSTANCE(true, false, true, DN_EPI_PLAIN_PRELU);
+DN_INSTANCE(false, false, true, DN_EPI_SLAB_PRELU);
 
 // Dropout arguments of the _drop entry points, checked: on = p_drop > 0 (p_drop = 0 runs the plain instances).
 struct DnDrop {
     bool on;
     const unsigned long long* seed; unsigned thresh; float keep_scale; int layer; long row0;
 };
+static const DnDrop DN_NO_DROP = {false, nullptr, 0u, 1.f, 0, 0};
 static int dn_drop_rate(const char* who, float p_drop, DnDrop* d) {
-    *d = DnDrop{false, nullptr, 0u, 1.f, 0, 0};
+    *d = DN_NO_DROP;
     XDFM_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "%s: p_drop = %g outside [0, 1)", who, p_drop);
     d->on = p_drop > 0.f;
     if (d->on) { d->thresh = xdfm_drop_thresh(p_drop); d->keep_scale = xdfm_drop_keep_scale(p_drop); }
@@ -405,145 +415,93 @@ static int dn_drop_mask_args(const char* who, float p_drop, const unsigned long 
     return XDFM_OK;
 }
 
+// What gates one layer's gradient: nothing, the ReLU mask y > 0, that mask with the kept cells scaled (dropout), or PReLU's
+// z > 0 ? 1 : alpha.  `y` is the operand the backward kernels read next to g -- the layer's output, for PReLU its
+// pre-activation z, which the forward writes there -- and `name` what the entry point calls it ("y" / "z", pitch "ldy" /
+// "ldz") in messages.
+struct DnGate {
+    enum Kind { PLAIN, RELU, DROP, PRELU } kind;
+    const char* name;
+    const float* y; long ldy;
+    DnDrop drop;                   // DROP; keep_scale = 1 for PLAIN and RELU
+    const float* alpha;            // PRELU
+};
+// the plain and the _drop entry points: drop.on decides, then y (NULL: no mask)
+static DnGate dn_gate(const float* y, long ldy, const DnDrop& drop) {
+    return DnGate{drop.on ? DnGate::DROP : y ? DnGate::RELU : DnGate::PLAIN, "y", y, ldy, drop, nullptr};
+}
+static DnGate dn_gate_prelu(const float* z, long ldz, const float* alpha) { return DnGate{DnGate::PRELU, "z", z, ldz, DnDrop{}, alpha}; }
+
+#define DN_REQUIRE_SHAPE(who, rows, in, out) \
+    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows); \
+    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in); \
+    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)", \
+                 who, rows, in, out)
+// the gating operand's pitch, and the dropped layer's need of its output (backward)
+#define DN_REQUIRE_GATE(who, gate, out) \
+    XDFM_REQUIRE(!gate.y || gate.ldy >= out, "%s: ld%s = %ld < out = %d", who, gate.name, gate.ldy, out); \
+    XDFM_REQUIRE(gate.kind != DnGate::DROP || gate.y, "%s: p_drop > 0 needs y (the layer's dropped output is the mask), y is NULL", who)
+
+// Forward.  The gate is PLAIN (act says whether the epilogue applies ReLU), DROP or PRELU (gate.y: where z goes, or NULL).
 static int dn_fwd(const char* who, const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act,
-                  float* y, long ldy, const DnDrop& drop, void* stream) {
+                  float* y, long ldy, const DnGate& gate, void* stream) {
     XDFM_REQUIRE(x && W && y, "%s: null pointer", who);
-    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
-    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 who, rows, in, out);
+    DN_REQUIRE_SHAPE(who, rows, in, out);
     XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
     XDFM_REQUIRE(ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
+    XDFM_REQUIRE(!gate.y || gate.ldy >= out, "%s: ld%s = %ld < out = %d", who, gate.name, gate.ldy, out);
     XDFM_REQUIRE(act == XDFM_ACT_LINEAR || act == XDFM_ACT_RELU, "%s: act = %d (0 = none, 1 = relu)", who, act);
-    XDFM_REQUIRE(!drop.on || act == XDFM_ACT_RELU, "%s: p_drop > 0 needs act = 1 (relu), act = %d: the backward reads the mask off y > 0",
-                 who, act);
+    XDFM_REQUIRE(gate.kind != DnGate::DROP || act == XDFM_ACT_RELU,
+                 "%s: p_drop > 0 needs act = 1 (relu), act = %d: the backward reads the mask off y > 0", who, act);
     DnArgs a{};
     a.A = x; a.lda = ldx; a.B = W; a.ldb = in; a.C = y; a.ldc = ldy; a.bias = b; a.relu = act == XDFM_ACT_RELU;
     a.M = rows; a.N = out; a.K = in; a.kper = round_up(in, DN_K);
-    a.seed = drop.seed; a.row0 = drop.row0; a.thresh = drop.thresh; a.layer = drop.layer; a.keep_scale = drop.keep_scale;
+    a.seed = gate.drop.seed; a.row0 = gate.drop.row0; a.thresh = gate.drop.thresh; a.layer = gate.drop.layer;
+    a.keep_scale = gate.drop.keep_scale;
+    a.alpha = gate.alpha; a.Z = const_cast<float*>(gate.y); a.ldz = gate.ldy;
     const dim3 grid(ceil_div(rows, DN_T), ceil_div(out, DN_T), 1);
-    if (drop.on) DN_LAUNCH(true, true, false, DN_EPI_FWD_DROP, grid, (hipStream_t)stream, a);
+    if (gate.kind == DnGate::DROP) DN_LAUNCH(true, true, false, DN_EPI_FWD_DROP, grid, (hipStream_t)stream, a);
+    else if (gate.kind == DnGate::PRELU) DN_LAUNCH(true, true, false, DN_EPI_FWD_PRELU, grid, (hipStream_t)stream, a);
     else DN_LAUNCH(true, true, false, DN_EPI_FWD, grid, (hipStream_t)stream, a);
     return xdfm_check_launch(who);
 }
 
-static int dn_bwd_x(const char* who, const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in,
-                    float* dx, long lddx, const DnDrop& drop, void* stream) {
+static int dn_bwd_x(const char* who, const float* g, long ldg, long rows, int out, const float* W, int in, float* dx, long lddx,
+                    const DnGate& gate, void* stream) {
     XDFM_REQUIRE(g && W && dx, "%s: null pointer", who);
-    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
-    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 who, rows, in, out);
+    DN_REQUIRE_SHAPE(who, rows, in, out);
     XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
-    XDFM_REQUIRE(!y || ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
+    DN_REQUIRE_GATE(who, gate, out);
     XDFM_REQUIRE(lddx >= in, "%s: lddx = %ld < in = %d", who, lddx, in);
-    XDFM_REQUIRE(!drop.on || y, "%s: p_drop > 0 needs y (the layer's dropped output is the mask), y is NULL", who);
     DnArgs a{};
-    a.A = g; a.Ay = y; a.lda = ldg; a.lday = ldy; a.B = W; a.ldb = in; a.C = dx; a.ldc = lddx;
+    a.A = g; a.Ay = gate.y; a.lda = ldg; a.lday = gate.ldy; a.B = W; a.ldb = in; a.C = dx; a.ldc = lddx;
     a.M = rows; a.N = in; a.K = out; a.kper = round_up(out, DN_K);
-    a.keep_scale = drop.keep_scale;
+    a.keep_scale = gate.drop.keep_scale; a.alpha = gate.alpha;
     const dim3 grid(ceil_div(rows, DN_T), ceil_div(in, DN_T), 1);
-    if (drop.on) DN_LAUNCH(true, false, true, DN_EPI_PLAIN_SCALED, grid, (hipStream_t)stream, a);
-    else if (y) DN_LAUNCH(true, false, true, DN_EPI_PLAIN, grid, (hipStream_t)stream, a);
+    if (gate.kind == DnGate::DROP) DN_LAUNCH(true, false, true, DN_EPI_PLAIN_SCALED, grid, (hipStream_t)stream, a);
+    else if (gate.kind == DnGate::PRELU) DN_LAUNCH(true, false, true, DN_EPI_PLAIN_PRELU, grid, (hipStream_t)stream, a);
+    else if (gate.kind == DnGate::RELU) DN_LAUNCH(true, false, true, DN_EPI_PLAIN, grid, (hipStream_t)stream, a);
     else DN_LAUNCH(true, false, false, DN_EPI_PLAIN, grid, (hipStream_t)stream, a);
     return xdfm_check_launch(who);
 }
 
-static int dn_bwd_w(const char* who, const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in,
-                    int out, float* ws, float* dW, float* db, const DnDrop& drop, void* stream) {
-    XDFM_REQUIRE(g && x && dW, "%s: null pointer", who);
-    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
-    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 who, rows, in, out);
-    XDFM_REQUIRE(ws, "%s: workspace is NULL (xdfm_dense_bwd_w_ws_elems floats)", who);
-    XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
-    XDFM_REQUIRE(!y || ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
-    XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
-    XDFM_REQUIRE(!drop.on || y, "%s: p_drop > 0 needs y (the layer's dropped output is the mask), y is NULL", who);
-    hipStream_t st = (hipStream_t)stream;
-    const int want = dn_splits(rows);
-    const long kper = round_up(ceil_div(rows, want), DN_K);
-    const int nsplit = ceil_div(rows, kper);             // <= want: what the workspace was sized for
-    const long mn = (long)out * in;
-    DnArgs a{};
-    a.A = g; a.Ay = y; a.lda = ldg; a.lday = ldy; a.B = x; a.ldb = ldx;
-    a.M = out; a.N = in; a.K = rows; a.kper = kper; a.ldc = in;
-    a.keep_scale = drop.keep_scale;
-    if (nsplit == 1) { a.C = dW; a.cslab = 0; a.dbpart = db; }
-    else { a.C = ws; a.cslab = mn; a.dbpart = db ? ws + (long)nsplit * mn : nullptr; }
-    const dim3 grid(ceil_div(out, DN_T), ceil_div(in, DN_T), nsplit);
-    if (drop.on) DN_LAUNCH(false, false, true, DN_EPI_SLAB_SCALED, grid, st, a);
-    else if (y) DN_LAUNCH(false, false, true, DN_EPI_SLAB, grid, st, a);
-    else DN_LAUNCH(false, false, false, DN_EPI_SLAB, grid, st, a);
-    if (nsplit > 1) {
-        const long total = mn + (db ? out : 0);
-        hipLaunchKernelGGL(dense_bwd_w_finish_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, ws, nsplit, mn, (long)out, dW, db);
-    }
-    return xdfm_check_launch(who);
-}
-
-// ---- PReLU layer
-// floats of the dW workspace in front of the doubles (the slabs and bias partials of xdfm_dense_bwd_w, rounded up to an
-// even count: the base is 8-byte aligned)
+// floats of the dW workspace: per split a slab of dW and the bias partials
+static inline size_t dn_ws_floats(int splits, long in, long out) { return (size_t)splits * ((size_t)out * in + out); }
+// ... in front of the PReLU layer's doubles: rounded up to an even count (the base is 8-byte aligned)
 static inline size_t dn_prelu_ws_floats(int splits, long in, long out) {
-    const size_t n = (size_t)splits * ((size_t)out * in + out);
+    const size_t n = dn_ws_floats(splits, in, out);
     return n + (n & 1);
 }
 
-static int dn_prelu_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, const float* alpha,
-                        float* y, long ldy, float* z, long ldz, void* stream) {
-    const char* who = "dense_prelu_fwd";
-    XDFM_REQUIRE(x && W && y && alpha, "%s: null pointer", who);
-    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
-    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 who, rows, in, out);
-    XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
-    XDFM_REQUIRE(ldy >= out, "%s: ldy = %ld < out = %d", who, ldy, out);
-    XDFM_REQUIRE(!z || ldz >= out, "%s: ldz = %ld < out = %d", who, ldz, out);
-    XDFM_REQUIRE(y != z, "%s: y == z (the backward needs the pre-activation apart from the output)", who);
-    DnArgs a{};
-    a.A = x; a.lda = ldx; a.B = W; a.ldb = in; a.C = y; a.ldc = ldy; a.bias = b; a.relu = 0;
-    a.M = rows; a.N = out; a.K = in; a.kper = round_up(in, DN_K);
-    a.alpha = alpha; a.Z = z; a.ldz = ldz;
-    const dim3 grid(ceil_div(rows, DN_T), ceil_div(out, DN_T), 1);
-    DN_LAUNCH(true, true, false, DN_EPI_FWD_PRELU, grid, (hipStream_t)stream, a);
-    return xdfm_check_launch(who);
-}
-
-static int dn_prelu_bwd_x(const float* g, long ldg, const float* z, long ldz, const float* alpha, long rows, int out, const float* W,
-                          int in, float* dx, long lddx, void* stream) {
-    const char* who = "dense_prelu_bwd_x";
-    XDFM_REQUIRE(g && z && alpha && W && dx, "%s: null pointer", who);
-    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
-    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 who, rows, in, out);
+// dalpha: PRELU only (NULL: no slope gradient); then ws is 8-byte aligned and holds the doubles behind its floats
+static int dn_bwd_w(const char* who, const float* g, long ldg, const float* x, long ldx, long rows, int in, int out, float* ws,
+                    float* dW, float* db, float* dalpha, const DnGate& gate, void* stream) {
+    const bool prelu = gate.kind == DnGate::PRELU;
+    XDFM_REQUIRE(g && x && dW, "%s: null pointer", who);
+    DN_REQUIRE_SHAPE(who, rows, in, out);
+    XDFM_REQUIRE(ws, "%s: workspace is NULL (xdfm_dense%s_bwd_w_ws_elems floats)", who, prelu ? "_prelu" : "");
     XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
-    XDFM_REQUIRE(ldz >= out, "%s: ldz = %ld < out = %d", who, ldz, out);
-    XDFM_REQUIRE(lddx >= in, "%s: lddx = %ld < in = %d", who, lddx, in);
-    DnArgs a{};
-    a.A = g; a.Ay = z; a.lda = ldg; a.lday = ldz; a.B = W; a.ldb = in; a.C = dx; a.ldc = lddx;
-    a.M = rows; a.N = in; a.K = out; a.kper = round_up(out, DN_K);
-    a.alpha = alpha;
-    const dim3 grid(ceil_div(rows, DN_T), ceil_div(in, DN_T), 1);
-    DN_LAUNCH(true, false, true, DN_EPI_PLAIN_PRELU, grid, (hipStream_t)stream, a);
-    return xdfm_check_launch(who);
-}
-
-static int dn_prelu_bwd_w(const float* g, long ldg, const float* z, long ldz, const float* alpha, const float* x, long ldx, long rows,
-                          int in, int out, float* ws, float* dW, float* db, float* dalpha, void* stream) {
-    const char* who = "dense_prelu_bwd_w";
-    XDFM_REQUIRE(g && z && alpha && x && dW, "%s: null pointer", who);
-    XDFM_REQUIRE(rows > 0, "%s: rows = %ld", who, rows);
-    XDFM_REQUIRE(in > 0, "%s: in = %d", who, in);
-    XDFM_REQUIRE(dn_supported(rows, in, out), "%s: unsupported shape rows = %ld, in = %d, out = %d (out must be a multiple of 32)",
-                 who, rows, in, out);
-    XDFM_REQUIRE(ws, "%s: workspace is NULL (xdfm_dense_prelu_bwd_w_ws_elems floats)", who);
-    XDFM_REQUIRE(((size_t)ws & 7) == 0, "%s: workspace not 8-byte aligned", who);
-    XDFM_REQUIRE(ldg >= out, "%s: ldg = %ld < out = %d", who, ldg, out);
-    XDFM_REQUIRE(ldz >= out, "%s: ldz = %ld < out = %d", who, ldz, out);
+    DN_REQUIRE_GATE(who, gate, out);
     XDFM_REQUIRE(ldx >= in, "%s: ldx = %ld < in = %d", who, ldx, in);
     hipStream_t st = (hipStream_t)stream;
     const int want = dn_splits(rows);
@@ -553,21 +511,33 @@ static int dn_prelu_bwd_w(const float* g, long ldg, const float* z, long ldz, co
     const int mtiles = ceil_div(out, DN_T);
     double* dapart = dalpha ? (double*)(ws + dn_prelu_ws_floats(nsplit, in, out)) : nullptr;
     DnArgs a{};
-    a.A = g; a.Ay = z; a.lda = ldg; a.lday = ldz; a.B = x; a.ldb = ldx;
+    a.A = g; a.Ay = gate.y; a.lda = ldg; a.lday = gate.ldy; a.B = x; a.ldb = ldx;
     a.M = out; a.N = in; a.K = rows; a.kper = kper; a.ldc = in;
-    a.alpha = alpha; a.dapart = dapart;
+    a.keep_scale = gate.drop.keep_scale; a.alpha = gate.alpha; a.dapart = dapart;
     if (nsplit == 1) { a.C = dW; a.cslab = 0; a.dbpart = db; }
     else { a.C = ws; a.cslab = mn; a.dbpart = db ? ws + (long)nsplit * mn : nullptr; }
     const dim3 grid(mtiles, ceil_div(in, DN_T), nsplit);
-    DN_LAUNCH(false, false, true, DN_EPI_SLAB_PRELU, grid, st, a);
+    if (gate.kind == DnGate::DROP) DN_LAUNCH(false, false, true, DN_EPI_SLAB_SCALED, grid, st, a);
+    else if (prelu) DN_LAUNCH(false, false, true, DN_EPI_SLAB_PRELU, grid, st, a);
+    else if (gate.kind == DnGate::RELU) DN_LAUNCH(false, false, true, DN_EPI_SLAB, grid, st, a);
+    else DN_LAUNCH(false, false, false, DN_EPI_SLAB, grid, st, a);
+    // the finish over the splits (none with a single split, whose dW and db are final); PReLU's has one more block for the slope
     const unsigned eblocks = nsplit > 1 ? (unsigned)ceil_div(mn + (db ? out : 0), 256) : 0u;
-    if (eblocks || dalpha)
+    if (prelu && (eblocks || dalpha))
         hipLaunchKernelGGL(dense_prelu_bwd_w_finish_kernel, dim3(eblocks + (dalpha ? 1u : 0u)), dim3(256), 0, st, ws, nsplit, mn,
                            (long)out, dW, db, eblocks, dapart, nsplit * mtiles, dalpha);
+    else if (!prelu && eblocks)
+        hipLaunchKernelGGL(dense_bwd_w_finish_kernel, dim3(eblocks), dim3(256), 0, st, ws, nsplit, mn, (long)out, dW, db);
     return xdfm_check_launch(who);
 }
 
 extern "C" {
+
+int xdfm_dense_supported(long rows, int in, int out) { return dn_supported(rows, in, out) ? 1 : 0; }
+
+size_t xdfm_dense_bwd_w_ws_elems(long rows, int in, int out) {
+    return dn_supported(rows, in, out) ? dn_ws_floats(dn_splits(rows), in, out) : 0;
+}
 
 size_t xdfm_dense_prelu_bwd_w_ws_elems(long rows, int in, int out) {
     if (!dn_supported(rows, in, out)) return 0;
@@ -575,68 +545,60 @@ size_t xdfm_dense_prelu_bwd_w_ws_elems(long rows, int in, int out) {
     return dn_prelu_ws_floats(splits, in, out) + (size_t)2 * splits * ceil_div(out, DN_T);       // one double per (tile of out, split)
 }
 
-int xdfm_dense_prelu_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, const float* alpha,
-                         float* y, long ldy, float* z, long ldz, void* stream) {
-    return dn_prelu_fwd(x, rows, in, ldx, W, out, b, alpha, y, ldy, z, ldz, stream);
-}
-
-int xdfm_dense_prelu_bwd_x(const float* g, long ldg, const float* z, long ldz, const float* alpha, long rows, int out, const float* W,
-                           int in, float* dx, long lddx, void* stream) {
-    return dn_prelu_bwd_x(g, ldg, z, ldz, alpha, rows, out, W, in, dx, lddx, stream);
-}
-
-int xdfm_dense_prelu_bwd_w(const float* g, long ldg, const float* z, long ldz, const float* alpha, const float* x, long ldx, long rows,
-                           int in, int out, float* ws, float* dW, float* db, float* dalpha, void* stream) {
-    return dn_prelu_bwd_w(g, ldg, z, ldz, alpha, x, ldx, rows, in, out, ws, dW, db, dalpha, stream);
-}
-
-int xdfm_dense_supported(long rows, int in, int out) { return dn_supported(rows, in, out) ? 1 : 0; }
-
-size_t xdfm_dense_bwd_w_ws_elems(long rows, int in, int out) {
-    if (!dn_supported(rows, in, out)) return 0;
-    return (size_t)dn_splits(rows) * ((size_t)out * in + out);
-}
-
 int xdfm_dense_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act, float* y,
                    long ldy, void* stream) {
-    DnDrop drop;
-    dn_drop_rate("dense_fwd", 0.f, &drop);
-    return dn_fwd("dense_fwd", x, rows, in, ldx, W, out, b, act, y, ldy, drop, stream);
+    return dn_fwd("dense_fwd", x, rows, in, ldx, W, out, b, act, y, ldy, dn_gate(nullptr, 0, DN_NO_DROP), stream);
 }
 
 int xdfm_dense_bwd_x(const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in, float* dx,
                      long lddx, void* stream) {
-    DnDrop drop;
-    dn_drop_rate("dense_bwd_x", 0.f, &drop);
-    return dn_bwd_x("dense_bwd_x", g, ldg, y, ldy, rows, out, W, in, dx, lddx, drop, stream);
+    return dn_bwd_x("dense_bwd_x", g, ldg, rows, out, W, in, dx, lddx, dn_gate(y, ldy, DN_NO_DROP), stream);
 }
 
 int xdfm_dense_bwd_w(const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in, int out,
                      float* ws, float* dW, float* db, void* stream) {
-    DnDrop drop;
-    dn_drop_rate("dense_bwd_w", 0.f, &drop);
-    return dn_bwd_w("dense_bwd_w", g, ldg, y, ldy, x, ldx, rows, in, out, ws, dW, db, drop, stream);
+    return dn_bwd_w("dense_bwd_w", g, ldg, x, ldx, rows, in, out, ws, dW, db, nullptr, dn_gate(y, ldy, DN_NO_DROP), stream);
 }
 
 int xdfm_dense_fwd_drop(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, int act, float* y,
                         long ldy, float p_drop, const unsigned long long* seed, int layer, long row0, void* stream) {
     DnDrop drop;
     if (int rc = dn_drop_mask_args("dense_fwd_drop", p_drop, seed, layer, row0, &drop)) return rc;
-    return dn_fwd("dense_fwd_drop", x, rows, in, ldx, W, out, b, act, y, ldy, drop, stream);
+    return dn_fwd("dense_fwd_drop", x, rows, in, ldx, W, out, b, act, y, ldy, dn_gate(nullptr, 0, drop), stream);
 }
 
 int xdfm_dense_bwd_x_drop(const float* g, long ldg, const float* y, long ldy, long rows, int out, const float* W, int in, float* dx,
                           long lddx, float p_drop, void* stream) {
     DnDrop drop;
     if (int rc = dn_drop_rate("dense_bwd_x_drop", p_drop, &drop)) return rc;
-    return dn_bwd_x("dense_bwd_x_drop", g, ldg, y, ldy, rows, out, W, in, dx, lddx, drop, stream);
+    return dn_bwd_x("dense_bwd_x_drop", g, ldg, rows, out, W, in, dx, lddx, dn_gate(y, ldy, drop), stream);
 }
 
 int xdfm_dense_bwd_w_drop(const float* g, long ldg, const float* y, long ldy, const float* x, long ldx, long rows, int in, int out,
                           float* ws, float* dW, float* db, float p_drop, void* stream) {
     DnDrop drop;
     if (int rc = dn_drop_rate("dense_bwd_w_drop", p_drop, &drop)) return rc;
-    return dn_bwd_w("dense_bwd_w_drop", g, ldg, y, ldy, x, ldx, rows, in, out, ws, dW, db, drop, stream);
+    return dn_bwd_w("dense_bwd_w_drop", g, ldg, x, ldx, rows, in, out, ws, dW, db, nullptr, dn_gate(y, ldy, drop), stream);
+}
+
+int xdfm_dense_prelu_fwd(const float* x, long rows, int in, long ldx, const float* W, int out, const float* b, const float* alpha,
+                         float* y, long ldy, float* z, long ldz, void* stream) {
+    XDFM_REQUIRE(alpha, "dense_prelu_fwd: null pointer");
+    XDFM_REQUIRE(!y || y != z, "dense_prelu_fwd: y == z (the backward needs the pre-activation apart from the output)");
+    return dn_fwd("dense_prelu_fwd", x, rows, in, ldx, W, out, b, XDFM_ACT_LINEAR, y, ldy, dn_gate_prelu(z, ldz, alpha), stream);
+}
+
+int xdfm_dense_prelu_bwd_x(const float* g, long ldg, const float* z, long ldz, const float* alpha, long rows, int out, const float* W,
+                           int in, float* dx, long lddx, void* stream) {
+    XDFM_REQUIRE(z && alpha, "dense_prelu_bwd_x: null pointer");
+    return dn_bwd_x("dense_prelu_bwd_x", g, ldg, rows, out, W, in, dx, lddx, dn_gate_prelu(z, ldz, alpha), stream);
+}
+
+int xdfm_dense_prelu_bwd_w(const float* g, long ldg, const float* z, long ldz, const float* alpha, const float* x, long ldx, long rows,
+                           int in, int out, float* ws, float* dW, float* db, float* dalpha, void* stream) {
+    XDFM_REQUIRE(z && alpha, "dense_prelu_bwd_w: null pointer");
+    XDFM_REQUIRE(((size_t)ws & 7) == 0, "dense_prelu_bwd_w: workspace not 8-byte aligned");
+    return dn_bwd_w("dense_prelu_bwd_w", g, ldg, x, ldx, rows, in, out, ws, dW, db, dalpha, dn_gate_prelu(z, ldz, alpha), stream);
 }
 
 int xdfm_dense_dropout_mask(long rows, int out, float p_drop, const unsigned long long* seed, int layer, long row0,

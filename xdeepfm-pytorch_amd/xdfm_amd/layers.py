@@ -203,22 +203,19 @@ class CINAttentionV2(_CINBase):
                              self.use_residual)
 
 
+def _stock_act(x, act):
+    return torch.relu(x) if act == "relu" else torch.sigmoid(x) if act == "sigmoid" else x
+
+
 class DNN(nn.Module):
-    """ReLU / linear / sigmoid / PReLU MLP (deepctr/layers/core.py:67-134).  Its GEMMs are far below 2 % of the step's FLOPs but, run as
-    six library GEMMs plus the mask and bias-gradient passes, were 7.5 % of the flagship step's time: layers whose
-    width is a multiple of 32 run their backward in the fp32-MFMA kernels of csrc/dnn.hip (ops.Dense / ops.DenseReLU,
-    `XDFM_DNN_NATIVE`).  Other widths keep hipBLASLt through torch, with the bias gradient by the library's
-    memset-free column sum; either way the step can be captured in a HIP graph.  In training with 0 < dropout_rate < 1 those
-    ReLU layers run their dropout inside the same kernels (ops.DenseReLUDropout, `XDFM_DNN_DROPOUT_NATIVE`): a hashed keep
-    mask, one seed per call in `last_drop_seed`; nn.Dropout stays for every other configuration.  With use_bn the batch norm
-    and the activation behind each dense layer run in the kernels of csrc/bn.hip (ops.bn_act, `XDFM_DNN_BN_NATIVE`; relu,
-    sigmoid and linear, any width); the nn.BatchNorm1d modules stay the holders of gamma, beta and the buffers.
-    activation='prelu' is the reference's: `activation_layers`, a ModuleList of nn.PReLU() (one slope per layer, 0.25, in the
-    l2_reg_dnn group like the reference's), holds the slopes; without batch norm a layer runs the fused dense + PReLU kernels
-    (ops.dense_prelu, `XDFM_DNN_PRELU_NATIVE`), otherwise -- other widths, behind batch norm, the switch off -- the
-    elementwise kernels of csrc/prelu.hip (ops.prelu) behind `ops.dense` / the batch norm; dropout with prelu stays nn.Dropout.
-    'dice' stays refused: the reference's own tower fails on it (Dice(hidden, dice_dim=3) asserts a 3-D input and gets the
-    tower's 2-D one)."""
+    """ReLU / linear / sigmoid / PReLU MLP (deepctr/layers/core.py:67-134).  Its GEMMs are far below 2 % of the step's FLOPs
+    but, run as six library GEMMs plus the mask and bias-gradient passes, were 7.5 % of the flagship step's time; `forward`
+    gives each layer one route through `ops`, whose entry points say which kernels they run and which `XDFM_DNN_*` switch
+    turns them off (the route table is tests/test_dnn_routes.py).  The stock modules stay the holders of the
+    parameters and buffers under the reference's state_dict keys: nn.Linear, nn.BatchNorm1d and, for activation='prelu',
+    `activation_layers`, a ModuleList of nn.PReLU() (one slope per layer, 0.25, in the l2_reg_dnn group).  'dice' stays
+    refused: the reference's own tower fails on it (Dice(hidden, dice_dim=3) asserts a 3-D input and gets the tower's 2-D
+    one)."""
 
     def __init__(self, inputs_dim, hidden_units, activation='relu', l2_reg=0, dropout_rate=0, use_bn=False,
                  init_std=0.0001, dice_dim=3, seed=1024, device='cpu'):
@@ -253,54 +250,42 @@ class DNN(nn.Module):
         return bool(self.use_bn and ops.DNN_BN_SYNC and ops.DNN_BN_NATIVE and isinstance(dp, xdist.RowParallel)
                     and all(b.weight is not None and b.weight.is_cuda for b in self.bn))
 
+    def _bn_act(self, x, bn, act):
+        """act(bn(x)), act one of relu / sigmoid / linear.  One process: the kernels of csrc/bn.hip, one [rows, out] tensor
+        written instead of three.  Row-parallel training: the same kernels split around one all-gather each
+        way where XDFM_DNN_BN_SYNC asks for the statistics of the global batch.  Otherwise the stock module, over each
+        rank's shard."""
+        dp = xdist.current()
+        if dp is None and ops.bn_native(x, bn):
+            return ops.bn_act(x, bn, act, self.training)
+        if ops.bn_sync_native(x, bn, dp):
+            return ops.bn_act_sync(x, bn, act, self.training, dp)
+        return _stock_act(bn(x), act)
+
     def forward(self, x):
-        p = float(self.dropout.p)
-        seed = None              # one per tower call, shared by the layers through their index
+        seed = None              # of the native dropout: one per tower call, shared by the layers through their index
         for i, lin in enumerate(self.linears):
-            if self.activation == "relu" and not self.use_bn:
-                if self.training and ops.dense_dropout_native(x, lin.weight, lin.bias, p):
-                    # dropout in the dense kernels' epilogue and staging: no mask tensor, no extra launch
-                    if seed is None:
-                        seed = self.last_drop_seed = ops.draw_dropout_seed(x.device)
-                    x = ops.dense_relu_dropout(x, lin.weight, lin.bias, p, seed, i)
-                    continue
-                x = self.dropout(ops.dense_relu(x, lin.weight, lin.bias))
-                continue
-            if self.activation == "prelu":
-                alpha = self.activation_layers[i].weight
-                if not self.use_bn:
-                    # y and the pre-activation out of one launch, the slope's gradient out of the dW kernel
-                    x = self.dropout(ops.dense_prelu(x, lin.weight, lin.bias, alpha))
-                    continue
+            act, drop = self.activation, self.dropout        # still to apply: a stage that takes one along clears it
+            # 1. dense: without batch norm ReLU (with its dropout, where the kernels take it) and PReLU ride along
+            if act == "relu" and not self.use_bn:
+                x, seed = ops.dense_relu_then_dropout(x, lin.weight, lin.bias, drop, self.training, seed, i)
+                act, drop = "linear", None
+            elif act == "prelu" and not self.use_bn:
+                x = ops.dense_prelu(x, lin.weight, lin.bias, self.activation_layers[i].weight)
+                act = "linear"
+            else:
                 x = ops.dense(x, lin.weight, lin.bias)
-                dp = xdist.current()
-                if dp is None and ops.bn_native(x, self.bn[i]):
-                    x = ops.bn_act(x, self.bn[i], "linear", self.training)
-                elif ops.bn_sync_native(x, self.bn[i], dp):
-                    x = ops.bn_act_sync(x, self.bn[i], "linear", self.training, dp)
-                else:
-                    x = self.bn[i](x)
-                x = self.dropout(ops.prelu(x, alpha))
-                continue
-            x = ops.dense(x, lin.weight, lin.bias)
-            dp = xdist.current() if self.use_bn else None
-            if self.use_bn and dp is None and ops.bn_native(x, self.bn[i]):
-                # batch norm + activation in the kernels of csrc/bn.hip: one [rows, out] tensor written instead of three
-                # (DESIGN 4.3d).  Row-parallel training keeps the stock modules over each rank's shard unless
-                # XDFM_DNN_BN_SYNC asks for the statistics of the global batch (below).
-                x = self.dropout(ops.bn_act(x, self.bn[i], self.activation, self.training))
-                continue
-            if self.use_bn and ops.bn_sync_native(x, self.bn[i], dp):
-                # row-parallel, opt-in: the same kernels split around one all-gather each way (ops.bn_act_sync)
-                x = self.dropout(ops.bn_act_sync(x, self.bn[i], self.activation, self.training, dp))
-                continue
+            # 2. batch norm, with every activation but PReLU
             if self.use_bn:
-                x = self.bn[i](x)
-            if self.activation == "relu":
-                x = torch.relu(x)
-            elif self.activation == "sigmoid":
-                x = torch.sigmoid(x)
-            x = self.dropout(x)
+                x = self._bn_act(x, self.bn[i], "linear" if act == "prelu" else act)
+                act = "prelu" if act == "prelu" else "linear"
+            # 3. activation
+            x = ops.prelu(x, self.activation_layers[i].weight) if act == "prelu" else _stock_act(x, act)
+            # 4. dropout
+            if drop is not None:
+                x = drop(x)
+        if seed is not None:
+            self.last_drop_seed = seed
         return x
 
 

@@ -919,36 +919,75 @@ def dense_native(x, W, b=None):
     return bool(_lib.load().xdfm_dense_supported(x.shape[0], x.shape[1], W.shape[0]))
 
 
-def _dense_fwd_native(x, W, b, act):
+def _dense_fwd_native(x, W, b, act, p=None, seed=None, layer=0, alpha=None, need_z=False):
+    """The forward launch of every native dense layer: y = act(x W^T + b); with `p` dropped as well (DenseReLUDropout);
+    with `alpha` the PReLU layer, whose result is (y, z) -- z the pre-activation, stored only with need_z."""
     lib = _lib.load()
     rows, k = x.shape
     out = W.shape[0]
     y = torch.empty(rows, out, dtype=torch.float32, device=x.device)
-    _lib.check(_run("dense_fwd", 0.0, lambda: lib.xdfm_dense_fwd(_ptr(x), rows, k, _ld(x), _ptr(W), out, _ptr(b), act, _ptr(y), out,
-                                                                 _stream())), "dense_fwd")
-    return y
+    operands = (_ptr(x), rows, k, _ld(x), _ptr(W), out, _ptr(b))
+    if alpha is not None:
+        z = torch.empty(rows, out, dtype=torch.float32, device=x.device) if need_z else None
+        name, args = "dense_prelu_fwd", operands + (_ptr(alpha), _ptr(y), out, _ptr(z), out)
+    elif p is not None:
+        name, args = "dense_fwd_drop", operands + (act, _ptr(y), out, p, _ptr(seed), int(layer), 0)
+    else:
+        name, args = "dense_fwd", operands + (act, _ptr(y), out)
+    _lib.check(_run(name, 0.0, lambda: getattr(lib, "xdfm_" + name)(*args, _stream())), name)
+    return y if alpha is None else (y, z)
 
 
-def _dense_bwd_native(g, y, x, W, need_dx, need_dw, need_db):
-    """(dx, dW, db) of one layer; y: the ReLU layer's output (its mask is applied while g is loaded) or None."""
+def _dense_bwd_native(g, y, x, W, need_dx, need_dw, need_db, p=None, alpha=None, need_da=False):
+    """(dx, dW, db) of one layer, with `alpha` (dx, dW, db, dalpha).  y gates g while the kernels load it: the ReLU layer's
+    output; with `p` its dropped output (a kept cell's g is scaled by 1 / (1 - p)); with `alpha` the PReLU layer's
+    pre-activation; None for no gate.  db, and dalpha, are by-products of the dW kernel: one call whatever the combination."""
     lib = _lib.load()
     rows, k = x.shape
     out = W.shape[0]
     if not _rows_ok(g):
         g = g.contiguous()
-    ldy = _ld(y) if y is not None else 0
-    dx = dW = db = None
+    dev = g.device
+    ws_elems = lib.xdfm_dense_bwd_w_ws_elems
+    if alpha is not None:
+        name_x, name_w, ws_elems = "dense_prelu_bwd_x", "dense_prelu_bwd_w", lib.xdfm_dense_prelu_bwd_w_ws_elems
+    elif p is not None:
+        name_x, name_w = "dense_bwd_x_drop", "dense_bwd_w_drop"
+    else:
+        name_x, name_w = "dense_bwd_x", "dense_bwd_w"
+    gated = (_ptr(g), _ld(g), _ptr(y), _ld(y) if y is not None else 0) + (() if alpha is None else (_ptr(alpha),))
+    rate = () if p is None else (p,)
+    dx = dW = db = da = None
     if need_dx:
-        dx = torch.empty(rows, k, dtype=torch.float32, device=g.device)
-        _lib.check(_run("dense_bwd_x", 0.0, lambda: lib.xdfm_dense_bwd_x(_ptr(g), _ld(g), _ptr(y), ldy, rows, out, _ptr(W), k, _ptr(dx), k,
-                                                                         _stream())), "dense_bwd_x")
-    if need_dw or need_db:
-        ws = torch.empty(lib.xdfm_dense_bwd_w_ws_elems(rows, k, out), dtype=torch.float32, device=g.device)
-        dW = torch.empty(out, k, dtype=torch.float32, device=g.device)
-        db = torch.empty(out, dtype=torch.float32, device=g.device) if need_db else None
-        _lib.check(_run("dense_bwd_w", 0.0, lambda: lib.xdfm_dense_bwd_w(_ptr(g), _ld(g), _ptr(y), ldy, _ptr(x), _ld(x), rows, k, out,
-                                                                         _ptr(ws), _ptr(dW), _ptr(db), _stream())), "dense_bwd_w")
-    return dx, dW if need_dw else None, db
+        dx = torch.empty(rows, k, dtype=torch.float32, device=dev)
+        _lib.check(_run(name_x, 0.0, lambda: getattr(lib, "xdfm_" + name_x)(*gated, rows, out, _ptr(W), k, _ptr(dx), k, *rate,
+                                                                          _stream())), name_x)
+    if need_dw or need_db or need_da:
+        ws = torch.empty(ws_elems(rows, k, out), dtype=torch.float32, device=dev)
+        dW = torch.empty(out, k, dtype=torch.float32, device=dev)
+        db = torch.empty(out, dtype=torch.float32, device=dev) if need_db else None
+        da = torch.empty(alpha.shape, dtype=torch.float32, device=dev) if need_da else None
+        slope = () if alpha is None else (_ptr(da),)
+        _lib.check(_run(name_w, 0.0, lambda: getattr(lib, "xdfm_" + name_w)(*gated, _ptr(x), _ld(x), rows, k, out, _ptr(ws), _ptr(dW),
+                                                                          _ptr(db), *slope, *rate, _stream())), name_w)
+    grads = (dx, dW if need_dw else None, db)
+    return grads if alpha is None else grads + (da,)
+
+
+def _bias_grad_lib(g, y=None):
+    """(gz, db) behind a library GEMM, g contiguous: db the column sums of gz by the library's own memset-free pass, gz = g
+    or, with the ReLU layer's output y, (y > 0) ? g : 0 written by the same pass."""
+    lib = _lib.load()
+    rows, cols = g.shape
+    ws = torch.empty(lib.xdfm_colsum_ws_elems(cols), dtype=torch.float32, device=g.device)
+    db = torch.empty(cols, dtype=torch.float32, device=g.device)
+    if y is None:
+        _lib.check(lib.xdfm_colsum(_ptr(g), rows, cols, g.stride(0), _ptr(ws), _ptr(db), _stream()), "colsum")
+        return g, db
+    gz = torch.empty_like(g)
+    _lib.check(lib.xdfm_relu_bwd_colsum(_ptr(g), _ptr(y), rows, cols, g.stride(0), y.stride(0), _ptr(ws), _ptr(gz), _ptr(db),
+                                        _stream()), "relu_bwd_colsum")
+    return gz, db
 
 
 class Dense(torch.autograd.Function):
@@ -975,13 +1014,7 @@ class Dense(torch.autograd.Function):
         g = g.contiguous()
         dx = g.mm(W) if ctx.needs_input_grad[0] else None
         dW = g.t().mm(x) if ctx.needs_input_grad[1] else None
-        db = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            lib = _lib.load()
-            rows, cols = g.shape
-            ws = torch.empty(lib.xdfm_colsum_ws_elems(cols), dtype=torch.float32, device=g.device)
-            db = torch.empty(cols, dtype=torch.float32, device=g.device)
-            _lib.check(lib.xdfm_colsum(_ptr(g), rows, cols, g.stride(0), _ptr(ws), _ptr(db), _stream()), "colsum")
+        db = _bias_grad_lib(g)[1] if ctx.has_bias and ctx.needs_input_grad[2] else None
         return dx, dW, db
 
 
@@ -1008,14 +1041,7 @@ class DenseReLU(torch.autograd.Function):
         x, W, y = ctx.saved_tensors
         if dense_native(x, W):
             return _dense_bwd_native(g, y, x, W, *ctx.needs_input_grad)
-        lib = _lib.load()
-        g = g.contiguous()
-        rows, cols = g.shape
-        ws = torch.empty(lib.xdfm_colsum_ws_elems(cols), dtype=torch.float32, device=g.device)
-        gz = torch.empty_like(g)
-        db = torch.empty(cols, dtype=torch.float32, device=g.device)
-        _lib.check(lib.xdfm_relu_bwd_colsum(_ptr(g), _ptr(y), rows, cols, g.stride(0), y.stride(0), _ptr(ws), _ptr(gz),
-                                            _ptr(db), _stream()), "relu_bwd_colsum")
+        gz, db = _bias_grad_lib(g.contiguous(), y)
         dx = gz.mm(W) if ctx.needs_input_grad[0] else None
         dW = gz.t().mm(x) if ctx.needs_input_grad[1] else None
         return dx, dW, db if ctx.needs_input_grad[2] else None
@@ -1059,40 +1085,15 @@ class DenseReLUDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b, p, seed, layer):
         _need_cuda(x, "x")
-        lib = _lib.load()
-        rows, k = x.shape
-        out = W.shape[0]
-        p = float(p)
-        d = torch.empty(rows, out, dtype=torch.float32, device=x.device)
-        _lib.check(_run("dense_fwd_drop", 0.0, lambda: lib.xdfm_dense_fwd_drop(
-            _ptr(x), rows, k, _ld(x), _ptr(W), out, _ptr(b), ACT_CODES["relu"], _ptr(d), out, p, _ptr(seed), int(layer), 0,
-            _stream())), "dense_fwd_drop")
-        ctx.p = p
+        ctx.p = float(p)
+        d = _dense_fwd_native(x, W, b, ACT_CODES["relu"], p=ctx.p, seed=seed, layer=layer)
         ctx.save_for_backward(x, W, d)
         return d
 
     @staticmethod
     def backward(ctx, g):
         x, W, d = ctx.saved_tensors
-        lib = _lib.load()
-        rows, k = x.shape
-        out = W.shape[0]
-        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
-        if not _rows_ok(g):
-            g = g.contiguous()
-        dx = dW = db = None
-        if need_dx:
-            dx = torch.empty(rows, k, dtype=torch.float32, device=g.device)
-            _lib.check(_run("dense_bwd_x_drop", 0.0, lambda: lib.xdfm_dense_bwd_x_drop(
-                _ptr(g), _ld(g), _ptr(d), _ld(d), rows, out, _ptr(W), k, _ptr(dx), k, ctx.p, _stream())), "dense_bwd_x_drop")
-        if need_dw or need_db:
-            ws = torch.empty(lib.xdfm_dense_bwd_w_ws_elems(rows, k, out), dtype=torch.float32, device=g.device)
-            dW = torch.empty(out, k, dtype=torch.float32, device=g.device)
-            db = torch.empty(out, dtype=torch.float32, device=g.device) if need_db else None
-            _lib.check(_run("dense_bwd_w_drop", 0.0, lambda: lib.xdfm_dense_bwd_w_drop(
-                _ptr(g), _ld(g), _ptr(d), _ld(d), _ptr(x), _ld(x), rows, k, out, _ptr(ws), _ptr(dW), _ptr(db), ctx.p, _stream())),
-                "dense_bwd_w_drop")
-        return dx, dW if need_dw else None, db, None, None, None
+        return _dense_bwd_native(g, d, x, W, *ctx.needs_input_grad[:3], p=ctx.p) + (None, None, None)
 
 
 def dense_relu_dropout(x, W, b, p, seed, layer):
@@ -1106,6 +1107,18 @@ def dense_relu_dropout(x, W, b, p, seed, layer):
     if not (seed.is_cuda and seed.dtype == torch.int64 and seed.numel() == 1):
         raise ValueError("dense_relu_dropout: seed must be an int64 device tensor of one element")
     return DenseReLUDropout.apply(x, W, b, float(p), seed, int(layer))
+
+
+def dense_relu_then_dropout(x, W, b, drop, training, seed, layer):
+    """One ReLU layer of a tower and the nn.Dropout `drop` behind it -> (result, seed).  In training the dropout runs inside
+    the dense kernels where `dense_dropout_native` says so: no mask tensor, no extra launch, keyed by `seed` --
+    one per call of the tower, drawn by the first layer that needs it (pass None) and shared through the layers' indices.
+    Everything else is dense_relu with `drop` applied to it."""
+    if training and dense_dropout_native(x, W, b, drop.p):
+        if seed is None:
+            seed = draw_dropout_seed(x.device)
+        return dense_relu_dropout(x, W, b, drop.p, seed, layer), seed
+    return drop(dense_relu(x, W, b)), seed
 
 
 # XDFM_DNN_PRELU_NATIVE: a dense layer followed by nn.PReLU() (layers.DNN with activation='prelu', no batch norm) runs
@@ -1139,41 +1152,15 @@ class DensePReLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b, alpha):
         _need_cuda(x, "x")
-        lib = _lib.load()
-        rows, k = x.shape
-        out = W.shape[0]
-        y = torch.empty(rows, out, dtype=torch.float32, device=x.device)
-        z = torch.empty(rows, out, dtype=torch.float32, device=x.device) if any(ctx.needs_input_grad) else None
-        _lib.check(_run("dense_prelu_fwd", 0.0, lambda: lib.xdfm_dense_prelu_fwd(
-            _ptr(x), rows, k, _ld(x), _ptr(W), out, _ptr(b), _ptr(alpha), _ptr(y), out, _ptr(z), out, _stream())), "dense_prelu_fwd")
+        y, z = _dense_fwd_native(x, W, b, ACT_CODES["linear"], alpha=alpha, need_z=any(ctx.needs_input_grad))
         ctx.save_for_backward(x, W, z, alpha)
         return y
 
     @staticmethod
     def backward(ctx, g):
         x, W, z, alpha = ctx.saved_tensors
-        lib = _lib.load()
-        rows, k = x.shape
-        out = W.shape[0]
         need_dx, need_dw, need_db, need_da = ctx.needs_input_grad
-        if not _rows_ok(g):
-            g = g.contiguous()
-        dev = g.device
-        dx = dW = db = da = None
-        if need_dx:
-            dx = torch.empty(rows, k, dtype=torch.float32, device=dev)
-            _lib.check(_run("dense_prelu_bwd_x", 0.0, lambda: lib.xdfm_dense_prelu_bwd_x(
-                _ptr(g), _ld(g), _ptr(z), out, _ptr(alpha), rows, out, _ptr(W), k, _ptr(dx), k, _stream())), "dense_prelu_bwd_x")
-        if need_dw or need_db or need_da:
-            # the slope's gradient is a by-product of this kernel, as the bias gradient is: one call whatever the combination
-            ws = torch.empty(lib.xdfm_dense_prelu_bwd_w_ws_elems(rows, k, out), dtype=torch.float32, device=dev)
-            dW = torch.empty(out, k, dtype=torch.float32, device=dev)
-            db = torch.empty(out, dtype=torch.float32, device=dev) if need_db else None
-            da = torch.empty(alpha.shape, dtype=torch.float32, device=dev) if need_da else None
-            _lib.check(_run("dense_prelu_bwd_w", 0.0, lambda: lib.xdfm_dense_prelu_bwd_w(
-                _ptr(g), _ld(g), _ptr(z), out, _ptr(alpha), _ptr(x), _ld(x), rows, k, out, _ptr(ws), _ptr(dW), _ptr(db), _ptr(da),
-                _stream())), "dense_prelu_bwd_w")
-        return dx, dW if need_dw else None, db, da
+        return _dense_bwd_native(g, z, x, W, need_dx, need_dw, need_db, alpha=alpha, need_da=need_da)
 
 
 def _dense_prelu_fused(x, W, b, alpha):

@@ -115,26 +115,13 @@ class SFGDecoder(nn.Module):
         if self.use_label_aware_attention and labels is not None:
             decoder_input = decoder_input * self.label_attention.forward_native(decoder_input, labels)
         x = decoder_input
-        mods = list(self.shared_layers)
+        mods = list(self.shared_layers)                             # (nn.Linear, nn.ReLU, nn.Dropout) per hidden layer
         seed = None                                                 # one per call, shared by the layers through their index
-        fused = False                                               # the previous Linear took its nn.Dropout along
-        for j, mod in enumerate(mods):
-            if isinstance(mod, nn.Linear):
-                # every Linear of shared_layers is followed by nn.ReLU and nn.Dropout: the triple is one launch where the
-                # dense kernels take it (layers.DNN.forward's conditions)
-                drop = mods[j + 2] if j + 2 < len(mods) and isinstance(mods[j + 2], nn.Dropout) else None
-                fused = drop is not None and drop.training and ops.dense_dropout_native(x, mod.weight, mod.bias, drop.p)
-                if fused:
-                    if seed is None:
-                        seed = self.last_drop_seed = ops.draw_dropout_seed(x.device)
-                    x = ops.dense_relu_dropout(x, mod.weight, mod.bias, drop.p, seed, j // 3)
-                else:
-                    x = ops.dense_relu(x, mod.weight, mod.bias)
-            elif isinstance(mod, nn.Dropout):
-                x = x if fused else mod(x)
-                fused = False
-            elif not isinstance(mod, nn.ReLU):
-                x = mod(x)
+        for i in range(len(mods) // 3):
+            lin, _, drop = mods[3 * i:3 * i + 3]
+            x, seed = ops.dense_relu_then_dropout(x, lin.weight, lin.bias, drop, drop.training, seed, i)
+        if seed is not None:
+            self.last_drop_seed = seed
         return x
 
     last_drop_seed = None        # the seed of the last hidden_native call that ran the native dropout (read by the tests)
