@@ -137,6 +137,10 @@ int xdfm_device_count(void);                /* <0: HIP error code negated */
  *      "bww_mt"), KV = 1 register-staged kernel ("dbg" bit 8), 2 dword LDS-DMA, 3 dwordx4 LDS-DMA (MT 4, N % 4 == 0, 16-byte
  *      aligned operands, not "dbg" bit 16), slab = 1 per-split slabs summed in order / 0 atomic epilogue ("bww_slab").
  *      Example: 32431 = 32 n-splits, MT 4, dwordx4 LDS-DMA, slabs. */
+/* "adam_rows" (default 1): xdfm_adam_catchup_rows / xdfm_adam_apply_rows with D % 4 == 0 give one thread a whole table row
+ * (one claim per `last` word of the row, the row's chunks in turn) instead of one thread per 16-byte chunk; 0 = by chunk,
+ * which is what every other D runs.  Same bits either way; read when the call issues its launch.  Probe "last_adam_rows":
+ * 1 / 0 = the last of those two calls launched the by-row / the by-chunk kernel, -1 before the first call. */
 int xdfm_set_option(const char* key, int value);
 int xdfm_get_option(const char* key);
 /* Ticket board: `board` = a DEVICE array of `slots` >= 1040 unsigned ints, zeroed once by the caller and kept alive, registered

@@ -352,8 +352,9 @@ __global__ void adam_clock_reset_kernel(int* __restrict__ clock) {
 
 // block sum of l2-weighted squares in fixed point (integer adds are exact: the total does not depend on which thread
 // replayed which chunk, nor on the order of the blocks), one atomic per block
-__device__ __forceinline__ void adam_backlog_add(float v, unsigned long long* __restrict__ backlog) {
-    long long f = (long long)((double)v * ADAM_FIX);
+__device__ __forceinline__ long long adam_backlog_fix(float v) { return (long long)((double)v * ADAM_FIX); }
+// ... of values a thread has converted and added up itself (one per chunk of its row: the same integers as a thread per chunk)
+__device__ __forceinline__ void adam_backlog_add_fix(long long f, unsigned long long* __restrict__ backlog) {
     for (int o = 32; o > 0; o >>= 1) f += __shfl_xor(f, o);
     __shared__ long long part[ADAM_THREADS / 64];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = f;
@@ -363,6 +364,9 @@ __device__ __forceinline__ void adam_backlog_add(float v, unsigned long long* __
         for (int k = 0; k < ADAM_THREADS / 64; ++k) tot += part[k];
         if (tot) atomicAdd(backlog, (unsigned long long)tot);
     }
+}
+__device__ __forceinline__ void adam_backlog_add(float v, unsigned long long* __restrict__ backlog) {
+    adam_backlog_add_fix(adam_backlog_fix(v), backlog);
 }
 
 struct AdamRowsDev {
@@ -523,6 +527,178 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_rows_kernel(
     }
 }
 
+// ---- by row (D % 4 == 0: a row is D / 4 whole chunks of its own; option "adam_rows") ----------------------------------
+// Threads [0, m * B): one per (field, example), the FIELD outermost, and the whole row is the thread's: one claim per `last`
+// word of the row (tbl_claim_row) instead of one per chunk -- at D = 16 a row's four bytes are one word, on which the four
+// lanes of the by-chunk kernels issue four CAS in turn -- then the row's chunks in turn, each from its OWN old byte (they
+// differ after a step the mark scan took).  A wave holds 64 rows of one field, so tables that are up to date (the small
+// vocabularies) and tables that are not no longer share waves: the replay, which every lane of a wave sits through
+// (adam_replay_span), is as long as that field needs.  Threads [m * B, 2 * m * B), with linear tables: one linear entry
+// each, claimed by chunk as before (four ids share a chunk, sixteen a word).  The arithmetic per chunk is the by-chunk
+// kernels', and so are the integers that go into the L2 sums (one conversion per chunk, adam_backlog_fix).
+struct AdamRow { int f; long c0; int nq; bool is_lin; };      // field, first chunk, chunks that are this thread's (0: none)
+__device__ __forceinline__ AdamRow adam_row_of(long idx, bool live, const float* __restrict__ X, long ldx, const int* __restrict__ cols,
+                                               const int* __restrict__ vocab, int m, int B, int D, int has_lin) {
+    AdamRow r;
+    r.f = 0; r.c0 = 0; r.nq = 0; r.is_lin = false;
+    const long nE = (long)m * B;
+    if (!live || idx >= (has_lin ? 2 * nE : nE)) return r;
+    r.is_lin = idx >= nE;
+    const long u = r.is_lin ? idx - nE : idx;
+    r.f = (int)(u / B);
+    const long b = u - (long)r.f * B;
+    const int V = vocab[r.f];
+    long id = (long)X[b * ldx + cols[r.f]];             // as the gather (embed.hip): truncation, clamped
+    if (id < 0 || id >= V) id = id < 0 ? 0 : V - 1;
+    const long w = r.is_lin ? 1 : D;
+    r.c0 = id * w / 4;
+    const long left = (long)V * w / 4 - r.c0;           // whole chunks from c0 on; the tail elements are updated densely every step
+    const long want = r.is_lin ? 1 : D / 4;
+    r.nq = (int)(left < want ? (left > 0 ? left : 0) : want);
+    return r;
+}
+// the claim of chunks q0 .. q0 + 7 of the thread's row -> their old bytes as tbl_claim_row returns them
+__device__ __forceinline__ unsigned long long adam_row_claim(const AdamRow& r, unsigned char* last, int q0, int t) {
+    const int gn = r.nq - q0 < 8 ? r.nq - q0 : 8;
+    if (gn <= 0) return ~0ull;
+    if (!r.is_lin) return tbl_claim_row(last, r.c0 + q0, gn, t);
+    const int old = tbl_claim(last, r.c0, t);
+    return old < 0 ? ~0ull : ((~0ull << 8) | (unsigned long long)old);
+}
+
+__global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_by_row_kernel(
+    const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
+    AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ backlog) {
+    const int t = clock[0];
+    const int Q = D / 4;
+    const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
+    const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+    const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
+    float zf;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
+    const AdamRow r = adam_row_of(idx, t > 0, X, ldx, cols, vocab, m, B, D, has_lin);
+    const AdamRowsDev R = adam_rows_pick(r.is_lin, emb, lin);
+    float4 *p4 = nullptr, *m4 = nullptr, *v4 = nullptr;
+    unsigned char* last = nullptr;
+    float l2c = 0.f;
+    if (r.nq > 0) {
+        p4 = reinterpret_cast<float4*>(R.p[r.f]) + r.c0;
+        m4 = reinterpret_cast<float4*>(R.m[r.f]) + r.c0;
+        v4 = reinterpret_cast<float4*>(R.v[r.f]) + r.c0;
+        last = R.last[r.f];
+        l2c = R.l2[r.f];
+    }
+    long long fix = 0;
+    for (int q0 = 0; q0 < Q; q0 += 8) {                 // wave-uniform trip counts: every lane reaches every adam_replay_span
+        const unsigned long long olds = adam_row_claim(r, last, q0, t);
+        const int turns = Q - q0 < 8 ? Q - q0 : 8;
+        for (int j = 0; j < turns; ++j) {
+            const int old = (int)((olds >> (8 * j)) & 255ull);
+            const bool act = old != 255;
+            float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), ma = pa, va = pa;
+            if (act) { pa = p4[q0 + j]; ma = m4[q0 + j]; va = v4[q0 + j]; }
+            adam_f2 sq2 = {0.f, 0.f};
+            adam_replay_span(pa, ma, va, act, old, t, consts, 2.f * l2c, zf, c, sq2, eps_ok);
+            if (act) {
+                p4[q0 + j] = pa; m4[q0 + j] = ma; v4[q0 + j] = va;
+                fix += adam_backlog_fix(l2c * (sq2.x + sq2.y));
+            }
+        }
+    }
+    adam_backlog_add_fix(fix, backlog);
+}
+
+// ... and the step's update: as adam_apply_rows_kernel, the 8 * m tail threads behind the row and linear threads
+__global__ __launch_bounds__(ADAM_THREADS) void adam_apply_by_row_kernel(
+    const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
+    AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell, float* __restrict__ l2_value,
+    unsigned* __restrict__ ticket) {
+    const int t = clock[0];
+    const int Q = D / 4;
+    const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
+    const long nrow = (long)B * m * (has_lin ? 2 : 1);
+    const float ss = consts[ADAM_CONSTS_PER_STEP * t], bc = consts[ADAM_CONSTS_PER_STEP * t + 1];
+    const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+    const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
+    float zf;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
+    long long fix = 0;
+    {
+        AdamRow r = adam_row_of(idx, true, X, ldx, cols, vocab, m, B, D, has_lin);
+        const AdamRowsDev R = adam_rows_pick(r.is_lin, emb, lin);
+        float4 *p4 = nullptr, *m4 = nullptr, *v4 = nullptr, *g4 = nullptr;
+        unsigned char *last = nullptr, *marks = nullptr;
+        float l2c = 0.f;
+        if (r.nq > 0 && R.p[r.f] == nullptr) r.nq = 0;  // a null table: left to the step's mark scan (small tables)
+        if (r.nq > 0) {
+            p4 = reinterpret_cast<float4*>(R.p[r.f]) + r.c0;
+            m4 = reinterpret_cast<float4*>(R.m[r.f]) + r.c0;
+            v4 = reinterpret_cast<float4*>(R.v[r.f]) + r.c0;
+            g4 = reinterpret_cast<float4*>(R.g[r.f]) + r.c0;
+            marks = R.marks[r.f] + r.c0;
+            last = R.last[r.f];
+            l2c = R.l2[r.f];
+        }
+        const float g2 = 2.f * l2c;
+        for (int q0 = 0; q0 < Q; q0 += 8) {
+            const unsigned long long olds = adam_row_claim(r, last, q0, t);
+            const int turns = Q - q0 < 8 ? Q - q0 : 8;
+            for (int j = 0; j < turns; ++j) {
+                const int old = (int)((olds >> (8 * j)) & 255ull);
+                const bool act = old != 255;
+                float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), ma = pa, va = pa, ga = pa;
+                if (act) {
+                    pa = p4[q0 + j]; ma = m4[q0 + j]; va = v4[q0 + j]; ga = g4[q0 + j];
+                    g4[q0 + j] = make_float4(zf, zf, zf, zf);
+                    marks[q0 + j] = 0;
+                }
+                adam_f2 sq2 = {0.f, 0.f};
+                adam_replay_span(pa, ma, va, act, old, t - 1, consts, g2, zf, c, sq2, eps_ok);   // the steps the chunk still misses
+                if (act) {                                                                       // then this step, with its gradient
+                    float sq = sq2.x + sq2.y;
+                    sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
+                    ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
+                    adam_one(pa.x, ga.x, ma.x, va.x, ss, bc, c); adam_one(pa.y, ga.y, ma.y, va.y, ss, bc, c);
+                    adam_one(pa.z, ga.z, ma.z, va.z, ss, bc, c); adam_one(pa.w, ga.w, ma.w, va.w, ss, bc, c);
+                    p4[q0 + j] = pa; m4[q0 + j] = ma; v4[q0 + j] = va;
+                    fix += adam_backlog_fix(l2c * sq);
+                }
+            }
+        }
+    }
+    if (idx >= nrow && idx < nrow + 8L * m) {
+        // tail elements: (table kind, field, element k < 4) -- updated every step, like the sweep does
+        const long u = idx - nrow;
+        const int kk = (int)(u & 3);
+        const int f = (int)((u >> 2) % m);
+        const bool is_lin = (u >> 2) >= m;
+        if (!is_lin || has_lin) {
+            const AdamRowsDev R = adam_rows_pick(is_lin, emb, lin);
+            const long numel = (long)vocab[f] * (is_lin ? 1 : D);
+            const long e = numel / 4 * 4 + kk;
+            if (e < numel && R.p[f] != nullptr) {
+                float* p = R.p[f]; float* mm = R.m[f]; float* vv = R.v[f]; float* g = R.g[f];
+                const float l2c = R.l2[f];
+                float pa = p[e], ma = mm[e], va = vv[e];
+                fix += adam_backlog_fix(l2c * (pa * pa));
+                adam_one(pa, fmaf(2.f * l2c, pa, g[e]), ma, va, ss, bc, c);
+                p[e] = pa; mm[e] = ma; vv[e] = va;
+                g[e] = 0.f;
+                R.marks[f][e >> 2] = 0;
+            }
+        }
+    }
+    adam_backlog_add_fix(fix, cell);
+    // adam_rows_finish_kernel's job, by the block that finishes last (every block's integer add is in `cell` by then)
+    if (ticket && xdfm_last_block_done(ticket, gridDim.x) && threadIdx.x == 0) {
+        const unsigned long long tot = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (l2_value) l2_value[0] += (float)((double)(long long)tot / ADAM_FIX);
+        __hip_atomic_store(cell, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 __global__ void adam_rows_finish_kernel(unsigned long long* __restrict__ cell, float* __restrict__ l2_value) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         if (l2_value) l2_value[0] += (float)((double)(long long)cell[0] / ADAM_FIX);
@@ -673,6 +849,14 @@ static int adam_clock_ok(const char* what, const xdfm_adam_clock* clk) {
     return XDFM_OK;
 }
 
+// which kernels xdfm_adam_catchup_rows / _apply_rows launch: by row where a row is whole chunks (every other D: by chunk,
+// whatever the option says); read when the launch is issued, so a captured graph keeps what it was captured with
+static bool adam_by_row(int D) {
+    const bool by_row = D % 4 == 0 && xdfm_opt(OPT_ADAM_ROWS) != 0;
+    xdfm_opt_note(OPT_LAST_ADAM_ROWS, by_row ? 1 : 0);
+    return by_row;
+}
+
 extern "C" {
 
 size_t xdfm_adam_step_ws_elems(int T) { return T > 0 ? (size_t)T * ADAM_BX : 0; }
@@ -757,11 +941,16 @@ int xdfm_adam_catchup_rows(const float* X, long ldx, int B, const int* cols, con
     XDFM_REQUIRE((((size_t)backlog) & 7) == 0, "adam_catchup_rows: backlog must be 8-byte aligned");
     const AdamRowsDev e = {emb->param, emb->exp_avg, emb->exp_avg_sq, emb->last, emb->l2, nullptr, nullptr};
     const AdamRowsDev l = lin ? AdamRowsDev{lin->param, lin->exp_avg, lin->exp_avg_sq, lin->last, lin->l2, nullptr, nullptr} : e;
-    const int QT = (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);
+    const bool by_row = adam_by_row(D);
+    const int QT = by_row ? (lin ? 2 : 1) : (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);      // threads per (example, field)
     const long threads = (long)B * m * QT;
-    hipLaunchKernelGGL(adam_catchup_rows_kernel, dim3((unsigned)ceil_div(threads, (long)ADAM_THREADS)), dim3(ADAM_THREADS), 0,
-                       (hipStream_t)stream, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2,
-                       eps, reinterpret_cast<unsigned long long*>(backlog));
+    const dim3 grid((unsigned)ceil_div(threads, (long)ADAM_THREADS));
+    if (by_row)
+        hipLaunchKernelGGL(adam_catchup_by_row_kernel, grid, dim3(ADAM_THREADS), 0, (hipStream_t)stream, X, ldx, B, cols, vocab, m, D,
+                           e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog));
+    else
+        hipLaunchKernelGGL(adam_catchup_rows_kernel, grid, dim3(ADAM_THREADS), 0, (hipStream_t)stream, X, ldx, B, cols, vocab, m, D,
+                           e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog));
     return xdfm_check_launch("adam_catchup_rows");
 }
 
@@ -776,13 +965,18 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
     XDFM_REQUIRE((((size_t)l2_cell) & 7) == 0, "adam_apply_rows: l2_cell must be 8-byte aligned");
     const AdamRowsDev e = {emb->param, emb->exp_avg, emb->exp_avg_sq, emb->last, emb->l2, emb->grad, emb->marks};
     const AdamRowsDev l = lin ? AdamRowsDev{lin->param, lin->exp_avg, lin->exp_avg_sq, lin->last, lin->l2, lin->grad, lin->marks} : e;
-    const int QT = (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);
+    const bool by_row = adam_by_row(D);
+    const int QT = by_row ? (lin ? 2 : 1) : (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);
     const long threads = (long)B * m * QT + 8L * m;
+    const dim3 grid((unsigned)ceil_div(threads, (long)ADAM_THREADS));
     hipStream_t st = (hipStream_t)stream;
     unsigned* ticket = nullptr;      // thousands of blocks: the finish stays a launch of its own (tickets on one address serialise)
-    hipLaunchKernelGGL(adam_apply_rows_kernel, dim3((unsigned)ceil_div(threads, (long)ADAM_THREADS)), dim3(ADAM_THREADS), 0, st, X, ldx,
-                       B, cols, vocab, m, D, e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2, eps,
-                       reinterpret_cast<unsigned long long*>(l2_cell), l2_value, ticket);
+    if (by_row)
+        hipLaunchKernelGGL(adam_apply_by_row_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0,
+                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell), l2_value, ticket);
+    else
+        hipLaunchKernelGGL(adam_apply_rows_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0,
+                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell), l2_value, ticket);
     if (!ticket)
         hipLaunchKernelGGL(adam_rows_finish_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long*>(l2_cell), l2_value);
     return xdfm_check_launch("adam_apply_rows");

@@ -1,6 +1,6 @@
 // What the table optimizers' translation units share beside their arithmetic (adam_math.h, opt_math.h): K7 / K7d
 // (adam.hip), K7s / K7g / K7r (sgd_adagrad.hip) and K7sd / K7gd / K7rd (sgd_adagrad_deferred.hip).
-//   device: the streaming float4 accesses, and the claim of a deferred chunk through its `last` byte
+//   device: the streaming float4 accesses, and the claim of a deferred chunk (or of a row's chunks) through `last`
 //   host:   the composition of a launch -- which tensors it takes, and each tensor's share of its 1-D grid
 // Everything here is inlined into the kernels and launchers of the three files; none of it has a symbol of its own.
 #pragma once
@@ -49,6 +49,42 @@ __device__ __forceinline__ int tbl_claim(unsigned char* last, long cc, int t) {
         seen = got;
     }
     return old;
+}
+
+// The claim of the n <= 8 consecutive chunks cc0 .. cc0 + n - 1 (a table row, or a piece of one) by ONE thread: per `last`
+// word the chunks' bytes fall into, one CAS that sets every one of them that is below t to t.  The other bytes of the word
+// (2 or 4 rows share a word at D = 8 / 4, and their lanes sit in the same wave) pass through as they were seen; a CAS that
+// finds the word changed starts over from the word it returned, where more of the row's bytes may be at t by then.
+// -> byte j = the step chunk cc0 + j was at, which the caller has to bring it up from, or 255 (never a step: t <= 255)
+// for a chunk that is at t already -- someone else's, or done -- and for j >= n.
+__device__ __forceinline__ unsigned long long tbl_claim_row(unsigned char* last, long cc0, int n, int t) {
+    unsigned long long olds = ~0ull;
+    const long end = cc0 + n;
+    for (long w0 = cc0 & ~3L; w0 < end; w0 += 4) {
+        unsigned* word = reinterpret_cast<unsigned*>(last + w0);
+        const int lo = (int)(cc0 - w0), hi = (int)(end - w0);       // the row's bytes of this word: lo <= b < hi
+        unsigned seen = *word;          // plain read, as tbl_claim's
+        while (true) {
+            unsigned mine = 0u;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (b >= lo && b < hi && ((seen >> (8 * b)) & 255u) < (unsigned)t) mine |= 255u << (8 * b);
+            if (!mine) break;
+            const unsigned want = (seen & ~mine) | (((unsigned)t * 0x01010101u) & mine);
+            const unsigned got = atomicCAS(word, seen, want);
+            if (got == seen) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if ((mine >> (8 * b)) & 1u) {
+                        const int sh = 8 * (b - lo);                 // b - lo = the chunk's index in the run (lo < 0: later words)
+                        olds = (olds & ~(255ull << sh)) | ((unsigned long long)((seen >> (8 * b)) & 255u) << sh);
+                    }
+                break;
+            }
+            seen = got;
+        }
+    }
+    return olds;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -38,6 +38,8 @@ enum {
     OPT_LAST_FWD_F32,    // read-only probes: template instance of the last fp32-MFMA forward / dX / dW launch (f32_*_code below),
     OPT_LAST_BWX_F32,    //   0 when the call ran an f16x3 / bf16 kernel, -1 before the first call
     OPT_LAST_BWW_F32,
+    OPT_ADAM_ROWS,       // 1 (default) = xdfm_adam_catchup_rows / _apply_rows give a thread a whole row where D % 4 == 0; 0 = a chunk
+    OPT_LAST_ADAM_ROWS,  // read-only probe: 1 / 0 = the last of those two calls launched the by-row / the by-chunk kernel, -1 before
     OPT_COUNT
 };
 // value of the instance probes: row tiles (forward MT, dX HBT, dW MT) * 1000 + waves * 100 + MFMA terms * 10 + folded level 0
