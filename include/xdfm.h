@@ -263,7 +263,8 @@ int xdfm_varlen_pool_bwd_rows(const float* X, long ldx, int R, const xdfm_varlen
  * gradients.  The dense gradient tables live in ONE caller-initialised buffer d_flat (zeros, or the
  * L2 gradient written by xdfm_l2_reg_bwd): table j starts at d_flat + tab_off[j], its linear table
  * at d_flat + lin_off[j] (device long[m], element offsets; either may be NULL); d_dense_w [nd] is added to as well.
- * No atomics: per field the (id, example) keys of a chunk of <= 4096 examples are sorted in LDS, runs of equal ids
+ * No atomics on the gradients: per field the examples of a chunk of <= 4096 are grouped by id through a hash table in LDS
+ * (equal ids end up adjacent, the groups in no particular order; embed_scatter_grouped_kernel), runs of equal ids
  * are summed EXACTLY (addends rounded once to a fixed-point grid 2^-13 ulp below the run's largest magnitude, added
  * as integers in doubles, rounded once to fp32) and added to d_flat by one lane per row.  The result is a function
  * of the multiset of rows: bit-identical from run to run, under any permutation of the examples of a chunk and on

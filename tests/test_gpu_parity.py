@@ -763,7 +763,8 @@ def _scatter_expected(X, vocab, nd, D, d_emb, d_dnn, d_lin):
     (1, [4, 4], 0, 3, "e"),
 ])
 def test_scatter_is_exact_deterministic_and_order_independent(B, vocab, nd, D, srcs):
-    """K2 (`embed_scatter_sorted_kernel`): sorted, segmented, atomics-free reduce of the row gradients.  Checked here:
+    """K2 (`embed_scatter_grouped_kernel`): the examples of a chunk are grouped by id through a hash table in LDS (equal ids
+    adjacent, the groups in no particular order), then a segmented, atomics-free reduce of the row gradients.  Checked here:
     (1) every element is the EXACT sum of its addends rounded to fp32, to within one ulp (float64 reference; an addend
         more than 2^14 below the largest of its run is first rounded to a grid 2^-13 fp32-ulp fine, which can turn a
         near-tie of the final rounding; the reference's CPU `embedding_dense_backward`, deepctr/inputs.py:168, sums
