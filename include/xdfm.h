@@ -141,6 +141,11 @@ int xdfm_device_count(void);                /* <0: HIP error code negated */
  * (one claim per `last` word of the row, the row's chunks in turn) instead of one thread per 16-byte chunk; 0 = by chunk,
  * which is what every other D runs.  Same bits either way; read when the call issues its launch.  Probe "last_adam_rows":
  * 1 / 0 = the last of those two calls launched the by-row / the by-chunk kernel, -1 before the first call. */
+/* "opt_bx" (default 0), the counterpart of "adam_bx" for xdfm_sgd_step / _adagrad_step / _rmsprop_step, their _deferred forms
+ * and xdfm_opt_flush / xdfm_rmsprop_flush: the most workgroups one tensor gets in a launch.  0, negative values and values
+ * above the built-in caps (512 in the sweep and in the deferred step's scan, 4096 in the flush) mean those caps.  Read when
+ * the call composes its launch; it changes the grid only -- same arithmetic, same bits, and xdfm_opt_step_ws_elems(T) stays
+ * T * 512.  A test knob: at 1 a tensor is one workgroup, whose loops then run many times at small sizes. */
 int xdfm_set_option(const char* key, int value);
 int xdfm_get_option(const char* key);
 /* Ticket board: `board` = a DEVICE array of `slots` >= 1040 unsigned ints, zeroed once by the caller and kept alive, registered

@@ -27,6 +27,29 @@ def test_new_symbols_are_declared_bound_and_exported():
     assert lib.xdfm_opt_step_ws_elems(0) == 0 and lib.xdfm_opt_step_ws_elems(3) >= 3
 
 
+def test_option_opt_bx_round_trips_and_adds_no_symbol():
+    """Option "opt_bx" (most blocks one tensor gets in the sweep, the deferred scan and the flush; a test knob): 0 by default,
+    set / get round trip, out-of-range values are stored as given and mean the built-in caps when a call composes its
+    launch; the workspace stays T * 512 floats and the family's entry points are the ones it had."""
+    from xdfm_amd import _lib
+    lib = _lib.load()
+    assert _lib.get_option("opt_bx") == 0
+    try:
+        for v in (1, 7, 512, 100000, -3, 0):
+            _lib.set_option("opt_bx", v)
+            assert _lib.get_option("opt_bx") == v
+            assert lib.xdfm_opt_step_ws_elems(3) == 3 * 512
+    finally:
+        _lib.set_option("opt_bx", 0)
+    assert _lib.get_option("adam_bx") == 0 and _lib.get_option("no_such_option") == -1
+    # an option is no ABI change: the version and the entry points of this family are what they were
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8
+    assert sorted(k for k in _lib.SIGNATURES if k.startswith(("xdfm_opt_", "xdfm_sgd_", "xdfm_adagrad_", "xdfm_rmsprop_"))) == [
+        "xdfm_adagrad_step", "xdfm_adagrad_step_deferred", "xdfm_opt_catchup_rows", "xdfm_opt_flush", "xdfm_opt_step_ws_elems",
+        "xdfm_rmsprop_catchup_rows", "xdfm_rmsprop_flush", "xdfm_rmsprop_step", "xdfm_rmsprop_step_deferred", "xdfm_sgd_step",
+        "xdfm_sgd_step_deferred"]
+
+
 def test_bad_arguments_are_refused_before_any_device_work():
     from xdfm_amd import _lib
     lib = _lib.load()

@@ -5,6 +5,7 @@
 // Both units are compiled with the same flags: sqrtf and / expand to hipcc's correctly rounded sequences in either.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "xdfm_internal.h"     // xdfm_opt
 
 // The optimizer a kernel instance is for.  SGD has no state; Adagrad's and RMSprop's `s` is the accumulator.
 enum OptKind { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_RMSPROP = 2 };
@@ -14,6 +15,13 @@ struct OptHyper { float eps, alpha, oma; };
 static inline OptHyper opt_hyper(int kind, double eps, double alpha) {
     return OptHyper{kind == OPT_SGD ? 0.f : (float)eps, kind == OPT_RMSPROP ? (float)alpha : 0.f,
                     kind == OPT_RMSPROP ? (float)(1.0 - alpha) : 0.f};
+}
+
+// Most blocks one tensor gets in a launch of these kernels (host side): the kernel's built-in cap, or option "opt_bx" where it
+// is in (0, built-in] -- read when the call composes its launch; the grid changes, the arithmetic and the results do not.
+static inline int opt_bx_cap(int builtin) {
+    const int o = xdfm_opt(OPT_OPT_BX);
+    return o > 0 && o < builtin ? o : builtin;
 }
 
 // One element.  The fusions are spelled out and the compiler's own contraction is off, so that the marked, the dense, the

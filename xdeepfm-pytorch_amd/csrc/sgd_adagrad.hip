@@ -236,7 +236,7 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
             const xdfm_opt_tensor& x = tensors[order[k]];
             batch.t[cnt++] = OptDev{x.param, x.grad, x.state, x.grad_marks, x.numel, x.l2};
         }
-        tbl_grid(batch, cnt, OPT_BLOCK_ELEMS, OPT_BX);
+        tbl_grid(batch, cnt, OPT_BLOCK_ELEMS, opt_bx_cap(OPT_BX));      // option "opt_bx" caps the blocks per tensor (tests)
         hipLaunchKernelGGL(opt_step_kernel<K>, dim3(batch.first[cnt]), dim3(OPT_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev,
                            opt_hyper(K, eps, alpha), l2_value ? l2_ws : nullptr);
         slot0 += batch.first[cnt];

@@ -372,7 +372,7 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
         OptDefBatch batch;
         const int cnt = n - l0 < OPTD_CHUNK ? n - l0 : OPTD_CHUNK;
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[def[l0 + k]], last[def[l0 + k]]);
-        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, OPTD_BX);
+        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, opt_bx_cap(OPTD_BX));
         hipLaunchKernelGGL(opt_step_deferred_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock,
                            clk->rates, opt_hyper(K, eps, alpha), clk->backlog, clk->cell);
     }
@@ -402,7 +402,7 @@ static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* 
         OptDefBatch batch;
         const int cnt = T - l0 < OPTD_CHUNK ? T - l0 : OPTD_CHUNK;
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[l0 + k], last[l0 + k]);
-        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, OPTD_FLUSH_BX);
+        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, opt_bx_cap(OPTD_FLUSH_BX));
         hipLaunchKernelGGL(opt_flush_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock, clk->rates,
                            opt_hyper(K, eps, alpha), clk->backlog);
     }

@@ -40,6 +40,8 @@ enum {
     OPT_LAST_BWW_F32,
     OPT_ADAM_ROWS,       // 1 (default) = xdfm_adam_catchup_rows / _apply_rows give a thread a whole row where D % 4 == 0; 0 = a chunk
     OPT_LAST_ADAM_ROWS,  // read-only probe: 1 / 0 = the last of those two calls launched the by-row / the by-chunk kernel, -1 before
+    OPT_OPT_BX,          // 0 = default (512 / 512 / 4096: OPT_BX, OPTD_BX, OPTD_FLUSH_BX); most blocks one tensor gets in the
+                         //   SGD / Adagrad / RMSprop sweep, deferred step scan and flush
     OPT_COUNT
 };
 // value of the instance probes: row tiles (forward MT, dX HBT, dW MT) * 1000 + waves * 100 + MFMA terms * 10 + folded level 0
