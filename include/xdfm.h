@@ -66,6 +66,8 @@
  * version stays 8.
  * xdfm_varlen_pool_bwd / _bwd_rows: an XDFM_POOL_MAX field now sends the gradient of an all-masked sequence to the recorded
  * (masked) position instead of dropping it -- a correction of the values, no struct or signature changed, the version stays 8.
+ * xdfm_sgdm_step, xdfm_sgdm_step_deferred, xdfm_sgdm_catchup_rows, xdfm_sgdm_flush (K7m / K7md: SGD with momentum, plain or
+ * Nesterov; xdfm_opt_tensor keeps its 48 bytes, `state` is the momentum buffer) -- additions, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -761,7 +763,7 @@ int xdfm_adam_step_lr(const xdfm_adam_tensor* tensors, int T, double lr, const d
 typedef struct {
     float* param;
     float* grad;
-    float* state;                   /* Adagrad: the accumulator ("sum"); RMSprop: "square_avg"; SGD: NULL */
+    float* state;                   /* Adagrad: the accumulator ("sum"); RMSprop: "square_avg"; SGD with momentum: "momentum_buffer"; SGD: NULL */
     long numel;
     float l2;
     unsigned char* grad_marks;      /* NULL: grad is read in full and left alone */
@@ -781,6 +783,18 @@ int xdfm_adagrad_step(const xdfm_opt_tensor* tensors, int T, double lr, const do
  * outside [0, 1), a tensor without `state`) are reported before any device work. */
 int xdfm_rmsprop_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double alpha, double eps,
                       float* l2_ws, float* l2_value, void* stream);
+/* SGD with momentum (K7m) -- replaces: torch.optim.SGD(params, momentum=mu[, nesterov=True]).step() -- for dampening 0, no
+ * weight decay, not maximize: the same sweep, descriptors (`state` is torch's "momentum_buffer"), rate, L2 term and marks,
+ * 16 bytes per parameter, one fma per line of torch/optim/sgd.py:
+ *   g' = fma(2 l2, p, g);   buf = fma(mu, buf, g');   d = nesterov ? fma(mu, buf, g') : buf;   p = fma(-lr, d, p)
+ * with mu rounded to float.  The buffer is signed and moves its weight in every step whatever the gradient, so the exact
+ * shortcut of K7s / K7g does not apply, with or without an L2 term: an unmarked chunk is computed with g = 0 like any other
+ * (RMSprop's rule; here p moves too).  Marks on / off give the same bits.  torch makes the buffer at the first step as
+ * clone(g'); a zero buffer gives the same value (mu * 0 + g'), but for the sign of a zero.  Errors (as above; mu outside
+ * (0, 1), a tensor without `state` or with one that is not 4-byte aligned -- 16-byte with grad_marks) are reported before any
+ * device work, with the offending value in the message. */
+int xdfm_sgdm_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double mu, int nesterov, float* l2_ws,
+                   float* l2_value, void* stream);
 
 /* ------------------------------------------------------------------ deferred Adam for the tables (K7d)
  * Same arithmetic, same results, bit for bit, as the dense sweep above -- but the sweep's 24 bytes per table parameter
@@ -904,6 +918,17 @@ int xdfm_rmsprop_catchup_rows(const float* X, long ldx, int B, const int* cols, 
                               double eps, void* stream);
 int xdfm_rmsprop_flush(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double alpha,
                        double eps, void* stream);
+/* K7md: the same three for SGD with momentum.  An untouched row with l2 > 0 evolves by g' = 2 l2 p, buf = fma(mu, buf, g'),
+ * d = nesterov ? fma(mu, buf, g') : buf, p = fma(-lr_t, d, p): buffer and weight both move in a replayed step.  Clock, `last`
+ * bytes, backlog and cell are those of K7sd / K7gd, and so are the errors (plus mu outside (0, 1) and a missing or misaligned
+ * state).  mu and nesterov are part of what a window of deferred steps assumes: flush before either changes.  A tensor
+ * with l2 == 0 is not deferred (the sweep takes it: 16 bytes per parameter and step). */
+int xdfm_sgdm_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
+                            double lr, const double* lr_dev, double mu, int nesterov, float* l2_ws, float* l2_value, void* stream);
+int xdfm_sgdm_catchup_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D, const xdfm_opt_rows* emb,
+                           const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double mu, int nesterov, void* stream);
+int xdfm_sgdm_flush(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double mu, int nesterov,
+                    void* stream);
 
 /* Test hook: compares the replay's short forms (csrc/adam_math.h) with the reference spellings ON THE DEVICE.
  * mode 0: square root, n = 2^32 bit patterns; 1: division by a step's constant, n = steps * 2^24 numerators; 2: general

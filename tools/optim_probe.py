@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the train step with `compile("sgd")` / `compile("adagrad")` / `compile("rmsprop")` (K7s / K7g / K7r: native sweep,
+"""A/B of the train step with `compile("sgd")` / `compile("adagrad")` / `compile("rmsprop")` (K7s / K7g / K7r; K7m with --momentum: native sweep,
 fused L2 term, marked gradients, graph replay) against the stock path the same strings took before (a torch.optim.SGD /
 Adagrad / RMSprop OBJECT handed
 to compile: eager launches, K6 value pass, table-sized L2 gradients, zero-filled dense table gradients).
@@ -15,8 +15,13 @@ the native sweep (`deferred=False`).  Its timed blocks end with a flush inside t
 the flush period, so every deferred update is paid for inside the time reported.  For that arm the tool also prints the
 flush (ms per flush, and amortised over the period) and the catch-up launch (us), from HIP events around them.
 
+With `--momentum MU` (and `--nesterov`), `sgd` is SGD with momentum (K7m / K7md): every arm builds
+xdfm_amd.optim.TableSGD(momentum=MU) and hands the object to compile; `sweep` and `deferred` run with XDFM_SGD_MOMENTUM_NATIVE on,
+`stock` with it off -- the fallback the class took before (flush, the L2 term by hand, torch.optim.SGD.step over dense
+gradients).  The switch is a module attribute that is set in front of every block.
+
     python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad,rmsprop] [--arms sweep,deferred,stock]
-                                [--out FILE.json]
+                                [--momentum 0.9 [--nesterov]] [--out FILE.json]
 """
 import argparse
 import json
@@ -33,13 +38,24 @@ import torch                                     # noqa: E402
 import bench                                     # noqa: E402
 
 
-def build(cfg, vocab, dev, optimizer, stock, deferred=False):
+def route(model):
+    """The route a model of this probe takes through TableSGD with a momentum: set in front of everything that steps it."""
+    from xdfm_amd import optim
+    optim.SGD_MOMENTUM_NATIVE = getattr(model, "_probe_native", True)
+
+
+def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, nesterov=False):
     from deepctr.inputs import DenseFeat, SparseFeat
     from deepctr.models import xDeepFM
     cols = [SparseFeat("C%d" % (i + 1), v, cfg["emb_dim"]) for i, v in enumerate(vocab)]
     cols += [DenseFeat("I%d" % (i + 1), 1) for i in range(cfg["n_dense"])]
     model = xDeepFM(cols, cols, dnn_hidden_units=cfg["dnn"], cin_layer_size=cfg["cin"], l2_reg_dnn=1e-5, device=dev)
-    if stock:
+    if optimizer == "sgd" and momentum:
+        from xdfm_amd.optim import TableSGD
+        opt = TableSGD(model.parameters(), lr=0.01, momentum=momentum, nesterov=nesterov, deferred=bool(deferred))
+        model.compile(opt, "binary_crossentropy", metrics=[])
+        model._probe_native = not stock
+    elif stock:
         opt = {"sgd": lambda p: torch.optim.SGD(p, lr=0.01), "adagrad": torch.optim.Adagrad,
                "rmsprop": torch.optim.RMSprop}[optimizer](model.parameters())
         model.compile(opt, "binary_crossentropy", metrics=[])
@@ -47,12 +63,13 @@ def build(cfg, vocab, dev, optimizer, stock, deferred=False):
         model.compile(optimizer, "binary_crossentropy", metrics=[])
         model.optim.deferred = bool(deferred)
     for pg in model.optim.param_groups:          # a rate at which a sum-reduced loss over 4096 rows stays finite
-        pg["lr"] = {"sgd": 1e-5, "adagrad": 1e-3, "rmsprop": 1e-4}[optimizer]
+        pg["lr"] = {"sgd": 1e-5 * (1.0 - momentum), "adagrad": 1e-3, "rmsprop": 1e-4}[optimizer]
     model.train()
     return model
 
 
 def timed(model, batches, steps, k0):
+    route(model)
     t0 = time.perf_counter()
     for k in range(steps):
         xb, yb = batches[(k0 + k) % len(batches)]
@@ -66,6 +83,7 @@ def timed(model, batches, steps, k0):
 
 def deferred_parts(model, batches, reps=3):
     """(ms per flush after a full period of steps, us per catch-up launch) of a model on the deferred path, by HIP events."""
+    route(model)
     opt = model.optim
     plan = model._gather_plan()
     flush_ms, catch_us = [], []
@@ -96,6 +114,7 @@ def deferred_parts(model, batches, reps=3):
 
 
 def eager_launches(model, batches):
+    route(model)
     try:
         from torch.profiler import ProfilerActivity, profile
         with profile(activities=[ProfilerActivity.CUDA]) as prof:
@@ -111,6 +130,7 @@ def eager_launches(model, batches):
 def kernel_rate(model, batches, optimizer):
     """(bytes by the byte model, seconds) of the sweep kernel per step, from HIP events around its launches (eager steps)."""
     from xdfm_amd import ops
+    route(model)
     ops.PROFILE = []
     try:
         for k in range(10):
@@ -129,10 +149,16 @@ def main():
     ap.add_argument("--block", type=int, default=128, help="steps per alternating block (longer than the flush period)")
     ap.add_argument("--warmup", type=int, default=12)
     ap.add_argument("--vocab", default="mid,criteo-card")
-    ap.add_argument("--optimizers", default="sgd,adagrad,rmsprop")
+    ap.add_argument("--optimizers", "--optimizer", dest="optimizers", default="sgd,adagrad,rmsprop")
+    ap.add_argument("--momentum", type=float, default=0.0, help="sgd only: SGD with this momentum, in (0, 1) (K7m)")
+    ap.add_argument("--nesterov", action="store_true", help="with --momentum: Nesterov momentum")
     ap.add_argument("--arms", default="sweep,deferred,stock")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if (args.momentum or args.nesterov) and args.optimizers != "sgd":
+        ap.error("--momentum / --nesterov need --optimizer sgd")
+    if not 0.0 <= args.momentum < 1.0 or (args.nesterov and not args.momentum):
+        ap.error("--momentum must be in [0, 1), and --nesterov needs one above 0")
     dev = torch.device("cuda:0")
     cfg = bench.WORKLOADS["criteo_c2"]
     B = cfg["batch"]
@@ -143,25 +169,37 @@ def main():
         batches = [(torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev))
                    for X, y in bench.synthetic_batches(8, B, vocab, cfg["n_dense"], seed=2025)]
         for optimizer in args.optimizers.split(","):
-            models = {a: build(cfg, vocab, dev, optimizer, stock=a == "stock", deferred=a == "deferred") for a in arms}
+            models = {a: build(cfg, vocab, dev, optimizer, stock=a == "stock", deferred=a == "deferred", momentum=args.momentum,
+                               nesterov=args.nesterov) for a in arms}
+            kernel = "sgdm" if optimizer == "sgd" and args.momentum else optimizer
             for m in models.values():
                 timed(m, batches, args.warmup, 0)
             native = models.get("sweep", models.get("deferred"))
             n_table = sum(t.numel() for t in native._gather_tables()) if native is not None else 0
             secs = {a: 0.0 for a in arms}
+            blocks = {a: [] for a in arms}
             done = 0
             while done < args.steps:
                 n = min(args.block, args.steps - done)
                 for a in arms:
-                    secs[a] += timed(models[a], batches, n, done)
+                    dt = timed(models[a], batches, n, done)
+                    secs[a] += dt
+                    blocks[a].append(round(dt / n * 1e3, 4))
                 done += n
             row = dict(vocab=preset, table_params=n_table, optimizer=optimizer, steps=args.steps, block=args.block)
+            if args.momentum:
+                row.update(momentum=args.momentum, nesterov=args.nesterov)
             for a in arms:
                 row["ms_" + a] = round(secs[a] / args.steps * 1e3, 4)
+                row["ms_blocks_" + a] = blocks[a]            # per alternating block: the spread
             if "sweep" in models:
                 step = models["sweep"].__dict__["_graphed_step"]
                 nodes = [e.nodes for e in step.entries.values() if e.graph is not None]
-                nbytes, ksecs = kernel_rate(models["sweep"], batches, optimizer)
+                if "stock" in models and args.momentum:
+                    st = models["stock"].__dict__.get("_graphed_step")
+                    row["graph_nodes_stock"] = ([e.nodes for e in st.entries.values() if e.graph is not None] or [None])[0] if st else None
+                    row["replays_stock"] = st.replays if st else 0
+                nbytes, ksecs = kernel_rate(models["sweep"], batches, kernel)
                 row.update(replays=step.replays, graph_nodes=nodes[0] if nodes else None, sweep_bytes=int(nbytes),
                            sweep_us=round(ksecs * 1e6, 2), sweep_TBps=round(nbytes / ksecs / 1e12, 3))
             if "stock" in models:
@@ -171,7 +209,7 @@ def main():
             if "deferred" in models:
                 opt = models["deferred"].optim
                 flush_ms, catch_us = deferred_parts(models["deferred"], batches)
-                nbytes, ksecs = kernel_rate(models["deferred"], batches, optimizer)
+                nbytes, ksecs = kernel_rate(models["deferred"], batches, kernel)
                 opt.flush()
                 row.update(flush_every=opt.flush_every, deferred_steps=opt.path_counts["scan"], flush_ms=round(flush_ms, 3),
                            flush_ms_per_step=round(flush_ms / opt.flush_every, 4), catchup_us=round(catch_us, 1),

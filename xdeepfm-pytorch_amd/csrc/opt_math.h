@@ -1,5 +1,5 @@
-// The element update of the SGD / Adagrad / RMSprop steps (K7s / K7g / K7r, sgd_adagrad.hip) and of their deferred form
-// (K7sd / K7gd / K7rd, sgd_adagrad_deferred.hip): ONE definition, included by both translation units.  The deferred kernels replay the steps a
+// The element update of the SGD / Adagrad / RMSprop / SGD-with-momentum steps (K7s / K7g / K7r / K7m, sgd_adagrad.hip) and of
+// their deferred form (K7sd / K7gd / K7rd / K7md, sgd_adagrad_deferred.hip): ONE definition, included by both translation units.  The deferred kernels replay the steps a
 // chunk missed by calling this very function with g = 0 (an opaque zero, as the sweep's unmarked chunks do) and the rate
 // the missed step used -- the bit identity of the two paths rests on there being nothing else that spells the arithmetic.
 // Both units are compiled with the same flags: sqrtf and / expand to hipcc's correctly rounded sequences in either.
@@ -7,15 +7,27 @@
 #include <hip/hip_runtime.h>
 #include "xdfm_internal.h"     // xdfm_opt
 
-// The optimizer a kernel instance is for.  SGD has no state; Adagrad's and RMSprop's `s` is the accumulator.
-enum OptKind { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_RMSPROP = 2 };
-// `eps` and RMSprop's decay, as floats (1 - alpha is taken in double on the host, as Python takes it)
-struct OptHyper { float eps, alpha, oma; };
-// eps and alpha as the kernels take them (host side)
-static inline OptHyper opt_hyper(int kind, double eps, double alpha) {
-    return OptHyper{kind == OPT_SGD ? 0.f : (float)eps, kind == OPT_RMSPROP ? (float)alpha : 0.f,
-                    kind == OPT_RMSPROP ? (float)(1.0 - alpha) : 0.f};
+// The optimizer a kernel instance is for.  SGD has no state; Adagrad's and RMSprop's `s` is the accumulator; SGDM is SGD with
+// momentum (dampening 0), plain or Nesterov, and its `s` is torch's signed `momentum_buffer`.
+enum OptKind { OPT_SGD = 0, OPT_ADAGRAD = 1, OPT_RMSPROP = 2, OPT_SGDM = 3 };
+// `eps` and RMSprop's decay, as floats (1 - alpha is taken in double on the host, as Python takes it); SGDM's momentum as a
+// float and whether the step is Nesterov's (one value per launch: a wave-uniform select in the element update)
+struct OptHyper { float eps, alpha, oma, mu; int nesterov; };
+// what every kind but SGDM passes for SGDM's two
+struct OptMom { double mu; int nesterov; };
+static const OptMom OPT_NO_MOM = {0.0, 0};
+// what a kind's `state` is, for the messages (host side)
+static inline const char* opt_state_name(int kind) { return kind == OPT_SGDM ? "the momentum buffer" : "the accumulator"; }
+// eps, alpha and the momentum as the kernels take them (host side)
+static inline OptHyper opt_hyper(int kind, double eps, double alpha, OptMom m = OPT_NO_MOM) {
+    const bool acc = kind == OPT_ADAGRAD || kind == OPT_RMSPROP;
+    return OptHyper{acc ? (float)eps : 0.f, kind == OPT_RMSPROP ? (float)alpha : 0.f,
+                    kind == OPT_RMSPROP ? (float)(1.0 - alpha) : 0.f, kind == OPT_SGDM ? (float)m.mu : 0.f,
+                    kind == OPT_SGDM && m.nesterov ? 1 : 0};
 }
+// kinds whose state moves in every step whatever the gradient (RMSprop's accumulator decays, SGDM's buffer decays and moves its
+// weight): an unmarked chunk of a tensor without an L2 term is no no-op for them, so the sweep's exact shortcut is off
+template <int K> struct OptMoves { static constexpr bool V = K == OPT_RMSPROP || K == OPT_SGDM; };
 
 // Most blocks one tensor gets in a launch of these kernels (host side): the kernel's built-in cap, or option "opt_bx" where it
 // is in (0, built-in] -- read when the call composes its launch; the grid changes, the arithmetic and the results do not.
@@ -38,6 +50,19 @@ __device__ __forceinline__ void opt_one(float& p, float& s, float g, float g2, f
         // mul_(alpha), then addcmul_(g, g, 1 - alpha) whose a + value * (b * c) contracts into one fma; addcdiv_ as Adagrad's
         s = fmaf(h.oma, gp * gp, h.alpha * s);
         p = fmaf(nlr, gp / (sqrtf(s) + h.eps), p);
+    } else if constexpr (K == OPT_SGDM) {
+        // torch/optim/sgd.py with dampening 0: buf.mul_(mu).add_(g'), then g'.add(buf, alpha=mu) for Nesterov, then
+        // p.add_(d, alpha=-lr).  One fma per line.  Found by one bitwise comparison on an MI355X (tools/sgd_contract_probe.py;
+        // the run is recorded in profiles/sgdm_probe.md) of torch.optim.SGD's step
+        // (foreach on and off, 2^20 elements, plain and Nesterov) with the eight fp32 spellings of the three lines: ATen's
+        // two add(alpha=) kernels contract a + alpha * b into one fma (0 mismatches for d and p as written here, 25163 and
+        // 32372 without the contraction), and mul_ / add_, two kernels, round mu * buf on its own.  So the last two lines
+        // MATCH torch's bits; the first does not and cannot by contraction -- it keeps the product exact, the more accurate
+        // spelling, and differs from torch's buffer by at most half an ulp of mu * buf (146398 of 2^20 elements differ).
+        // tests/test_sgdm_reference.py holds both spellings to half of the float64 bars.
+        s = fmaf(h.mu, s, gp);
+        const float d = h.nesterov ? fmaf(h.mu, s, gp) : s;
+        p = fmaf(nlr, d, p);
     } else {
         p = fmaf(nlr, gp, p);
     }

@@ -1,7 +1,8 @@
-// K7s / K7g / K7r: SGD (momentum 0), Adagrad (lr_decay 0) and RMSprop (momentum 0, not centered) steps over all
+// K7s / K7g / K7r / K7m: SGD (momentum 0), Adagrad (lr_decay 0), RMSprop (momentum 0, not centered) and SGD with momentum
+// (K7m: dampening 0, plain or Nesterov) steps over all
 // parameters -- the streaming sweep of K7 (adam.hip) for the other optimizers the trainer offers (xdftrain.py:723
 // --optimizer adam|adagrad|sgd; "rmsprop" is the fourth string of deepctr/models/basemodel.py:447-461).  One kernel
-// template, three instances.
+// template, four instances.
 //
 // replaces torch.optim.SGD.step() / torch.optim.Adagrad.step() plus the passes the stock path needs around them
 // (zero fill of the dense table gradients, value and gradient of the L2 term).  Per parameter and step the sweep
@@ -18,6 +19,10 @@
 //   RMSprop:  v = fma(1 - alpha, g' g', alpha v);   p = fma(-lr, g' / (sqrt(v) + eps), p)   (torch/optim/rmsprop.py: mul_(alpha),
 //             addcmul_(g, g, 1 - alpha), sqrt().add_(eps), addcdiv_).  v decays in EVERY step, so for RMSprop an unmarked chunk of
 //             a tensor without an L2 term is no no-op: it is computed like any other (16 bytes per parameter), g' = 0 leaves p's bits.
+//   SGDM:     buf = fma(mu, buf, g');   d = nesterov ? fma(mu, buf, g') : buf;   p = fma(-lr, d, p)   (torch/optim/sgd.py, dampening 0:
+//             buf.mul_(mu).add_(g'), g'.add(buf, alpha=mu), p.add_(d, alpha=-lr); opt_math.h says where this follows ATen's rounding).
+//             buf is signed state that moves p in EVERY step, so an unmarked chunk is never skipped, with or without an L2 term: RMSprop's
+//             rule, and here g' = 0 does move p.  16 bytes per parameter.
 // Descriptors by value in the kernel arguments, a 1-D grid shared out by tensor size, the learning rate as an argument
 // or from one device double, per-block L2 partials summed in a fixed order by a finish kernel: all as K7.
 #include "xdfm_internal.h"
@@ -71,10 +76,11 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_step_kernel(const OptBatch ba
     const float4 zero4 = make_float4(zf, zf, zf, zf);
     const unsigned tx = threadIdx.x, tx16 = tx * 16u;
     long i = tid;
-    if (marks && l2c == 0.f && K != OPT_RMSPROP) {
+    if (marks && l2c == 0.f && !OptMoves<K>::V) {
         // No L2 term: an unmarked chunk has g' == 0 -- p and the accumulator keep their bits, so the chunk is not read
         // at all.  (Not RMSprop: its accumulator decays to alpha * v whatever the gradient, so every chunk is a real update
-        // and takes the branch below -- with g' == 0 that update leaves the bits of p as they are.)  The scan reads the mark bytes 16 at a time (one uint4 per lane and load), two groups per thread in
+        // and takes the branch below -- with g' == 0 that update leaves the bits of p as they are.  Not SGDM either: with
+        // g' == 0 its buffer becomes mu * buf and still moves p.)  The scan reads the mark bytes 16 at a time (one uint4 per lane and load), two groups per thread in
         // flight; the chunks in front of the marks' first 16-byte boundary and behind the last whole group go one by one.
         auto process = [&](long e) {
             float4 pa = p4[e], sa = ADA ? s4[e] : zero4;
@@ -208,18 +214,22 @@ __global__ __launch_bounds__(1024) void opt_l2_finish_kernel(const float* __rest
 
 template <int K>
 static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
-                         double alpha, float* l2_ws, float* l2_value, void* stream) {
+                         double alpha, OptMom mom, float* l2_ws, float* l2_value, void* stream) {
     constexpr bool ADA = K != OPT_SGD;
     XDFM_REQUIRE(tensors, "%s: null pointer", what);
     XDFM_REQUIRE(T > 0 && T <= 65535, "%s: bad tensor count %d", what, T);
-    XDFM_REQUIRE(lr >= 0 && (!ADA || eps > 0), "%s: bad hyper-parameters", what);
+    XDFM_REQUIRE(lr >= 0 && (!ADA || K == OPT_SGDM || eps > 0), "%s: bad hyper-parameters", what);
     XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "%s: bad hyper-parameters (alpha %g is outside [0, 1))", what, alpha);
+    XDFM_REQUIRE(K != OPT_SGDM || (mom.mu > 0 && mom.mu < 1), "%s: bad hyper-parameters (momentum %g is outside (0, 1))", what, mom.mu);
     XDFM_REQUIRE(!l2_value || l2_ws, "%s: l2_value needs l2_ws", what);
     for (int t = 0; t < T; ++t)
         XDFM_REQUIRE(tensors[t].param && tensors[t].grad && tensors[t].numel >= 0 && tensors[t].l2 >= 0,
                      "%s: tensor %d has a null pointer, a negative size or a negative l2", what, t);
     for (int t = 0; t < T; ++t)
-        XDFM_REQUIRE(!ADA || tensors[t].state, "%s: tensor %d has no state (the accumulator)", what, t);
+        XDFM_REQUIRE(!ADA || tensors[t].state, "%s: tensor %d has no state (%s)", what, t, opt_state_name(K));
+    for (int t = 0; t < T; ++t)       // a float pointer off a float boundary (checked for the new kind only: the others' calls stay as they were)
+        XDFM_REQUIRE(K != OPT_SGDM || (((size_t)tensors[t].state) & 3) == 0, "%s: tensor %d has a misaligned state (%p is not 4-byte aligned)",
+                     what, t, (void*)tensors[t].state);
     for (int t = 0; t < T; ++t)
         XDFM_REQUIRE(!tensors[t].grad_marks ||
                          ((((size_t)tensors[t].param) | ((size_t)tensors[t].grad) | (ADA ? (size_t)tensors[t].state : 0)) & 15) == 0,
@@ -238,7 +248,7 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
         }
         tbl_grid(batch, cnt, OPT_BLOCK_ELEMS, opt_bx_cap(OPT_BX));      // option "opt_bx" caps the blocks per tensor (tests)
         hipLaunchKernelGGL(opt_step_kernel<K>, dim3(batch.first[cnt]), dim3(OPT_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev,
-                           opt_hyper(K, eps, alpha), l2_value ? l2_ws : nullptr);
+                           opt_hyper(K, eps, alpha, mom), l2_value ? l2_ws : nullptr);
         slot0 += batch.first[cnt];
     }
     if (l2_value) hipLaunchKernelGGL(opt_l2_finish_kernel, dim3(1), dim3(1024), 0, st, l2_ws, slot0, l2_value);
@@ -247,10 +257,11 @@ static int opt_step_impl(const char* what, const xdfm_opt_tensor* tensors, int T
 
 // the sweep over the tensors the deferred step (sgd_adagrad_deferred.hip) does not defer: the same launches as below
 int xdfm_opt_step_dense(int kind, const char* what, const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
-                        double alpha, float* l2_ws, float* l2_value, void* stream) {
-    return kind == OPT_RMSPROP   ? opt_step_impl<OPT_RMSPROP>(what, tensors, T, lr, lr_dev, eps, alpha, l2_ws, l2_value, stream)
-           : kind == OPT_ADAGRAD ? opt_step_impl<OPT_ADAGRAD>(what, tensors, T, lr, lr_dev, eps, 0.0, l2_ws, l2_value, stream)
-                                 : opt_step_impl<OPT_SGD>(what, tensors, T, lr, lr_dev, 0.0, 0.0, l2_ws, l2_value, stream);
+                        double alpha, double mu, int nesterov, float* l2_ws, float* l2_value, void* stream) {
+    return kind == OPT_SGDM      ? opt_step_impl<OPT_SGDM>(what, tensors, T, lr, lr_dev, 0.0, 0.0, OptMom{mu, nesterov}, l2_ws, l2_value, stream)
+           : kind == OPT_RMSPROP ? opt_step_impl<OPT_RMSPROP>(what, tensors, T, lr, lr_dev, eps, alpha, OPT_NO_MOM, l2_ws, l2_value, stream)
+           : kind == OPT_ADAGRAD ? opt_step_impl<OPT_ADAGRAD>(what, tensors, T, lr, lr_dev, eps, 0.0, OPT_NO_MOM, l2_ws, l2_value, stream)
+                                 : opt_step_impl<OPT_SGD>(what, tensors, T, lr, lr_dev, 0.0, 0.0, OPT_NO_MOM, l2_ws, l2_value, stream);
 }
 
 extern "C" {
@@ -259,17 +270,22 @@ size_t xdfm_opt_step_ws_elems(int T) { return T > 0 ? (size_t)T * OPT_BX : 0; }
 
 int xdfm_sgd_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, float* l2_ws, float* l2_value,
                   void* stream) {
-    return opt_step_impl<OPT_SGD>("sgd_step", tensors, T, lr, lr_dev, 0.0, 0.0, l2_ws, l2_value, stream);
+    return opt_step_impl<OPT_SGD>("sgd_step", tensors, T, lr, lr_dev, 0.0, 0.0, OPT_NO_MOM, l2_ws, l2_value, stream);
 }
 
 int xdfm_adagrad_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps, float* l2_ws,
                       float* l2_value, void* stream) {
-    return opt_step_impl<OPT_ADAGRAD>("adagrad_step", tensors, T, lr, lr_dev, eps, 0.0, l2_ws, l2_value, stream);
+    return opt_step_impl<OPT_ADAGRAD>("adagrad_step", tensors, T, lr, lr_dev, eps, 0.0, OPT_NO_MOM, l2_ws, l2_value, stream);
 }
 
 int xdfm_rmsprop_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double alpha, double eps,
                       float* l2_ws, float* l2_value, void* stream) {
-    return opt_step_impl<OPT_RMSPROP>("rmsprop_step", tensors, T, lr, lr_dev, eps, alpha, l2_ws, l2_value, stream);
+    return opt_step_impl<OPT_RMSPROP>("rmsprop_step", tensors, T, lr, lr_dev, eps, alpha, OPT_NO_MOM, l2_ws, l2_value, stream);
+}
+
+int xdfm_sgdm_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double mu, int nesterov, float* l2_ws,
+                   float* l2_value, void* stream) {
+    return opt_step_impl<OPT_SGDM>("sgdm_step", tensors, T, lr, lr_dev, 0.0, 0.0, OptMom{mu, nesterov}, l2_ws, l2_value, stream);
 }
 
 }  // extern "C"

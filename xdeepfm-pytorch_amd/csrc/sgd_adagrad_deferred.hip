@@ -1,5 +1,5 @@
-// K7sd / K7gd: the deferred (exact) form of the SGD and Adagrad steps for the embedding / linear tables (xdfm.h), K7d's
-// scheme (adam.hip) for K7s / K7g (sgd_adagrad.hip).
+// K7sd / K7gd / K7rd / K7md: the deferred (exact) form of the SGD, Adagrad, RMSprop and SGD-with-momentum steps for the
+// embedding / linear tables (xdfm.h), K7d's scheme (adam.hip) for K7s / K7g / K7r / K7m (sgd_adagrad.hip).
 //
 // With an L2 term every table parameter is a real update in every step (an untouched row sees g' = 2 l2 p), so K7s / K7g
 // sweep 8 / 16 bytes per table parameter and step.  An untouched chunk evolves by a recurrence in its own registers and the
@@ -245,8 +245,12 @@ __global__ __launch_bounds__(OPTD_THREADS) void opt_catchup_rows_kernel(
 // chunks per thread in flight: one chunk's replay is a dependent chain per element (Adagrad: an IEEE square root and a
 // division deep), so a thread carries several chunks = 4 * N independent chains through the steps.  The step is computed
 // for every chunk and taken by a select (a chunk that is ahead, or a lane behind the end, keeps its registers): a branch
-// per chunk would put the chunks of a thread one after the other again.
-template <int K> struct OptFlushFlight { static constexpr int N = K != OPT_SGD ? 2 : 4; };
+// per chunk would put the chunks of a thread one after the other again.  Adagrad and RMSprop carry two chunks: their square
+// root and division sequences are long enough to fill the pipeline from eight chains, and more would cost registers.  SGDM
+// carries p and the buffer as they do, but its element-step is three dependent fmas, as short as SGD's one, so it takes
+// SGD's four (114 VGPRs, no scratch, four waves per SIMD).  Four against two has NOT been measured for it; the measured
+// flush is 7.55 ms per 574 M table parameters and 64 steps (profiles/sgdm_probe.md).
+template <int K> struct OptFlushFlight { static constexpr int N = K == OPT_ADAGRAD || K == OPT_RMSPROP ? 2 : 4; };
 
 template <int K>
 __global__ __launch_bounds__(OPTD_THREADS) void opt_flush_kernel(const OptDefBatch batch, int cnt, const int* __restrict__ clock,
@@ -335,20 +339,24 @@ static OptDefDev opt_def_dev(const xdfm_opt_tensor& x, unsigned char* last) {
 
 template <int K>
 static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tensors, unsigned char* const* last, int T,
-                                  const xdfm_opt_clock* clk, double lr, const double* lr_dev, double eps, double alpha, float* l2_ws,
-                                  float* l2_value, void* stream) {
+                                  const xdfm_opt_clock* clk, double lr, const double* lr_dev, double eps, double alpha, OptMom mom,
+                                  float* l2_ws, float* l2_value, void* stream) {
     constexpr bool ADA = K != OPT_SGD;
     XDFM_REQUIRE(tensors && last, "%s: null pointer", what);
     XDFM_REQUIRE(T > 0 && T <= 65535, "%s: bad tensor count %d", what, T);
     if (int rc = opt_clock_ok(what, clk)) return rc;
-    XDFM_REQUIRE(lr >= 0 && (!ADA || eps > 0), "%s: bad hyper-parameters", what);
+    XDFM_REQUIRE(lr >= 0 && (!ADA || K == OPT_SGDM || eps > 0), "%s: bad hyper-parameters", what);
     XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "%s: bad hyper-parameters (alpha %g is outside [0, 1))", what, alpha);
+    XDFM_REQUIRE(K != OPT_SGDM || (mom.mu > 0 && mom.mu < 1), "%s: bad hyper-parameters (momentum %g is outside (0, 1))", what, mom.mu);
     XDFM_REQUIRE(!l2_value || l2_ws, "%s: l2_value needs l2_ws", what);
     for (int t = 0; t < T; ++t)
         XDFM_REQUIRE(tensors[t].param && tensors[t].grad && tensors[t].numel >= 0 && tensors[t].l2 >= 0,
                      "%s: tensor %d has a null pointer, a negative size or a negative l2", what, t);
     for (int t = 0; t < T; ++t)
-        XDFM_REQUIRE(!ADA || tensors[t].state, "%s: tensor %d has no state (the accumulator)", what, t);
+        XDFM_REQUIRE(!ADA || tensors[t].state, "%s: tensor %d has no state (%s)", what, t, opt_state_name(K));
+    for (int t = 0; t < T; ++t)
+        XDFM_REQUIRE(K != OPT_SGDM || (((size_t)tensors[t].state) & 3) == 0, "%s: tensor %d has a misaligned state (%p is not 4-byte aligned)",
+                     what, t, (void*)tensors[t].state);
     for (int t = 0; t < T; ++t) {
         if (!last[t]) continue;
         XDFM_REQUIRE(tensors[t].grad_marks, "%s: tensor %d is deferred but has no grad_marks", what, t);
@@ -365,7 +373,7 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
     }
     hipLaunchKernelGGL(opt_tick_kernel, dim3(1), dim3(64), 0, st, clk->clock, clk->rates, clk->cap, lr, lr_dev);
     if (!dense.empty()) {                               // stepped exactly as xdfm_sgd_step / xdfm_adagrad_step step them
-        if (int rc = xdfm_opt_step_dense(K, what, dense.data(), (int)dense.size(), lr, lr_dev, eps, alpha, l2_ws, l2_value, stream)) return rc;
+        if (int rc = xdfm_opt_step_dense(K, what, dense.data(), (int)dense.size(), lr, lr_dev, eps, alpha, mom.mu, mom.nesterov, l2_ws, l2_value, stream)) return rc;
     }
     const int n = (int)def.size();
     for (int l0 = 0; l0 < n; l0 += OPTD_CHUNK) {
@@ -374,7 +382,7 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[def[l0 + k]], last[def[l0 + k]]);
         tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, opt_bx_cap(OPTD_BX));
         hipLaunchKernelGGL(opt_step_deferred_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock,
-                           clk->rates, opt_hyper(K, eps, alpha), clk->backlog, clk->cell);
+                           clk->rates, opt_hyper(K, eps, alpha, mom), clk->backlog, clk->cell);
     }
     hipLaunchKernelGGL(opt_l2_cell_finish_kernel, dim3(1), dim3(64), 0, st, clk->cell, l2_value, dense.empty() ? 0 : 1);
     return xdfm_check_launch(what);
@@ -382,18 +390,19 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
 
 template <int K>
 static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double eps,
-                          double alpha, void* stream) {
+                          double alpha, OptMom mom, void* stream) {
     constexpr bool ADA = K != OPT_SGD;
     XDFM_REQUIRE(tensors && last, "opt_flush: null pointer");
     XDFM_REQUIRE(T > 0 && T <= 65535, "opt_flush: bad tensor count %d", T);
     if (int rc = opt_clock_ok("opt_flush", clk)) return rc;
-    XDFM_REQUIRE(!ADA || eps > 0, "opt_flush: bad hyper-parameters");
+    XDFM_REQUIRE(!ADA || K == OPT_SGDM || eps > 0, "opt_flush: bad hyper-parameters");
     XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "opt_flush: bad hyper-parameters (alpha %g is outside [0, 1))", alpha);
+    XDFM_REQUIRE(K != OPT_SGDM || (mom.mu > 0 && mom.mu < 1), "opt_flush: bad hyper-parameters (momentum %g is outside (0, 1))", mom.mu);
     for (int t = 0; t < T; ++t) {
         XDFM_REQUIRE(tensors[t].param && tensors[t].numel >= 0 && tensors[t].l2 >= 0,
                      "opt_flush: tensor %d has a null pointer, a negative size or a negative l2", t);
         XDFM_REQUIRE(last[t], "opt_flush: tensor %d has no last", t);
-        XDFM_REQUIRE(!ADA || tensors[t].state, "opt_flush: tensor %d has no state (the accumulator)", t);
+        XDFM_REQUIRE(!ADA || tensors[t].state, "opt_flush: tensor %d has no state (%s)", t, opt_state_name(K));
         XDFM_REQUIRE(((((size_t)tensors[t].param) | (ADA ? (size_t)tensors[t].state : 0)) & 15) == 0,
                      "opt_flush: tensor %d has a pointer that is not 16-byte aligned", t);
     }
@@ -404,7 +413,7 @@ static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* 
         for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[l0 + k], last[l0 + k]);
         tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, opt_bx_cap(OPTD_FLUSH_BX));
         hipLaunchKernelGGL(opt_flush_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock, clk->rates,
-                           opt_hyper(K, eps, alpha), clk->backlog);
+                           opt_hyper(K, eps, alpha, mom), clk->backlog);
     }
     hipLaunchKernelGGL(opt_clock_reset_kernel, dim3(1), dim3(64), 0, st, clk->clock);
     return xdfm_check_launch("opt_flush");
@@ -412,20 +421,20 @@ static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* 
 
 template <int K>
 static int opt_catchup_impl(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D, const xdfm_opt_rows* emb,
-                            const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps, double alpha, void* stream) {
+                            const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps, double alpha, OptMom mom, void* stream) {
     const OptRowsDev e = {emb->param, emb->state, emb->last, emb->l2};
     const OptRowsDev l = lin ? OptRowsDev{lin->param, lin->state, lin->last, lin->l2} : e;
     const int QT = (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);
     const long threads = (long)B * m * QT;
     hipLaunchKernelGGL(opt_catchup_rows_kernel<K>, dim3((unsigned)ceil_div(threads, (long)OPTD_THREADS)), dim3(OPTD_THREADS), 0,
                        (hipStream_t)stream, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0, clk->clock, clk->rates,
-                       opt_hyper(K, eps, alpha), clk->backlog);
+                       opt_hyper(K, eps, alpha, mom), clk->backlog);
     return xdfm_check_launch("opt_catchup_rows");
 }
 
 // what xdfm_opt_catchup_rows and xdfm_rmsprop_catchup_rows check before any device work
 static int opt_catchup_ok(int kind, const float* X, int B, const int* cols, const int* vocab, int m, int D, const xdfm_opt_rows* emb,
-                          const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps, double alpha) {
+                          const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps, double alpha, double mu = 0.0) {
     XDFM_REQUIRE(X && cols && vocab && emb, "opt_catchup_rows: null pointer");
     if (int rc = opt_clock_ok("opt_catchup_rows", clk)) return rc;
     XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "opt_catchup_rows: bad shape B=%d m=%d D=%d", B, m, D);
@@ -434,6 +443,8 @@ static int opt_catchup_ok(int kind, const float* X, int B, const int* cols, cons
     XDFM_REQUIRE(kind != OPT_ADAGRAD || (eps > 0 && emb->state && (!lin || lin->state)), "opt_catchup_rows: Adagrad needs state and eps > 0");
     XDFM_REQUIRE(kind != OPT_RMSPROP || (eps > 0 && emb->state && (!lin || lin->state)), "opt_catchup_rows: RMSprop needs state and eps > 0");
     XDFM_REQUIRE(kind != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "opt_catchup_rows: bad hyper-parameters (alpha %g is outside [0, 1))", alpha);
+    XDFM_REQUIRE(kind != OPT_SGDM || (emb->state && (!lin || lin->state)), "opt_catchup_rows: SGD with momentum needs state (the buffers)");
+    XDFM_REQUIRE(kind != OPT_SGDM || (mu > 0 && mu < 1), "opt_catchup_rows: bad hyper-parameters (momentum %g is outside (0, 1))", mu);
     return XDFM_OK;
 }
 
@@ -441,44 +452,61 @@ extern "C" {
 
 int xdfm_sgd_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                            double lr, const double* lr_dev, float* l2_ws, float* l2_value, void* stream) {
-    return opt_step_deferred_impl<OPT_SGD>("sgd_step_deferred", tensors, last, T, clk, lr, lr_dev, 0.0, 0.0, l2_ws, l2_value, stream);
+    return opt_step_deferred_impl<OPT_SGD>("sgd_step_deferred", tensors, last, T, clk, lr, lr_dev, 0.0, 0.0, OPT_NO_MOM, l2_ws, l2_value, stream);
 }
 
 int xdfm_adagrad_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                                double lr, const double* lr_dev, double eps, float* l2_ws, float* l2_value, void* stream) {
-    return opt_step_deferred_impl<OPT_ADAGRAD>("adagrad_step_deferred", tensors, last, T, clk, lr, lr_dev, eps, 0.0, l2_ws, l2_value, stream);
+    return opt_step_deferred_impl<OPT_ADAGRAD>("adagrad_step_deferred", tensors, last, T, clk, lr, lr_dev, eps, 0.0, OPT_NO_MOM, l2_ws, l2_value, stream);
 }
 
 int xdfm_rmsprop_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                                double lr, const double* lr_dev, double alpha, double eps, float* l2_ws, float* l2_value,
                                void* stream) {
-    return opt_step_deferred_impl<OPT_RMSPROP>("rmsprop_step_deferred", tensors, last, T, clk, lr, lr_dev, eps, alpha, l2_ws, l2_value, stream);
+    return opt_step_deferred_impl<OPT_RMSPROP>("rmsprop_step_deferred", tensors, last, T, clk, lr, lr_dev, eps, alpha, OPT_NO_MOM, l2_ws, l2_value, stream);
+}
+
+int xdfm_sgdm_step_deferred(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
+                            double lr, const double* lr_dev, double mu, int nesterov, float* l2_ws, float* l2_value, void* stream) {
+    return opt_step_deferred_impl<OPT_SGDM>("sgdm_step_deferred", tensors, last, T, clk, lr, lr_dev, 0.0, 0.0, OptMom{mu, nesterov}, l2_ws,
+                                            l2_value, stream);
 }
 
 int xdfm_opt_catchup_rows(int adagrad, const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
                           const xdfm_opt_rows* emb, const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double eps,
                           void* stream) {
     if (int rc = opt_catchup_ok(adagrad ? OPT_ADAGRAD : OPT_SGD, X, B, cols, vocab, m, D, emb, lin, clk, eps, 0.0)) return rc;
-    return adagrad ? opt_catchup_impl<OPT_ADAGRAD>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, eps, 0.0, stream)
-                   : opt_catchup_impl<OPT_SGD>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, 0.0, 0.0, stream);
+    return adagrad ? opt_catchup_impl<OPT_ADAGRAD>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, eps, 0.0, OPT_NO_MOM, stream)
+                   : opt_catchup_impl<OPT_SGD>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, 0.0, 0.0, OPT_NO_MOM, stream);
 }
 
 int xdfm_rmsprop_catchup_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
                               const xdfm_opt_rows* emb, const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double alpha,
                               double eps, void* stream) {
     if (int rc = opt_catchup_ok(OPT_RMSPROP, X, B, cols, vocab, m, D, emb, lin, clk, eps, alpha)) return rc;
-    return opt_catchup_impl<OPT_RMSPROP>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, eps, alpha, stream);
+    return opt_catchup_impl<OPT_RMSPROP>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, eps, alpha, OPT_NO_MOM, stream);
+}
+
+int xdfm_sgdm_catchup_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D, const xdfm_opt_rows* emb,
+                           const xdfm_opt_rows* lin, const xdfm_opt_clock* clk, double mu, int nesterov, void* stream) {
+    if (int rc = opt_catchup_ok(OPT_SGDM, X, B, cols, vocab, m, D, emb, lin, clk, 0.0, 0.0, mu)) return rc;
+    return opt_catchup_impl<OPT_SGDM>(X, ldx, B, cols, vocab, m, D, emb, lin, clk, 0.0, 0.0, OptMom{mu, nesterov}, stream);
 }
 
 int xdfm_opt_flush(int adagrad, const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk,
                    double eps, void* stream) {
-    return adagrad ? opt_flush_impl<OPT_ADAGRAD>(tensors, last, T, clk, eps, 0.0, stream)
-                   : opt_flush_impl<OPT_SGD>(tensors, last, T, clk, 0.0, 0.0, stream);
+    return adagrad ? opt_flush_impl<OPT_ADAGRAD>(tensors, last, T, clk, eps, 0.0, OPT_NO_MOM, stream)
+                   : opt_flush_impl<OPT_SGD>(tensors, last, T, clk, 0.0, 0.0, OPT_NO_MOM, stream);
 }
 
 int xdfm_rmsprop_flush(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double alpha,
                        double eps, void* stream) {
-    return opt_flush_impl<OPT_RMSPROP>(tensors, last, T, clk, eps, alpha, stream);
+    return opt_flush_impl<OPT_RMSPROP>(tensors, last, T, clk, eps, alpha, OPT_NO_MOM, stream);
+}
+
+int xdfm_sgdm_flush(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double mu, int nesterov,
+                    void* stream) {
+    return opt_flush_impl<OPT_SGDM>(tensors, last, T, clk, 0.0, 0.0, OptMom{mu, nesterov}, stream);
 }
 
 }  // extern "C"

@@ -133,10 +133,10 @@ static inline int xdfm_check_launch(const char* what) {
     return XDFM_OK;
 }
 
-// K7s / K7g / K7r over a list of tensors (sgd_adagrad.hip): what xdfm_sgd_step / xdfm_adagrad_step / xdfm_rmsprop_step launch,
-// for the deferred step; kind: OptKind of opt_math.h
+// K7s / K7g / K7r / K7m over a list of tensors (sgd_adagrad.hip): what xdfm_sgd_step / xdfm_adagrad_step / xdfm_rmsprop_step /
+// xdfm_sgdm_step launch, for the deferred step; kind: OptKind of opt_math.h (mu, nesterov: OPT_SGDM's)
 int xdfm_opt_step_dense(int kind, const char* what, const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
-                        double alpha, float* l2_ws, float* l2_value, void* stream);
+                        double alpha, double mu, int nesterov, float* l2_ws, float* l2_value, void* stream);
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 static inline long round_up(long a, long b) { return (a + b - 1) / b * b; }

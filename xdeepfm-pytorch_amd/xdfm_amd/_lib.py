@@ -98,6 +98,10 @@ SIGNATURES = {
     "xdfm_rmsprop_step_deferred": (c_int, [P, P, c_int, P, c_double, P, c_double, c_double, P, P, P]),
     "xdfm_rmsprop_catchup_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, c_double, P]),
     "xdfm_rmsprop_flush": (c_int, [P, P, c_int, P, c_double, c_double, P]),
+    "xdfm_sgdm_step": (c_int, [P, c_int, c_double, P, c_double, c_int, P, P, P]),
+    "xdfm_sgdm_step_deferred": (c_int, [P, P, c_int, P, c_double, P, c_double, c_int, P, P, P]),
+    "xdfm_sgdm_catchup_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, c_int, P]),
+    "xdfm_sgdm_flush": (c_int, [P, P, c_int, P, c_double, c_int, P]),
     "xdfm_vocab_lse_update": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_softmax_grad": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_ce_x3_supported": (c_int, [c_int]),

@@ -14,7 +14,8 @@ passes over the parameters (basemodel.py:412-428) from the step.
 Gradients that are views of a kept gradient buffer (`ops.GradArena`, registered through `grad_sources`) are read by
 their chunk marks: K7 skips the untouched rows of the dense table gradients and re-zeroes the touched ones.
 
-`TableSGD`, `TableAdagrad` and `TableRMSprop` (K7s / K7g / K7r, `xdfm_sgd_step` / `xdfm_adagrad_step` / `xdfm_rmsprop_step`)
+`TableSGD`, `TableAdagrad` and `TableRMSprop` (K7s / K7g / K7r, `xdfm_sgd_step` / `xdfm_adagrad_step` / `xdfm_rmsprop_step`;
+TableSGD with a momentum: K7m, `xdfm_sgdm_step`)
 give the other optimizer strings of basemodel.py:447-461 (`--optimizer sgd|adagrad|rmsprop`) the same sweep, armed L2 term,
 marked gradients and device-resident learning rate; their state layout is that of torch.optim.SGD / Adagrad / RMSprop.
 Tables with an L2 term may take the deferred (exact) form of those steps (K7sd / K7gd / K7rd, `xdfm_sgd_step_deferred` /
@@ -37,6 +38,10 @@ DEFER_MIN_NUMEL = int(os.environ.get("XDFM_ADAM_DEFER_MIN_NUMEL", 1 << 26))   # 
 # the crossover near 94 M (SGD) / 79 M (Adagrad).  2^27 is above both.
 OPT_DEFER_MIN_NUMEL = max(int(os.environ.get("XDFM_OPT_DEFER_MIN_NUMEL", 1 << 27)), 1 << 26)
 ROWS_MIN_NUMEL = 1 << 20  # tables at least this large get the step's update by the batch's rows (XDFM_ADAM_ROWS_MIN_NUMEL overrides)
+# XDFM_SGD_MOMENTUM_NATIVE (default 1): TableSGD with 0 < momentum < 1 and dampening 0 (plain or Nesterov) runs K7m / K7md;
+# 0 gives the stock torch.optim.SGD.step back for it.  Read once, at import; tools/optim_probe.py and the tests flip this
+# attribute to run both routes in one process (a captured graph keeps the route it was captured with).
+SGD_MOMENTUM_NATIVE = os.environ.get("XDFM_SGD_MOMENTUM_NATIVE", "1") != "0"
 
 
 def _ptr_tables(struct, ts, ent, cols, tolerate, pad=0):
@@ -58,7 +63,7 @@ class _TableStep(object):
     kernel implements (`_plain`, `_state_of`, `_hyper`) and the class attributes below; `step` here is the one of TableSGD,
     TableAdagrad and TableRMSprop, TableAdam has its own."""
     table_step = True
-    _KERNEL = None               # "sgd" / "adagrad" / "rmsprop"
+    _KERNEL = None               # "sgd" / "adagrad" / "rmsprop" ("sgdm" is TableSGD's second kernel: `_kind`)
     _ENV = "XDFM_OPT"            # the environment's <_ENV>_DEFERRED / <_ENV>_FLUSH_EVERY
     _PATHS = ("scan",)           # keys of `path_counts`
     _FLOOR = "OPT_DEFER_MIN_NUMEL"      # the module constant "auto" compares with (by name: read when the decision is taken)
@@ -160,7 +165,7 @@ class _TableStep(object):
             d = self._def = dict(clock=torch.zeros(2, dtype=torch.int32, device=dev),
                                  rates=torch.zeros(DEFER_CAP, dtype=torch.float32, device=dev),
                                  backlog=kept if kept is not None and kept.device == dev else torch.zeros(1, **i64),
-                                 cell=torch.zeros(1, **i64), last={}, tensors={}, rows={}, plans=[], eps=None)
+                                 cell=torch.zeros(1, **i64), last={}, tensors={}, rows={}, plans=[], eps=None, kind=self._KERNEL)
             d["clk"] = _lib.OptClock(d["clock"].data_ptr(), d["rates"].data_ptr(), DEFER_CAP, d["backlog"].data_ptr(),
                                      d["cell"].data_ptr())
             for src in self.grad_sources:             # the gathers whose rows must be current before they are read
@@ -214,10 +219,13 @@ class _TableStep(object):
         head = (X.data_ptr(), X.stride(0), X.shape[0], cols.data_ptr(), vocab.data_ptr(), plan.m, plan.D, ctypes.byref(e_struct),
                 ctypes.byref(l_struct) if l_struct is not None else None, ctypes.byref(d["clk"]))
         stream = torch.cuda.current_stream(X.device).cuda_stream
-        if self._KERNEL == "rmsprop":                   # d["eps"]: (alpha, eps) of the steps the replays stand for
+        kind = d["kind"]                                # the kernel of the steps the replays stand for, and its d["eps"]:
+        if kind == "rmsprop":                           # (alpha, eps)
             rc = _lib.load().xdfm_rmsprop_catchup_rows(*(head + (float(d["eps"][0]), float(d["eps"][1]), stream)))
+        elif kind == "sgdm":                            # (mu, nesterov)
+            rc = _lib.load().xdfm_sgdm_catchup_rows(*(head + (float(d["eps"][0]), int(d["eps"][1]), stream)))
         else:
-            rc = _lib.load().xdfm_opt_catchup_rows(1 if self._KERNEL == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
+            rc = _lib.load().xdfm_opt_catchup_rows(1 if kind == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
         _lib.check(rc, "opt_catchup_rows")
 
     @torch.no_grad()
@@ -242,10 +250,13 @@ class _TableStep(object):
             arr[k].state = state.data_ptr() if state is not None else None
             last[k] = lb.data_ptr()
         head = (ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(last, ctypes.c_void_p), len(ent), ctypes.byref(d["clk"]))
-        if self._KERNEL == "rmsprop":
+        kind = d["kind"]
+        if kind == "rmsprop":
             rc = _lib.load().xdfm_rmsprop_flush(*(head + (float(d["eps"][0]), float(d["eps"][1]), stream)))
+        elif kind == "sgdm":
+            rc = _lib.load().xdfm_sgdm_flush(*(head + (float(d["eps"][0]), int(d["eps"][1]), stream)))
         else:
-            rc = _lib.load().xdfm_opt_flush(1 if self._KERNEL == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
+            rc = _lib.load().xdfm_opt_flush(1 if kind == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
         _lib.check(rc, "opt_flush")
 
     def take_backlog(self):
@@ -362,6 +373,9 @@ class _TableStep(object):
     def _hyper(self, group):                    # what the replays of a deferred step assume beside the rate: a change flushes
         return None
 
+    def _kind(self, group):                     # the kernel a group's step runs (TableSGD has two)
+        return self._KERNEL
+
     def _native(self):
         """True when every group can take the kernel: plain hyper-parameters, dense contiguous fp32 CUDA tensors."""
         if getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
@@ -392,13 +406,13 @@ class _TableStep(object):
         lib = _lib.load()
         from . import ops                              # per-kernel timing hook of bench.py
         from . import dist as xdist
-        kind = self._KERNEL
         capturing = torch.cuda.is_current_stream_capturing()
         host_steps = []
         for gi, group in enumerate(self.param_groups):
             params = [p for p in group["params"] if p.grad is not None]
             if not params:
                 continue
+            kind = self._kind(group)
             grads = [p.grad for p in params]
             states = [self._state_of(group, p) for p in params]
             host_steps += [st[1] for st in states if st[1] is not None]
@@ -452,17 +466,18 @@ class _TableStep(object):
                 else:
                     want = {params[k].data_ptr(): (states[k][0], float(l2[k]), params[k].numel()) for k in deferred_now}
                     eps = self._hyper(group)
-                    same = d["eps"] == eps and len(want) == len(d["tensors"]) and all(
+                    same = d["kind"] == kind and d["eps"] == eps and len(want) == len(d["tensors"]) and all(
                         ptr in d["tensors"] and d["tensors"][ptr][0] is w[0] and d["tensors"][ptr][2] == w[1]
                         for ptr, w in want.items())
                     if not same:
-                        # the set of deferred tables, an L2 strength, eps or alpha changed: the replays assumed the old ones
+                        # the set of deferred tables, an L2 strength, eps, alpha, the momentum or the kernel changed: the replays
+                        # assumed the old ones (the flush below still runs with them)
                         if capturing:                  # (the `last` bytes are allocated and zeroed by an eager step)
                             raise RuntimeError("xdfm %s: the deferred tables changed inside a HIP-graph capture" % type(self).__name__)
                         self.flush()
                         byptr = {params[k].data_ptr(): params[k] for k in deferred_now}
                         d["tensors"] = {ptr: (w[0], self._last_bytes(byptr[ptr]), w[1], w[2]) for ptr, w in want.items()}
-                        d["rows"], d["eps"] = {}, eps
+                        d["rows"], d["eps"], d["kind"] = {}, eps, kind
                     if not capturing and self._since >= self.flush_every:
                         self.flush()
                     last_arr = (ctypes.c_void_p * T)()
@@ -470,10 +485,11 @@ class _TableStep(object):
                         last_arr[k] = d["tensors"][params[k].data_ptr()][1].data_ptr()
             nbytes = 0.0
             for k in range(T):
-                per = 8.0 if kind == "sgd" else 16.0   # the byte model of DESIGN.md (K7s / K7g / K7r)
+                per = 8.0 if kind == "sgd" else 16.0   # the byte model of DESIGN.md (K7s / K7g / K7r / K7m)
                 if arr[k].grad_marks:
-                    # (RMSprop's accumulator decays in every step: no shortcut for a tensor without an L2 term)
-                    skip = (arr[k].l2 == 0.0 and kind != "rmsprop") or (last_arr is not None and last_arr[k])
+                    # (RMSprop's accumulator decays in every step, the momentum buffer moves its weight in every step: no shortcut
+                    # for a tensor without an L2 term)
+                    skip = (arr[k].l2 == 0.0 and kind not in ("rmsprop", "sgdm")) or (last_arr is not None and last_arr[k])
                     nbytes += params[k].numel() * (0.0625 if skip else per + 0.0625)
                 else:
                     nbytes += params[k].numel() * (per + 4.0)
@@ -488,6 +504,10 @@ class _TableStep(object):
                     launch = lambda: lib.xdfm_rmsprop_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
                                                                     float(group["lr"]), lr_ptr, float(group["alpha"]),
                                                                     float(group["eps"]), ws_ptr, val_ptr, stream)
+                elif kind == "sgdm":
+                    launch = lambda: lib.xdfm_sgdm_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
+                                                                 float(group["lr"]), lr_ptr, float(group["momentum"]),
+                                                                 int(bool(group["nesterov"])), ws_ptr, val_ptr, stream)
                 elif kind == "adagrad":
                     launch = lambda: lib.xdfm_adagrad_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
                                                                     float(group["lr"]), lr_ptr, float(group["eps"]), ws_ptr,
@@ -501,13 +521,16 @@ class _TableStep(object):
             elif kind == "rmsprop":
                 launch = lambda: lib.xdfm_rmsprop_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                        float(group["alpha"]), float(group["eps"]), ws_ptr, val_ptr, stream)
+            elif kind == "sgdm":
+                launch = lambda: lib.xdfm_sgdm_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
+                                                    float(group["momentum"]), int(bool(group["nesterov"])), ws_ptr, val_ptr, stream)
             elif kind == "adagrad":
                 launch = lambda: lib.xdfm_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                        float(group["eps"]), ws_ptr, val_ptr, stream)
             else:
                 launch = lambda: lib.xdfm_sgd_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                    ws_ptr, val_ptr, stream)
-            _lib.check(ops._run("%s_step[bytes]" % self._KERNEL, nbytes, launch), "%s_step" % self._KERNEL)
+            _lib.check(ops._run("%s_step[bytes]" % kind, nbytes, launch), "%s_step" % kind)
             self._add_l2(val)
         if host_steps:
             if capturing:
@@ -792,10 +815,13 @@ class TableAdam(_TableStep, torch.optim.Adam):
 
 
 class TableSGD(_TableStep, torch.optim.SGD):
-    """torch.optim.SGD whose step is K7s (`xdfm_sgd_step`) for momentum 0 (the reference's `compile("sgd")`, lr 0.01).
-    Momentum, dampening, nesterov, weight decay, maximize, tensor learning rates, sparse / non-fp32 / non-CUDA tensors and
-    closures fall back to torch.optim.SGD.step with the armed L2 term applied by hand."""
-    _KERNEL = "sgd"
+    """torch.optim.SGD whose step is K7s (`xdfm_sgd_step`) for momentum 0 (the reference's `compile("sgd")`, lr 0.01) and K7m
+    (`xdfm_sgdm_step`) for 0 < momentum < 1 with dampening 0, plain or Nesterov; tables with an L2 term may take the deferred
+    forms (K7sd / K7md).  With momentum the state is torch's: `momentum_buffer` per parameter, created by the first eager step,
+    never inside a capture.  Dampening, a momentum outside (0, 1), weight decay, maximize, tensor learning rates, sparse /
+    non-fp32 / non-CUDA tensors and closures -- and every momentum with XDFM_SGD_MOMENTUM_NATIVE=0 -- fall back to
+    torch.optim.SGD.step with the armed L2 term applied by hand."""
+    _KERNEL = "sgd"              # momentum 0; "sgdm" otherwise (`_kind`)
 
     def __init__(self, params, lr=0.01, momentum=0, dampening=0, weight_decay=0, nesterov=False, *, maximize=False,
                  deferred=None, flush_every=64):
@@ -804,10 +830,32 @@ class TableSGD(_TableStep, torch.optim.SGD):
         self._table_init(deferred, flush_every)
 
     def _plain(self, group):
-        return group["momentum"] == 0 and group["dampening"] == 0 and not group["nesterov"]
+        mu = group["momentum"]
+        if mu == 0:
+            return group["dampening"] == 0 and not group["nesterov"]
+        # (torch itself allows nesterov only with a momentum and dampening 0)
+        return SGD_MOMENTUM_NATIVE and isinstance(mu, float) and 0.0 < mu < 1.0 and group["dampening"] == 0
+
+    def _kind(self, group):
+        return "sgd" if group["momentum"] == 0 else "sgdm"
 
     def _state_of(self, group, p):
-        return None, None
+        if group["momentum"] == 0:
+            return None, None
+        st = self.state[p]
+        buf = st.get("momentum_buffer")         # None: absent (a torch.optim.SGD checkpoint saved before any step)
+        if buf is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("xdfm TableSGD: the state is created by an eager step, not inside a HIP-graph capture")
+            # torch makes the buffer at the first step as clone(g'); zeros give the same first value, mu * 0 + g' -- it differs
+            # only in the sign of a zero (g' == -0 gives +0 here)
+            buf = st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        if not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
+            raise RuntimeError("xdfm TableSGD: the momentum buffer of a CUDA parameter must be a contiguous fp32 CUDA tensor")
+        return buf, None
+
+    def _hyper(self, group):
+        return None if group["momentum"] == 0 else (float(group["momentum"]), bool(group["nesterov"]))
 
 
 class TableAdagrad(_TableStep, torch.optim.Adagrad):

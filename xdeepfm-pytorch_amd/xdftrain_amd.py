@@ -93,6 +93,9 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--dnn_dropout", type=float, default=0.0)
     p.add_argument("--learning_rate", type=float, default=0.001)
     p.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adagrad", "sgd", "rmsprop"])
+    p.add_argument("--momentum", type=float, default=0.0,
+                   help="with --optimizer sgd: SGD with this momentum, in [0, 1) (0: plain SGD, as compile('sgd'))")
+    p.add_argument("--nesterov", action="store_true", help="with --optimizer sgd and --momentum > 0: Nesterov momentum")
     p.add_argument("--class_weight", type=float, nargs=2, default=None, metavar=("W0", "W1"),
                    help="weights of the negative and the positive examples in the training loss, e.g. 1 4 for a log whose "
                         "negatives were down-sampled (fit(class_weight={0: W0, 1: W1})); default: none")
@@ -120,6 +123,12 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--autodis_buckets", type=int, default=16)
     p.add_argument("--use_light_version", action="store_true")
     args = p.parse_args(argv)
+    if (args.momentum != 0.0 or args.nesterov) and args.optimizer != "sgd":
+        p.error("--momentum / --nesterov need --optimizer sgd (got --optimizer %s)" % args.optimizer)
+    if not 0.0 <= args.momentum < 1.0:
+        p.error("--momentum %g is outside [0, 1)" % args.momentum)
+    if args.nesterov and args.momentum == 0.0:
+        p.error("--nesterov needs --momentum > 0")
     for k, v in SCRIPT_DEFAULTS[script or args.model].items():
         if getattr(args, k) is None:
             setattr(args, k, v)
@@ -253,6 +262,18 @@ def build_model(args, cols):
                autodis_buckets=args.autodis_buckets, **common)
 
 
+def make_optimizer(args, model):
+    """What compile() gets: the optimizer's name, or -- SGD with a momentum, which no name of compile() stands for -- the object:
+    xdfm_amd.optim.TableSGD (K7m) for a model on a GPU, torch.optim.SGD on the CPU.  The rate is set after compile()."""
+    if args.optimizer != "sgd" or args.momentum == 0.0:
+        return args.optimizer
+    params = list(model.parameters())
+    if params and all(p.is_cuda for p in params):
+        from xdfm_amd.optim import TableSGD
+        return TableSGD(params, lr=0.01, momentum=args.momentum, nesterov=args.nesterov)
+    return torch.optim.SGD(params, lr=0.01, momentum=args.momentum, nesterov=args.nesterov)
+
+
 def main(argv=None, model=None, script=None):
     args = parse_args(argv, model, script)
     rank = int(os.environ.get("RANK", "0"))
@@ -299,7 +320,7 @@ def main(argv=None, model=None, script=None):
     names = get_feature_names(cols + cols)
     model = build_model(args, cols)
     # final mode compiles without metrics: a single-class batch would make AUC undefined (xdftrain.py:607-621)
-    model.compile(optimizer=args.optimizer, loss="binary_crossentropy",
+    model.compile(optimizer=make_optimizer(args, model), loss="binary_crossentropy",
                   metrics=[] if final else ["binary_crossentropy", "auc"])
     for pg in model.optim.param_groups:
         pg["lr"] = args.learning_rate
