@@ -68,6 +68,8 @@
  * (masked) position instead of dropping it -- a correction of the values, no struct or signature changed, the version stays 8.
  * xdfm_sgdm_step, xdfm_sgdm_step_deferred, xdfm_sgdm_catchup_rows, xdfm_sgdm_flush (K7m / K7md: SGD with momentum, plain or
  * Nesterov; xdfm_opt_tensor keeps its 48 bytes, `state` is the momentum buffer) -- additions, the version stays 8.
+ * xdfm_finish_batch_begin, xdfm_finish_batch_run, xdfm_finish_batch_active, xdfm_finish and the option "finish_batch" (the
+ * one-block "finish" launches of a train step collected into one launch) -- additions, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -156,6 +158,43 @@ int xdfm_get_option(const char* key);
  * ten launches fewer per train step, identical results.  The kernels reset the tickets they use; one calling thread and
  * one stream per device at a time (as for the rest of the library). */
 int xdfm_set_ticket_board(unsigned* board, int slots);
+/* Finish batch: the same saving without tickets.  Between xdfm_finish_batch_begin() and xdfm_finish_batch_run(stream), on
+ * the current device, every entry point that would launch a finish kernel of its own (the dbias of xdfm_cin_dout_det /
+ * xdfm_cin_bwd_prep, the split sums of xdfm_dense_bwd_w / _drop / xdfm_dense_prelu_bwd_w with its slope, xdfm_colsum /
+ * xdfm_relu_bwd_colsum, the loss of xdfm_head_fwd* and the parameter gradients of xdfm_head_bwd*, the L2 value of
+ * xdfm_adam_step* and the cell of xdfm_adam_apply_rows) records a job instead; _run issues ONE launch over all recorded jobs
+ * (16 to a launch: a longer list takes more launches), whose job table travels in the kernel arguments -- no copy, no memset
+ * node, capturable.  Every sum keeps its order: the results are bit-identical to the separate launches.
+ *   - The deferred OUTPUTS (dbias, dW / db / dalpha of a layer with more than one split, the column sums, the loss, the head's
+ *     grads, l2_value) and the `cell` are undefined until _run; the partials' workspaces must stay allocated and untouched
+ *     until then.  The caller must not read a deferred output before _run, on the device or on the host.
+ *   - The finish of xdfm_adam_apply_rows rides behind the L2 finish that sets the same l2_value; a job that reads what an
+ *     earlier job of the batch writes, and cannot ride behind it, first sends the recorded jobs off in a launch of their own.
+ *   - Inside a batch the CIN dbias is STORED (0 + sum), not accumulated: it need not be zeroed (xdfm_finish_batch_active
+ *     tells a caller whether that holds for the next call).
+ *   - A registered ticket board takes precedence: kernels that take tickets finish themselves, nothing is recorded for them.
+ *   - Errors (XDFM_ERR_INVALID): _begin while a batch is open; a job or _run on another stream than the batch's first job; a
+ *     job, _begin or _run on another device than the open batch's.  _run without an open batch, or with no recorded job,
+ *     launches nothing and returns XDFM_OK.  A failed _run leaves the batch open.  One batch at a time per process.
+ *   - Option "finish_batch" (default 1): 0 = _begin opens nothing, every finish stays its own launch (A/B runs).
+ * xdfm_finish_batch_active: 1 when jobs are being recorded on the current device (a batch is open, no ticket board), else 0.
+ * xdfm_finish: ONE finish over partials the caller supplies -- exactly what the entry points above call after their main
+ * kernel: recorded in the open batch, else launched.  For tests and tools.  kind / arguments (others 0 / NULL):
+ *   0 CIN dbias    part [i0 = H][i1 = partials per row] -> out [H] (+= outside a batch)
+ *   1 dense dW     part = ws (xdfm_dense_bwd_w's layout: i0 = nsplit slabs [n0 = out][n1 = in], then nsplit x [out] for db),
+ *                  out = dW, out2 = db or NULL; PReLU: part2 = i1 double partials, out3 = dalpha or NULL.  One split and no
+ *                  dalpha: nothing to do (the main kernel's dW, db are final)
+ *   2 column sums  part [64][i0 = cols] -> out [cols]
+ *   3 head loss    part [128] -> out [1]
+ *   4 head grads   part [128][i0 = KT] -> out [KT]
+ *   5 Adam L2      part [i0 = n] -> out [1]
+ *   6 rows cell    out2 = cell (8-byte aligned): out[0] += cell / 2^40 (out may be NULL), cell = 0
+ *   7 add          out[0] = part[0] + part2[0] (fp32): the step's total loss; rides behind the job that writes part2 */
+int xdfm_finish_batch_begin(void);
+int xdfm_finish_batch_run(void* stream);
+int xdfm_finish_batch_active(void);
+int xdfm_finish(int kind, const void* part, const void* part2, void* out, void* out2, void* out3, long n0, long n1, int i0, int i1,
+                void* stream);
 /* [host] node types of a captured hipGraph_t (the host side replays the train step from a HIP graph):
  * memset nodes are counted separately because they are not ordered reliably against neighbouring kernel
  * nodes on ROCm 7.2 / gfx950 (tools/graph_memset_probe.py) -- a graph with n_memset > 0 must not be replayed;

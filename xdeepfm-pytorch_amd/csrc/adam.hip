@@ -16,6 +16,7 @@
 // the pre-update weights (per-block partials summed in a fixed order by adam_l2_finish_kernel).  That removes
 // two table-sized passes per step (sum of squares; gradient initialisation) from the train step.
 #include "xdfm_internal.h"
+#include "finish_batch.h"
 #include "adam_math.h"
 #include "table_step.h"    // the streaming accesses, the chunk claim, the launch order and the grid composer
 
@@ -29,7 +30,7 @@
 // 1.9 GB, 4.4-5.5 TB/s at the 7.7 GB this step sweeps -- K7 runs at 5.0-5.5 TB/s (tools/adam_probe.py), the rate the
 // memory system gives this footprint.
 
-#define ADAM_FIX 1099511627776.0          // 2^40: fixed-point scale of the L2 backlog (integer adds: order-independent)
+// ADAM_FIX (2^40), the fixed-point scale of the L2 backlog (integer adds: order-independent): finish_batch.h
 
 #define ADAM_CHUNK 64
 // first[k] = first block of tensor k in the launch's 1-D grid (first[cnt] = grid size), see tbl_grid (table_step.h)
@@ -312,15 +313,18 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
 
 __global__ __launch_bounds__(1024) void adam_l2_finish_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
     __shared__ float acc[1024];
-    float v = 0.f;
-    for (int k = threadIdx.x; k < n; k += 1024) v += part[k];
-    acc[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-        if (threadIdx.x < o) acc[threadIdx.x] += acc[threadIdx.x + o];
-        __syncthreads();
-    }
+    adam_l2_finish_block<1024>(part, n, acc);
     if (threadIdx.x == 0) out[0] = acc[0];
+}
+// a job of the open finish batch (finish_batch.h), else its own launch
+int xdfm_adam_l2_finish(const float* part, int n, float* out, hipStream_t st) {
+    FinishJob j{};
+    j.kind = FJ_ADAM_L2; j.blocks = 1;
+    j.part = part; j.out = out; j.i0 = n;
+    bool taken = false;
+    if (int rc = xdfm_finish_defer(j, st, &taken)) return rc;
+    if (!taken) hipLaunchKernelGGL(adam_l2_finish_kernel, dim3(1), dim3(1024), 0, st, part, n, out);
+    return XDFM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -700,10 +704,17 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_by_row_kernel(
 }
 
 __global__ void adam_rows_finish_kernel(unsigned long long* __restrict__ cell, float* __restrict__ l2_value) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        if (l2_value) l2_value[0] += (float)((double)(long long)cell[0] / ADAM_FIX);
-        cell[0] = 0ull;
-    }
+    if (threadIdx.x == 0 && blockIdx.x == 0) adam_rows_finish_one(cell, l2_value);
+}
+// a job of the open finish batch (finish_batch.h: behind the L2 finish that sets the same l2_value), else its own launch
+int xdfm_adam_rows_finish(unsigned long long* cell, float* l2_value, hipStream_t st) {
+    FinishJob j{};
+    j.kind = FJ_ADAM_ROWS; j.blocks = 1;
+    j.cell = cell; j.out = l2_value;
+    bool taken = false;
+    if (int rc = xdfm_finish_defer(j, st, &taken)) return rc;
+    if (!taken) hipLaunchKernelGGL(adam_rows_finish_kernel, dim3(1), dim3(64), 0, st, cell, l2_value);
+    return XDFM_OK;
 }
 
 // Every chunk of the deferred tensors up to the clock; `last` back to 0.  Same 1-D grid as the step.
@@ -928,7 +939,8 @@ static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_ada
                                lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts, l2_value, l2_total, tk);
         slot0 += batch.first[cnt];
     }
-    if (l2_value && !ticket) hipLaunchKernelGGL(adam_l2_finish_kernel, dim3(1), dim3(1024), 0, st, l2_ws, slot0, l2_value);
+    if (l2_value && !ticket)
+        if (int rc = xdfm_adam_l2_finish(l2_ws, slot0, l2_value, st)) return rc;
     return xdfm_check_launch("adam_step");
 }
 
@@ -978,7 +990,7 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
         hipLaunchKernelGGL(adam_apply_rows_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0,
                            clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell), l2_value, ticket);
     if (!ticket)
-        hipLaunchKernelGGL(adam_rows_finish_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<unsigned long long*>(l2_cell), l2_value);
+        if (int rc = xdfm_adam_rows_finish(reinterpret_cast<unsigned long long*>(l2_cell), l2_value, st)) return rc;
     return xdfm_check_launch("adam_apply_rows");
 }
 

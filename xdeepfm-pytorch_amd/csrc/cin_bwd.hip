@@ -9,6 +9,7 @@
 // The reference stores Z (1.5 GB per step at B=4096, D=16, cin=(256,128,128)) for these two
 // products; here both kernels rebuild their Z / dZ tiles in registers.
 #include "xdfm_internal.h"
+#include "finish_batch.h"
 
 // =============================================================================================
 // dOut + dbias
@@ -94,11 +95,17 @@ __global__ __launch_bounds__(256) void cin_dout_kernel(
 }
 
 __global__ void cin_dbias_finish_kernel(const float* __restrict__ part, int H, int gx, float* __restrict__ dbias) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= H) return;
-    float s = 0.f;
-    for (int k = 0; k < gx; ++k) s += part[(long)h * gx + k];
-    dbias[h] += s;
+    cin_dbias_finish_row(blockIdx.x * blockDim.x + threadIdx.x, part, H, gx, dbias, false);
+}
+// the finish of a level's dbias: a job of the open finish batch (finish_batch.h), else its own launch
+int xdfm_cin_dbias_finish(const float* part, int H, int gx, float* dbias, hipStream_t st) {
+    FinishJob j{};
+    j.kind = FJ_CIN_DBIAS; j.blocks = ceil_div(H, FINISH_THREADS);
+    j.part = part; j.out = dbias; j.i0 = H; j.i1 = gx; j.i2 = 1;
+    bool taken = false;
+    if (int rc = xdfm_finish_defer(j, st, &taken)) return rc;
+    if (!taken) hipLaunchKernelGGL(cin_dbias_finish_kernel, dim3(ceil_div(H, 64)), dim3(64), 0, st, part, H, gx, dbias);
+    return XDFM_OK;
 }
 
 // =============================================================================================
@@ -807,7 +814,8 @@ static int cin_dout_impl(const float* A, const unsigned* mask, long mask_ld, int
     else
         hipLaunchKernelGGL(cin_dout_kernel<1>, dim3(gx, H), dim3(256), 0, (hipStream_t)stream, A, H, N, D,
                            act, dh, hid0, hid_rows, dd, dir_mode, lddir, dir_off, dir0, dir_rows, dOut, dbias, ws, ticket, mask, mask_ld);
-    if (ws && !ticket) hipLaunchKernelGGL(cin_dbias_finish_kernel, dim3(ceil_div(H, 64)), dim3(64), 0, (hipStream_t)stream, ws, H, gx, dbias);
+    if (ws && !ticket)
+        if (int rc = xdfm_cin_dbias_finish(ws, H, gx, dbias, (hipStream_t)stream)) return rc;
     return xdfm_check_launch("cin_dout");
 }
 
@@ -932,8 +940,7 @@ int xdfm_cin_bwd_prep(const float* A, const unsigned* mask, long mask_ld, int H,
                          ticket, xp, x0, Hp, m, bww_ws, st);
     if (rc) return rc;
     if (!ticket)
-        hipLaunchKernelGGL(cin_dbias_finish_kernel, dim3(ceil_div(H, 64)), dim3(64), 0, st, dout_ws, H,
-                           x3_bwd_prep_blocks(xp == x0, H, Hp, m, N), dbias);
+        if (int rc2 = xdfm_cin_dbias_finish(dout_ws, H, x3_bwd_prep_blocks(xp == x0, H, Hp, m, N), dbias, st)) return rc2;
     *prepared = 1;
     return xdfm_check_launch("cin_bwd_prep");
 }

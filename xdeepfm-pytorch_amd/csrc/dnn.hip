@@ -42,6 +42,7 @@
 // kernel as the bias gradient is: the blocks that leave the bias partials also leave one partial per (tile of out, split),
 // products and sums in double, and the finish launch adds them in a fixed order and rounds once.
 #include "xdfm_internal.h"
+#include "finish_batch.h"
 
 #define DN_T 64                    // tile edge (rows and columns of C per workgroup)
 #define DN_K 32                    // contraction indices per LDS stage
@@ -50,7 +51,6 @@
 #define DN_PLANE (DN_T * 4 + 8)    // floats per plane (8 of padding)
 #define DN_TILE (8 * DN_PLANE)     // floats per operand tile
 #define DN_SPLIT_ROWS 256          // rows of the contraction per dW split
-#define DN_MAX_SPLIT 32
 #define DN_MAX_DIM (1 << 20)       // in, out
 
 struct DnArgs {
@@ -311,34 +311,6 @@ __global__ __launch_bounds__(DN_NW * 64) void dense_mfma_kernel(DnArgs a) {
     }
 }
 
-// dW[e] = sum over the splits of slab[z][e], db[c] likewise, over a fixed pairwise tree: eight splits at a time, then the
-// (at most DN_MAX_SPLIT / 8) sums of eight.  A running sum in split order rounds once per split at the magnitude of the total:
-// at 29 splits the bias gradient's error was 3 ulp, three times that of a pairwise column sum of the same values.
-__device__ __forceinline__ void dn_finish_elem(long e, const float* __restrict__ ws, int nsplit, long mn, long m,
-                                               float* __restrict__ dW, float* __restrict__ db) {
-    const long total = mn + (db ? m : 0);
-    if (e >= total) return;
-    const float* p = e < mn ? ws + e : ws + (long)nsplit * mn + (e - mn);
-    const long pitch = e < mn ? mn : m;
-    float q[DN_MAX_SPLIT / 8];
-#pragma unroll
-    for (int i = 0; i < DN_MAX_SPLIT / 8; ++i) {
-        const int z = 8 * i;
-        q[i] = 0.f;
-        if (z < nsplit) {                              // uniform; eight loads in flight, a split past the end counts as 0
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = p[(long)(z + j < nsplit ? z + j : nsplit - 1) * pitch];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = z + j < nsplit ? v[j] : 0.f;
-            q[i] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-        }
-    }
-    static_assert(DN_MAX_SPLIT == 32, "the tree below adds four sums of eight splits");
-    const float sum = (q[0] + q[1]) + (q[2] + q[3]);
-    if (e < mn) dW[e] = sum;
-    else db[e - mn] = sum;
-}
 __global__ __launch_bounds__(256) void dense_bwd_w_finish_kernel(const float* __restrict__ ws, int nsplit, long mn, long m,
                                                                  float* __restrict__ dW, float* __restrict__ db) {
     dn_finish_elem((long)blockIdx.x * 256 + threadIdx.x, ws, nsplit, mn, m, dW, db);
@@ -355,10 +327,27 @@ __global__ __launch_bounds__(256) void dense_prelu_bwd_w_finish_kernel(const flo
         return;
     }
     __shared__ double sm[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < npart; i += 256) s += dapart[i];
-    s = xdfm_block_sum_f64(s, sm);
-    if (threadIdx.x == 0) *dalpha = (float)s;
+    dn_dalpha_finish_block(dapart, npart, dalpha, sm);
+}
+// the finish of a layer's dW / db (/ dalpha): a job of the open finish batch (finish_batch.h), else its own launch; eblocks = 0
+// and no dalpha: nothing to do (a single split's dW and db are final)
+int xdfm_dense_w_finish(const float* ws, int nsplit, long mn, long m, float* dW, float* db, bool prelu, const double* dapart, int npart,
+                        float* dalpha, hipStream_t st) {
+    const unsigned eblocks = nsplit > 1 ? (unsigned)ceil_div(mn + (db ? m : 0), 256) : 0u;
+    if (!eblocks && !(prelu && dalpha)) return XDFM_OK;
+    FinishJob j{};
+    j.kind = FJ_DENSE_W; j.blocks = (int)eblocks + (prelu && dalpha ? 1 : 0);
+    j.part = ws; j.i0 = nsplit; j.n0 = mn; j.n1 = m; j.out = dW; j.out2 = db; j.i1 = (int)eblocks;
+    if (prelu) { j.part2 = dapart; j.i2 = npart; j.out3 = dalpha; }
+    bool taken = false;
+    if (int rc = xdfm_finish_defer(j, st, &taken)) return rc;
+    if (taken) return XDFM_OK;
+    if (prelu)
+        hipLaunchKernelGGL(dense_prelu_bwd_w_finish_kernel, dim3(eblocks + (dalpha ? 1u : 0u)), dim3(256), 0, st, ws, nsplit, mn, m, dW,
+                           db, eblocks, dapart, npart, dalpha);
+    else
+        hipLaunchKernelGGL(dense_bwd_w_finish_kernel, dim3(eblocks), dim3(256), 0, st, ws, nsplit, mn, m, dW, db);
+    return XDFM_OK;
 }
 
 static inline bool dn_supported(long rows, long in, long out) {
@@ -522,12 +511,7 @@ static int dn_bwd_w(const char* who, const float* g, long ldg, const float* x, l
     else if (gate.kind == DnGate::RELU) DN_LAUNCH(false, false, true, DN_EPI_SLAB, grid, st, a);
     else DN_LAUNCH(false, false, false, DN_EPI_SLAB, grid, st, a);
     // the finish over the splits (none with a single split, whose dW and db are final); PReLU's has one more block for the slope
-    const unsigned eblocks = nsplit > 1 ? (unsigned)ceil_div(mn + (db ? out : 0), 256) : 0u;
-    if (prelu && (eblocks || dalpha))
-        hipLaunchKernelGGL(dense_prelu_bwd_w_finish_kernel, dim3(eblocks + (dalpha ? 1u : 0u)), dim3(256), 0, st, ws, nsplit, mn,
-                           (long)out, dW, db, eblocks, dapart, nsplit * mtiles, dalpha);
-    else if (!prelu && eblocks)
-        hipLaunchKernelGGL(dense_bwd_w_finish_kernel, dim3(eblocks), dim3(256), 0, st, ws, nsplit, mn, (long)out, dW, db);
+    if (int rc = xdfm_dense_w_finish(ws, nsplit, mn, (long)out, dW, db, prelu, dapart, nsplit * mtiles, dalpha, st)) return rc;
     return xdfm_check_launch(who);
 }
 

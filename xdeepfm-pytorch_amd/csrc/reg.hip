@@ -10,6 +10,7 @@
 // Deterministic: every tensor is reduced by a fixed grid of REG_BLOCKS blocks into partials that a
 // single block sums in a fixed order.
 #include "xdfm_internal.h"
+#include "finish_batch.h"
 
 #define REG_BLOCKS 32
 #define REG_THREADS 256
@@ -123,7 +124,7 @@ int xdfm_l2_reg_bwd(const float* const* ptrs, const long* numel, const float* co
 // graph is not reliably ordered against its neighbouring kernel nodes on this stack
 // (tools/graph_memset_probe.py: 3 of 4 replays wrong), so the train step uses this two-launch,
 // atomics-free, fixed-order version instead.
-#define CS_ROWBLK 64
+// CS_ROWBLK (64) row blocks: finish_batch.h
 // the CS_ROWBLK partials of every column, summed in the order of colsum_finish_kernel (4 groups of 16, then the groups),
 // by the block that finished last (xdfm_last_block_done): same bits, no launch of its own
 __device__ __forceinline__ void colsum_finish_all(const float* __restrict__ part, int cols, float* __restrict__ out) {
@@ -205,17 +206,18 @@ __global__ __launch_bounds__(256) void relu_bwd_colsum_partial_kernel(const floa
 
 // 64 columns per block, the CS_ROWBLK partials of a column summed by 4 threads in a fixed order
 __global__ __launch_bounds__(256) void colsum_finish_kernel(const float* __restrict__ part, int cols, float* __restrict__ out) {
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int q = threadIdx.x >> 6;
-    float s = 0.f;
-    if (c < cols) {
-#pragma unroll
-        for (int k = 0; k < CS_ROWBLK / 4; ++k) s += part[(long)(q * (CS_ROWBLK / 4) + k) * cols + c];
-    }
-    __shared__ float red[4][64];
-    red[q][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (q == 0 && c < cols) out[c] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    __shared__ float red[4 * 64];
+    colsum_finish_block(blockIdx.x, part, cols, out, red);
+}
+// a job of the open finish batch (finish_batch.h), else its own launch
+int xdfm_colsum_finish(const float* part, int cols, float* out, hipStream_t st) {
+    FinishJob j{};
+    j.kind = FJ_COLSUM; j.blocks = ceil_div(cols, 64);
+    j.part = part; j.out = out; j.i0 = cols;
+    bool taken = false;
+    if (int rc = xdfm_finish_defer(j, st, &taken)) return rc;
+    if (!taken) hipLaunchKernelGGL(colsum_finish_kernel, dim3(ceil_div(cols, 64)), dim3(256), 0, st, part, cols, out);
+    return XDFM_OK;
 }
 
 extern "C" {
@@ -228,7 +230,8 @@ int xdfm_colsum(const float* g, long rows, int cols, long ld, float* ws, float* 
     hipStream_t st = (hipStream_t)stream;
     unsigned* ticket = ceil_div(cols, 64) <= TK_ROWS ? xdfm_ticket(TK_ROW0) : nullptr;
     hipLaunchKernelGGL(colsum_partial_kernel, dim3(ceil_div(cols, 64), CS_ROWBLK), dim3(256), 0, st, g, rows, cols, ld, ws, out, ticket);
-    if (!ticket) hipLaunchKernelGGL(colsum_finish_kernel, dim3(ceil_div(cols, 64)), dim3(256), 0, st, ws, cols, out);
+    if (!ticket)
+        if (int rc = xdfm_colsum_finish(ws, cols, out, st)) return rc;
     return xdfm_check_launch("colsum");
 }
 
@@ -240,7 +243,8 @@ int xdfm_relu_bwd_colsum(const float* g, const float* y, long rows, int cols, lo
     unsigned* ticket = ceil_div(cols, 64) <= TK_ROWS ? xdfm_ticket(TK_ROW0) : nullptr;
     hipLaunchKernelGGL(relu_bwd_colsum_partial_kernel, dim3(ceil_div(cols, 64), CS_ROWBLK), dim3(256), 0, st, g, y, rows, cols,
                        ldg, ldy, gz, ws, out, ticket);
-    if (!ticket) hipLaunchKernelGGL(colsum_finish_kernel, dim3(ceil_div(cols, 64)), dim3(256), 0, st, ws, cols, out);
+    if (!ticket)
+        if (int rc = xdfm_colsum_finish(ws, cols, out, st)) return rc;
     return xdfm_check_launch("relu_bwd_colsum");
 }
 
@@ -274,7 +278,7 @@ int xdfm_relu_bwd_colsum(const float* g, const float* y, long rows, int cols, lo
 //   any link  any loss   term -> fl(w * term)   g -> fl(w * g)            one rounding more than the row above
 // Everything after g (dlin, du, dv, the column sums, dbias) and the order of every sum are those of the unweighted
 // instances; w is not range-checked here (w = 0 and a finite pred: exact zeros).
-#define HEAD_BLOCKS 128
+// HEAD_BLOCKS (128) workgroups: finish_batch.h
 #define HEAD_THREADS 256
 enum { HEAD_SIGMOID = XDFM_LINK_SIGMOID, HEAD_IDENTITY = XDFM_LINK_IDENTITY };
 enum { HEAD_BCE = XDFM_LOSS_BCE, HEAD_MSE = XDFM_LOSS_MSE, HEAD_MAE = XDFM_LOSS_MAE };
@@ -401,12 +405,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(
 
 __global__ __launch_bounds__(HEAD_BLOCKS) void head_fwd_finish_kernel(const float* __restrict__ part, float* __restrict__ loss) {
     __shared__ float red[HEAD_BLOCKS];
-    red[threadIdx.x] = part[threadIdx.x];
-    __syncthreads();
-    for (int o = HEAD_BLOCKS / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    head_fwd_finish_block(part, red);
     if (threadIdx.x == 0) loss[0] = red[0];
 }
 
@@ -537,11 +536,26 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_vec_kernel(
 }
 
 __global__ void head_bwd_finish_kernel(const float* __restrict__ part, int KT, float* __restrict__ out) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= KT) return;
-    float s = 0.f;
-    for (int b = 0; b < HEAD_BLOCKS; ++b) s += part[(long)b * KT + k];
-    out[k] = s;
+    head_bwd_finish_elem(blockIdx.x * blockDim.x + threadIdx.x, part, KT, out);
+}
+// jobs of the open finish batch (finish_batch.h), else their own launches
+int xdfm_head_fwd_finish(const float* part, float* loss, hipStream_t st) {
+    FinishJob j{};
+    j.kind = FJ_HEAD_FWD; j.blocks = 1;
+    j.part = part; j.out = loss;
+    bool taken = false;
+    if (int rc = xdfm_finish_defer(j, st, &taken)) return rc;
+    if (!taken) hipLaunchKernelGGL(head_fwd_finish_kernel, dim3(1), dim3(HEAD_BLOCKS), 0, st, part, loss);
+    return XDFM_OK;
+}
+int xdfm_head_bwd_finish(const float* part, int KT, float* out, hipStream_t st) {
+    FinishJob j{};
+    j.kind = FJ_HEAD_BWD; j.blocks = ceil_div(KT, FINISH_THREADS);
+    j.part = part; j.out = out; j.i0 = KT;
+    bool taken = false;
+    if (int rc = xdfm_finish_defer(j, st, &taken)) return rc;
+    if (!taken) hipLaunchKernelGGL(head_bwd_finish_kernel, dim3(ceil_div(KT, 256)), dim3(256), 0, st, part, KT, out);
+    return XDFM_OK;
 }
 
 extern "C" {
@@ -586,7 +600,8 @@ static int head_fwd_launch(const float* lin, const float* u, const float* wu, in
     HEAD_DISPATCH(HEAD_FWD_LAUNCH)
 #undef HEAD_FWD_LAUNCH
 #undef HEAD_FWD_GO
-    if (!ticket) hipLaunchKernelGGL(head_fwd_finish_kernel, dim3(1), dim3(HEAD_BLOCKS), 0, st, ws, loss_out);
+    if (!ticket)
+        if (int rc = xdfm_head_fwd_finish(ws, loss_out, st)) return rc;
     return xdfm_check_launch("head_fwd");
 }
 
@@ -631,7 +646,8 @@ static int head_bwd_launch(const float* pred, const float* y, const float* gloss
     HEAD_DISPATCH(HEAD_BWD_LAUNCH)
 #undef HEAD_BWD_LAUNCH
 #undef HEAD_BWD_GO
-    if (!ticket) hipLaunchKernelGGL(head_bwd_finish_kernel, dim3(ceil_div(KT, 256)), dim3(256), 0, st, ws, KT, grads);
+    if (!ticket)
+        if (int rc = xdfm_head_bwd_finish(ws, KT, grads, st)) return rc;
     return xdfm_check_launch("head_bwd");
 }
 

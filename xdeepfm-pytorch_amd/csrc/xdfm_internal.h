@@ -42,6 +42,7 @@ enum {
     OPT_LAST_ADAM_ROWS,  // read-only probe: 1 / 0 = the last of those two calls launched the by-row / the by-chunk kernel, -1 before
     OPT_OPT_BX,          // 0 = default (512 / 512 / 4096: OPT_BX, OPTD_BX, OPTD_FLUSH_BX); most blocks one tensor gets in the
                          //   SGD / Adagrad / RMSprop sweep, deferred step scan and flush
+    OPT_FINISH_BATCH,    // 1 (default) = xdfm_finish_batch_begin opens a batch; 0 = it opens none and every finish stays its own launch
     OPT_COUNT
 };
 // value of the instance probes: row tiles (forward MT, dX HBT, dW MT) * 1000 + waves * 100 + MFMA terms * 10 + folded level 0

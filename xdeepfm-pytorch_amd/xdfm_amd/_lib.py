@@ -25,6 +25,10 @@ SIGNATURES = {
     "xdfm_get_option": (c_int, [c_char_p]),
     "xdfm_graph_node_census": (c_int, [P, P, P, P]),
     "xdfm_set_ticket_board": (c_int, [P, c_int]),
+    "xdfm_finish_batch_begin": (c_int, []),
+    "xdfm_finish_batch_run": (c_int, [P]),
+    "xdfm_finish_batch_active": (c_int, []),
+    "xdfm_finish": (c_int, [c_int, P, P, P, P, P, c_long, c_long, c_int, c_int, P]),
     "xdfm_embed_gather_fwd": (c_int, [P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, c_int, P, P, P, P, P]),
     "xdfm_embed_gather_fwd_ld": (c_int, [P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, c_int, P, P, c_long, c_int, P, P, P]),
     "xdfm_varlen_pool_fwd": (c_int, [P, c_long, c_int, P, P, c_int, c_int, c_int, P, P, c_long, c_int, P, P, P, P]),

@@ -634,17 +634,10 @@ class BaseModel(nn.Module):
             y_pred, loss, stash = self._split_step_first(x, y, sw)
             return self._split_step_second(y_pred, loss, stash, fuse)
         self.optim.zero_grad()
-        y_pred, loss = self._loss_forward(x, y) if sw is None else self._loss_forward(x, y, sw)
         if fuse is not None:
-            # gradient and value of the L2 term come from K7 (added after the gradient all-reduce when row-parallel:
-            # the term is identical on every replica and must count once)
-            self.optim.arm_l2(*fuse)
-            total_loss = loss if self._aux_unset else loss + self.aux_loss
-            total_loss = self._with_step_extra(total_loss)
-            total_loss.backward(self._unit_grad(total_loss))
-            if dp is not None:
-                dp.reduce_dense_grads(self)
-        elif dp is None:
+            return self._train_step_fused_l2(x, y, sw, dp, fuse)
+        y_pred, loss = self._loss_forward(x, y) if sw is None else self._loss_forward(x, y, sw)
+        if dp is None:
             reg_loss = self.get_regularization_loss(_defer_tables=True)
             total_loss = self._with_step_extra(loss + reg_loss + self.aux_loss)
             total_loss.backward()
@@ -661,10 +654,38 @@ class BaseModel(nn.Module):
             (reg_d + self.aux_loss).backward()
             total_loss = self._with_step_extra(loss.detach() + reg_t.detach() + reg_d.detach() + self.aux_loss).detach()
         self.optim.step()
-        if fuse is not None and self.optim.l2_value is not None:
-            total_loss = total_loss.detach() + self.optim.l2_value
         # detached: a caller that keeps these alive must not keep the step's autograd graph (and with it the
         # parameters' AccumulateGrad nodes and their stream) alive into the next step
+        return y_pred.detach(), loss.detach(), total_loss.detach()
+
+    def _train_step_fused_l2(self, x, y, sw, dp, fuse):
+        """The step whose L2 term (gradient and value) comes from K7 (added after the gradient all-reduce when row-parallel:
+        the term is identical on every replica and must count once).  Its one-block finish launches run as two finish batches
+        (ops.finish_batch_begin): one for forward + backward, run before anything reads a gradient, and one for the
+        optimizer.  The head's loss value joins the first: with the data loss as the whole objective nothing reads it before
+        the step's last line; a further term (aux_loss, `_step_extra`) is added to it on the device, so the batch runs first."""
+        ops.finish_batch_begin()
+        try:
+            y_pred, loss = self._loss_forward(x, y) if sw is None else self._loss_forward(x, y, sw)
+            self.optim.arm_l2(*fuse)
+            if not self._aux_unset or self.__dict__.get("_step_extra") is not None:
+                ops.finish_batch_flush()
+            total_loss = loss if self._aux_unset else loss + self.aux_loss
+            total_loss = self._with_step_extra(total_loss)
+            total_loss.backward(self._unit_grad(total_loss))
+            ops.finish_batch_run()
+            if dp is not None:
+                dp.reduce_dense_grads(self)
+            ops.finish_batch_begin()
+            self.optim.step()
+            l2 = self.optim.l2_value
+            if l2 is not None:
+                a = total_loss.detach()
+                total_loss = ops.finish_add(a, l2)      # behind the finish that leaves the value, in the optimizer's batch
+            ops.finish_batch_run()
+        except BaseException:
+            ops.finish_batch_run(quiet=True)
+            raise
         return y_pred.detach(), loss.detach(), total_loss.detach()
 
     def _global_batch_labels(self, y):

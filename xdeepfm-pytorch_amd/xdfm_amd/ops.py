@@ -40,6 +40,71 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+# Finish batch (include/xdfm.h, xdfm_finish_batch_begin): inside the model's own train step the one-block finish launches of
+# the backward, and those of the optimizer, are collected and run as one launch each.  A deferred finish reads its partials
+# when the batch runs, long after the op that made them has returned and dropped its workspace: `finish_keep` holds those
+# tensors until then (the caching allocator would hand their memory to the next op on the same stream).
+FJ_ADD = 7                       # `kind` of xdfm_finish: out[0] = a[0] + b[0]
+_FINISH_OPEN = False             # finish_batch_begin without its finish_batch_run yet
+_FINISH_KEEP = None              # a list while the library records finishes for that batch
+
+
+def finish_batch_begin():
+    """Opens a batch on the current device (nothing opens with the option "finish_batch" at 0).  Pair with finish_batch_run."""
+    global _FINISH_OPEN, _FINISH_KEEP
+    lib = _lib.load()
+    _lib.check(lib.xdfm_finish_batch_begin(), "finish_batch_begin")
+    _FINISH_OPEN = True
+    _FINISH_KEEP = [] if lib.xdfm_finish_batch_active() else None      # option at 0, or a ticket board: nothing is recorded
+
+
+def finish_batch_run(quiet=False):
+    """Runs and closes the open batch (no-op without one); `quiet`: on an error path, never raises."""
+    global _FINISH_OPEN, _FINISH_KEEP
+    if not _FINISH_OPEN:
+        return
+    try:
+        rc = _lib.load().xdfm_finish_batch_run(_stream())
+        if not quiet:
+            _lib.check(rc, "finish_batch_run")
+    except Exception:            # noqa: BLE001
+        if not quiet:
+            raise
+    finally:
+        _FINISH_OPEN, _FINISH_KEEP = False, None
+
+
+def finish_batch_flush():
+    """Runs what the open batch holds and opens the next one: before the host issues work that reads a deferred output."""
+    if _FINISH_OPEN:
+        finish_batch_run()
+        finish_batch_begin()
+
+
+def finish_active():
+    """True when the library records the next finish instead of launching it: its output must not be read before
+    finish_batch_run, its workspace goes to finish_keep."""
+    return _FINISH_KEEP is not None and bool(_lib.load().xdfm_finish_batch_active())
+
+
+def finish_add(a, b):
+    """a + b where b may be a deferred output of the open batch (the step's total loss + the optimizer's L2 value): for two
+    fp32 one-element tensors a job of that batch, run behind the finish that writes b -- the sum is then as deferred as b.
+    Anything else: the batch is flushed and torch adds."""
+    if finish_active() and a.numel() == 1 and b.numel() == 1 and a.dtype == b.dtype == torch.float32 and a.device == b.device:
+        out = torch.empty(torch.broadcast_shapes(a.shape, b.shape), dtype=torch.float32, device=a.device)
+        _lib.check(_lib.load().xdfm_finish(FJ_ADD, _ptr(a), _ptr(b), _ptr(out), None, None, 0, 0, 0, 0, _stream()), "finish add")
+        finish_keep(a, b)
+        return out
+    finish_batch_flush()
+    return a + b
+
+
+def finish_keep(*tensors):
+    if _FINISH_KEEP is not None:
+        _FINISH_KEEP.extend(t for t in tensors if t is not None)
+
+
 def _need_cuda(t: torch.Tensor, name: str):
     if t.is_cuda:
         _lib.ticket_board(t.device)
@@ -694,7 +759,8 @@ class CINStack(torch.autograd.Function):
         dx0_set = False
         grads = [None] * (2 * L)
         dhid = None                                  # gradient w.r.t. this level's hidden rows
-        dbias_all = torch.zeros(sum(lv[0] for lv in levels), dtype=torch.float32, device=dev)   # one fill for all levels
+        # one fill for all levels; none inside a finish batch, whose dbias finish stores 0 + sum instead of adding
+        dbias_all = (torch.empty if finish_active() else torch.zeros)(sum(lv[0] for lv in levels), dtype=torch.float32, device=dev)
         dbias_off = [sum(lv[0] for lv in levels[:k]) for k in range(L)]
         for l in range(L - 1, -1, -1):
             H, Hp, hid, dir0, drows, off = levels[l]
@@ -714,6 +780,7 @@ class CINStack(torch.autograd.Function):
             # planes of dOut and the dW kernel's scales, straight into the dW workspace (xdfm_cin_bwd_prep)
             dws = torch.empty(lib.xdfm_cin_bwd_prep_ws_elems(H, Hp, m, B, D), dtype=torch.float32, device=dev)   # fixed-order dbias
             ws = torch.empty(lib.xdfm_cin_bwd_w_ws_elems(H, Hp, m, N), dtype=torch.float32, device=dev) if need_dw else None
+            finish_keep(dws)
             prepared = ctypes.c_int(0)
             _lib.check(_run("cin_dout", 0.0, lambda: lib.xdfm_cin_bwd_prep(
                 _ptr(A), _ptr(mk), mk.shape[1] if mk is not None else 0, H, B, D, act, _ptr(dhid) if has_hid else None, 0, hid if has_hid else 0, _ptr(g),
@@ -968,6 +1035,7 @@ def _dense_bwd_native(g, y, x, W, need_dx, need_dw, need_db, p=None, alpha=None,
         db = torch.empty(out, dtype=torch.float32, device=dev) if need_db else None
         da = torch.empty(alpha.shape, dtype=torch.float32, device=dev) if need_da else None
         slope = () if alpha is None else (_ptr(da),)
+        finish_keep(ws)
         _lib.check(_run(name_w, 0.0, lambda: getattr(lib, "xdfm_" + name_w)(*gated, _ptr(x), _ld(x), rows, k, out, _ptr(ws), _ptr(dW),
                                                                           _ptr(db), *slope, *rate, _stream())), name_w)
     grads = (dx, dW if need_dw else None, db)
@@ -981,6 +1049,7 @@ def _bias_grad_lib(g, y=None):
     rows, cols = g.shape
     ws = torch.empty(lib.xdfm_colsum_ws_elems(cols), dtype=torch.float32, device=g.device)
     db = torch.empty(cols, dtype=torch.float32, device=g.device)
+    finish_keep(ws)
     if y is None:
         _lib.check(lib.xdfm_colsum(_ptr(g), rows, cols, g.stride(0), _ptr(ws), _ptr(db), _stream()), "colsum")
         return g, db
@@ -1490,6 +1559,7 @@ class Head(torch.autograd.Function):
         pred = torch.empty(B, dtype=torch.float32, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.xdfm_head_ws_elems(Ku, Kv), dtype=torch.float32, device=dev)
+        finish_keep(ws)
         if w is None:
             _lib.check(lib.xdfm_head_fwd_ex(_ptr(linv), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, _ptr(bias), _ptr(yv), B,
                                             _ptr(pred), _ptr(out), _ptr(ws), int(link), int(loss), _stream()), "head_fwd")
@@ -1519,6 +1589,7 @@ class Head(torch.autograd.Function):
         dv = torch.empty((B, Kv), **f32) if v is not None else None
         grads = torch.empty(Ku + Kv + 1, **f32)
         ws = torch.empty(lib.xdfm_head_ws_elems(Ku, Kv), **f32)
+        finish_keep(ws)
         gl = gloss.reshape(1).contiguous()
         if w is None:
             _lib.check(lib.xdfm_head_bwd_ex(_ptr(pred), _ptr(yv), _ptr(gl), _ptr(u), _ptr(wu), Ku, _ptr(v), _ptr(wv), Kv, B,

@@ -358,10 +358,16 @@ class _TableStep(object):
         """(workspace of the per-block partials, [1] value) for a group's armed L2 term, (None, None) without one."""
         if l2 is None or not any(l2):
             return None, None
-        return torch.empty(ws_elems(T), dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
+        from . import ops
+        ws = torch.empty(ws_elems(T), dtype=torch.float32, device=dev)
+        ops.finish_keep(ws)                     # inside a finish batch the partials are read when the batch runs
+        return ws, torch.empty(1, dtype=torch.float32, device=dev)
 
     def _add_l2(self, val):
         if val is not None:
+            if self.l2_value is not None:
+                from . import ops
+                ops.finish_batch_flush()        # a further group's value: both must be final before they are added
             self.l2_value = val if self.l2_value is None else self.l2_value + val
 
     def _plain(self, group):                    # hyper-parameters the kernel implements
