@@ -70,6 +70,8 @@
  * Nesterov; xdfm_opt_tensor keeps its 48 bytes, `state` is the momentum buffer) -- additions, the version stays 8.
  * xdfm_finish_batch_begin, xdfm_finish_batch_run, xdfm_finish_batch_active, xdfm_finish and the option "finish_batch" (the
  * one-block "finish" launches of a train step collected into one launch) -- additions, the version stays 8.
+ * XDFM_METRIC_*, xdfm_batch_metrics_ws_bytes, xdfm_batch_metrics (K14: the per-batch training metrics of fit() in two
+ * launches) -- additions, the version stays 8.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -1102,6 +1104,34 @@ int xdfm_autodis_fwd(const float* x, long ldx, long B, int F, int K, int D, cons
                      const float* temp, float* out, void* stream);
 int xdfm_autodis_bwd(const float* x, long ldx, long B, int F, int K, int D, const float* meta, const float* const* proj,
                      const float* temp, const float* g, long ldg, int flags, float* ws, float* grads, float* dx, void* stream);
+
+/* ------------------------------------------------------------------ K14: per-batch training metrics (csrc/metrics.hip)
+ * replaces: the sklearn calls the reference's fit makes on host copies of every batch (deepctr/models/basemodel.py:264-269:
+ *           log_loss, roc_auc_score, mean_squared_error, accuracy_score) -- on the device so far float64 ATen compositions
+ *           (xdfm_amd/metrics.py *_device: a sort, two searchsorted and a dozen small kernels for the AUC, a dozen more
+ *           for the logloss; the accuracy through a device-to-host copy and a sync) -- by two launches for any subset of
+ *           the four: a main grid and a one-block finish.  No float atomics, no memset; a repeated call gives the same bits.
+ *   y, p    [B] fp32 labels and predictions (contiguous); which: XDFM_METRIC_* bits, the metrics wanted
+ *   out4    [4] doubles, slot order logloss | auc | mse | accuracy; a slot `which` does not name keeps its bits
+ *   ws      xdfm_batch_metrics_ws_bytes(B, which) bytes, 8-byte aligned, the caller's.  Every cell the finish reads is written
+ *           by the main grid first: the workspace may hold anything.  0 for a B or a `which` outside the supported range.
+ * The values are those of xdfm_amd/metrics.py's numpy functions on (y, double(p)):
+ *   auc       exact pair counting, no sort: C = sum over (i: y_i > 0.5, j: not) of 2 [p_i > p_j] + [p_i == p_j] in unsigned
+ *             64-bit integers -- per-workgroup partials, added by the finish -- and auc = (C * 0.5) / (double(n_pos) *
+ *             double(n_neg)): one IEEE division of exact operands, the bits of roc_auc_score (mid-ranks for ties).  A batch
+ *             of one class gives 0 / 0 = NaN; so does any NaN in p.
+ *   logloss   -(1 / B) sum (y log(pc) + (1 - y) log(1 - pc)), pc = clamp(double(p), 2^-52, 1 - 2^-52), in double, y as a
+ *             double factor (soft labels allowed)
+ *   mse       (1 / B) sum (double(y) - double(p))^2
+ *             both sums: a thread adds its 2 rows of a 512-row tile in index order, the workgroup's threads are added by a
+ *             fixed tree, the finish adds the tiles' partials by the same tree, then one division by B (the negation is
+ *             exact).  Against a float64 sum in another order: |got - ref| <= (B + 4) * 2^-52 * ref.
+ *   accuracy  #{(p > 0.5 ? 1 : 0) == y} / B: an integer count and one IEEE division, the bits of accuracy_score
+ * 1 <= B <= 65536 (8 ranks x 8192 rows gathered).  XDFM_ERR_INVALID, before any device call: a NULL operand, B outside the
+ * range, which == 0 or with bits above 15, a ws or out4 off 8-byte alignment. */
+enum { XDFM_METRIC_LOGLOSS = 1, XDFM_METRIC_AUC = 2, XDFM_METRIC_MSE = 4, XDFM_METRIC_ACC = 8 };
+size_t xdfm_batch_metrics_ws_bytes(int B, int which);
+int xdfm_batch_metrics(const float* y, const float* p, int B, int which, void* ws, double* out4, void* stream);
 
 #ifdef __cplusplus
 }

@@ -769,6 +769,15 @@ class BaseModel(nn.Module):
             self.metrics_names.append(name)
         return out
 
+    def _native_metric_slots(self, y_true, y_pred, max_rows):
+        """{History key: slot of xdfm_batch_metrics' out4} for the entries of `self.metrics` that K14 serves in this fit: the
+        switch ops.METRICS_NATIVE on, fp32 labels and predictions on a GPU, a global batch within the kernel's cap, and the
+        entry still the function `_get_metrics` wires in (a callable the user put there keeps the path it had)."""
+        if not (ops.METRICS_NATIVE and max_rows <= ops.METRICS_MAX_ROWS and ops.batch_metrics_supported(y_true, y_pred)):
+            return {}
+        table = {M.log_loss: 0, M.roc_auc_score: 1, M.mean_squared_error: 2, BaseModel._accuracy_score: 3}
+        return {name: table[fn] for name, fn in self.metrics.items() if fn in table}
+
     def _in_multi_worker_mode(self):
         return None
 
@@ -852,7 +861,7 @@ class BaseModel(nn.Module):
         self.stop_training = False
         print("Train on {0} samples, validate on {1} samples, {2} steps per epoch".format(
             sample_num, len(val_y), steps_per_epoch))
-        loss_log = metric_log = None
+        loss_log = metric_log = native_log = None
         for epoch in range(initial_epoch, epochs):
             cbs.on_epoch_begin(epoch)
             epoch_logs, train_result = {}, {}
@@ -860,6 +869,7 @@ class BaseModel(nn.Module):
             total_loss_epoch = 0.0
             step_no = 0
             logged = {}
+            native_logged = {}
             has_extra = False
             order = epoch_order(sample_num, shuffle)
             if order is not None:
@@ -905,7 +915,17 @@ class BaseModel(nn.Module):
                         yt, yp = yd, y_pred
                         if dp is not None:
                             yt, yp = dp.gather_rows(yd.reshape(-1)), dp.gather_rows(y_pred.detach().reshape(-1))
+                        # K14: every metric that is still the function `compile` put there, from ONE ops.batch_metrics call
+                        # (two launches) into a float64 log read once per epoch
+                        native = self._native_metric_slots(yt, yp, global_bs)
+                        if native:
+                            if native_log is None or native_log.device != yt.device:
+                                native_log = torch.empty((steps_per_epoch + 1, 4), dtype=torch.float64, device=yt.device)
+                            ops.batch_metrics(yt, yp, sum({1 << s for s in native.values()}), native_log[step_no - 1])
+                            native_logged.update(native)
                         for k, (name, fn) in enumerate(self.metrics.items()):
+                            if name in native:
+                                continue
                             dev_fn = M.DEVICE.get(fn) if yt.is_cuda else None
                             if dev_fn is None:
                                 train_result.setdefault(name, []).append(
@@ -961,7 +981,12 @@ class BaseModel(nn.Module):
                 if name == "auc" and any(v != v for v in vals):
                     raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
                 train_result[name] = vals
-            for name in self.metrics:                              # History keys in the order `compile` was given
+            for name, slot in native_logged.items():
+                vals = native_log[:step_no, slot].tolist()
+                if slot == 1 and any(v != v for v in vals):
+                    raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+                train_result[name] = vals
+            for name in self.metrics:                             # History keys in the order `compile` was given
                 if name in train_result:
                     epoch_logs[name] = np.sum(train_result[name]) / steps_per_epoch
             if do_validation:

@@ -2113,3 +2113,54 @@ def l2_regulariser(tensors, coeffs, cache: dict, embed_plan=None, n_defer=0):
     full, sub, rest = plans
     defer = (embed_plan, sub, rest) if n_defer else None
     return L2Reg.apply(full, defer, n_defer, *tensors)
+
+
+# --------------------------------------------------------------------------------------------- #
+# per-batch training metrics (K14, csrc/metrics.hip)                                             #
+# --------------------------------------------------------------------------------------------- #
+# XDFM_METRICS_NATIVE (default 1): `fit(verbose > 0)` takes the per-step logloss / AUC / mse / accuracy of a batch from
+# `batch_metrics` (two launches for all of them) instead of the float64 compositions of metrics.py (*_device) and, for the
+# accuracy, a host copy with its sync.  Read once, at import; a module attribute the tests and tools/metrics_probe.py flip.
+# The default follows profiles/metrics_probe.md.
+METRICS_NATIVE = _env_switch(os.environ, "XDFM_METRICS_NATIVE")
+METRIC_LOGLOSS, METRIC_AUC, METRIC_MSE, METRIC_ACC = 1, 2, 4, 8         # XDFM_METRIC_* of include/xdfm.h: slot k is bit 1 << k
+METRICS_MAX_ROWS = 65536
+_METRICS_WS = {}
+
+
+def batch_metrics_supported(y, p):
+    """Can `batch_metrics` take this (labels, predictions) pair?  fp32 device tensors of one numel within the kernel's cap."""
+    return bool(isinstance(y, torch.Tensor) and isinstance(p, torch.Tensor) and y.is_cuda and p.is_cuda and y.device == p.device
+                and y.dtype == torch.float32 and p.dtype == torch.float32 and y.numel() == p.numel()
+                and 1 <= y.numel() <= METRICS_MAX_ROWS)
+
+
+def batch_metrics(y, p, which, out):
+    """out[k] = metric k of (y, p) for every bit k of `which` (logloss | auc | mse | accuracy; xdfm_batch_metrics): two launches
+    on the current stream, nothing reaches the host.  y, p: fp32 device tensors of equal numel (any shape; at most 65536
+    elements); out: a float64 [4] view on the same device, whose other slots keep their values.  One workspace per device,
+    sized for the cap, is kept: calls on one stream follow each other, which is how `fit` uses it."""
+    _need_cuda(y, "y")
+    _need_cuda(p, "p")
+    if y.numel() != p.numel() or y.device != p.device:
+        raise ValueError("xdfm batch_metrics: y has %d elements on %s, p %d on %s" % (y.numel(), y.device, p.numel(), p.device))
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float64 and out.numel() == 4 and out.is_contiguous()
+            and out.device == y.device):
+        raise ValueError("xdfm batch_metrics: out must be a contiguous float64 [4] view on %s" % (y.device,))
+    lib = _lib.load()
+    y, p = y.detach().reshape(-1), p.detach().reshape(-1)
+    y = y if y.is_contiguous() else y.contiguous()
+    p = p if p.is_contiguous() else p.contiguous()
+    B = y.numel()
+    if lib.xdfm_batch_metrics_ws_bytes(B, int(which)) == 0:
+        raise ValueError("xdfm batch_metrics: B=%d, which=%d outside the supported range (1 <= B <= %d, 1 <= which <= 15)"
+                         % (B, int(which), METRICS_MAX_ROWS))
+    idx = y.device.index if y.device.index is not None else torch.cuda.current_device()
+    ws = _METRICS_WS.get(idx)
+    if ws is None:
+        ws = torch.empty(lib.xdfm_batch_metrics_ws_bytes(METRICS_MAX_ROWS, 15) // 8, dtype=torch.float64, device=y.device)
+        if not torch.cuda.is_current_stream_capturing():          # a tensor born inside a capture belongs to that graph's pool
+            _METRICS_WS[idx] = ws
+    _lib.check(_run("batch_metrics", 0.0, lambda: lib.xdfm_batch_metrics(_ptr(y), _ptr(p), B, int(which), _ptr(ws), _ptr(out), _stream())),
+               "batch_metrics")
+    return out
