@@ -35,7 +35,7 @@
  * ABI 7: xdfm_cin_bwd_x_is_folded (a pure query instead of the "last_sym" probe on the product path); the deferred update's
  * constant table holds 4 floats per step (xdfm_adam_clock.consts: 4 * cap) and its replayed steps run the short forms of
  * csrc/adam_math.h (same bits, about half the issue slots); xdfm_adam_selftest; xdfm_cin_bwd_prep +
- * xdfm_cin_level_bwd_w_prepared (dOut, its fp16 planes and the dW kernel's scales in one pass); xdfm_set_ticket_board;
+ * xdfm_cin_level_bwd_w_prepared (dOut, its fp16 planes and the dW kernel's scales in one pass);
  * xdfm_cin_attn_pool_bwd_det (K5's parameter gradients without float atomics); xdfm_cin_level_fwd_ex (direct-connect sums
  * and ReLU sign bits from the forward's epilogue; the direct-connect half of a level is never stored).
  * ABI 8 additions (no existing struct or signature changed): xdfm_opt_tensor, xdfm_opt_step_ws_elems, xdfm_sgd_step,
@@ -72,6 +72,8 @@
  * one-block "finish" launches of a train step collected into one launch) -- additions, the version stays 8.
  * XDFM_METRIC_*, xdfm_batch_metrics_ws_bytes, xdfm_batch_metrics (K14: the per-batch training metrics of fit() in two
  * launches) -- additions, the version stays 8.
+ * ABI 9: the export that registered a device array for last-block finishes inside the producer kernels (added with ABI 7, opt-in,
+ * measured slower) is removed; the finish batch saves those launches.  Nothing else changes.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -83,7 +85,7 @@
 extern "C" {
 #endif
 
-#define XDFM_ABI_VERSION 8
+#define XDFM_ABI_VERSION 9
 
 enum {
     XDFM_OK = 0,
@@ -154,13 +156,8 @@ int xdfm_device_count(void);                /* <0: HIP error code negated */
  * T * 512.  A test knob: at 1 a tensor is one workgroup, whose loops then run many times at small sizes. */
 int xdfm_set_option(const char* key, int value);
 int xdfm_get_option(const char* key);
-/* Ticket board: `board` = a DEVICE array of `slots` >= 1040 unsigned ints, zeroed once by the caller and kept alive, registered
- * for the CURRENT device (NULL unregisters).  With a board, every kernel of the library that leaves per-block partials lets
- * the block that finishes last add them up (in the same fixed order) instead of a one-block "finish" launch of its own:
- * ten launches fewer per train step, identical results.  The kernels reset the tickets they use; one calling thread and
- * one stream per device at a time (as for the rest of the library). */
-int xdfm_set_ticket_board(unsigned* board, int slots);
-/* Finish batch: the same saving without tickets.  Between xdfm_finish_batch_begin() and xdfm_finish_batch_run(stream), on
+/* Finish batch: the one-block "finish" launches of a train step in one launch.
+ * Between xdfm_finish_batch_begin() and xdfm_finish_batch_run(stream), on
  * the current device, every entry point that would launch a finish kernel of its own (the dbias of xdfm_cin_dout_det /
  * xdfm_cin_bwd_prep, the split sums of xdfm_dense_bwd_w / _drop / xdfm_dense_prelu_bwd_w with its slope, xdfm_colsum /
  * xdfm_relu_bwd_colsum, the loss of xdfm_head_fwd* and the parameter gradients of xdfm_head_bwd*, the L2 value of
@@ -174,12 +171,11 @@ int xdfm_set_ticket_board(unsigned* board, int slots);
  *     earlier job of the batch writes, and cannot ride behind it, first sends the recorded jobs off in a launch of their own.
  *   - Inside a batch the CIN dbias is STORED (0 + sum), not accumulated: it need not be zeroed (xdfm_finish_batch_active
  *     tells a caller whether that holds for the next call).
- *   - A registered ticket board takes precedence: kernels that take tickets finish themselves, nothing is recorded for them.
  *   - Errors (XDFM_ERR_INVALID): _begin while a batch is open; a job or _run on another stream than the batch's first job; a
  *     job, _begin or _run on another device than the open batch's.  _run without an open batch, or with no recorded job,
  *     launches nothing and returns XDFM_OK.  A failed _run leaves the batch open.  One batch at a time per process.
  *   - Option "finish_batch" (default 1): 0 = _begin opens nothing, every finish stays its own launch (A/B runs).
- * xdfm_finish_batch_active: 1 when jobs are being recorded on the current device (a batch is open, no ticket board), else 0.
+ * xdfm_finish_batch_active: 1 when jobs are being recorded on the current device (a batch is open), else 0.
  * xdfm_finish: ONE finish over partials the caller supplies -- exactly what the entry points above call after their main
  * kernel: recorded in the open batch, else launched.  For tests and tools.  kind / arguments (others 0 / NULL):
  *   0 CIN dbias    part [i0 = H][i1 = partials per row] -> out [H] (+= outside a batch)

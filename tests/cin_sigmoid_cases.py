@@ -2,25 +2,15 @@
 (+ xdfm_cin_level_bwd_w_prepared) with act = 2 (sigmoid), every call twice.
 
 make_case(name) builds the inputs on the CPU from a seed; run_cases(dev) runs every case and returns the outputs as numpy
-arrays.  As a program (python cin_sigmoid_cases.py OUT.npz, started by the test with XDFM_TICKETS=1 in a fresh process) it
-registers the ticket board first and writes the arrays to OUT.npz: the board is registered once per process and changes
-every later launch, so the ticketed half never runs inside the pytest process (as tests/ticket_child.py).
+arrays.
 
 ACT_CASES are the cases of tests/test_gpu_cin_f32_instances.py for act = 0 (linear) and 1 (ReLU), built by the same
 make_case: hidden rows that start at hid0 > 0, rows with neither gradient source, a non-zero dbias before the call, the call
-in place (dOut is A) and the atomic finish (ws = NULL) beside the workspace one.  `python cin_sigmoid_cases.py OUT.npz act`
-runs those instead of CASES."""
+in place (dOut is A) and the atomic finish (ws = NULL) beside the workspace one.  run_cases(dev, ACT_CASES) runs those
+instead of CASES."""
 import ctypes
-import os
-import sys
 
 import numpy as np
-
-if __name__ == "__main__":          # as a program: the paths conftest.py sets for the tests
-    _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for _p in (_ROOT, os.path.join(_ROOT, "xdeepfm-pytorch_amd")):
-        if _p not in sys.path:
-            sys.path.insert(0, _p)
 
 SIGMOID = 2
 LINEAR, RELU = 0, 1
@@ -151,29 +141,8 @@ def _run(c, dev):
 
 
 def run_cases(dev, cases=None):
-    import torch
-    from xdfm_amd import _lib
     out = {}
     for name in (CASES if cases is None else cases):
         out.update(_run(make_case(name), dev))
-        torch.cuda.synchronize()
-        if 0 in _lib._BOARDS:
-            out["board/" + name] = _lib._BOARDS[0].cpu().numpy().copy()
-    out["meta/board_registered"] = np.array(int(0 in _lib._BOARDS))
     return out
 
-
-def main(path, cases=None):
-    import torch
-    from xdfm_amd import _lib
-    assert os.environ.get("XDFM_TICKETS") == "1", "start this program with XDFM_TICKETS=1"
-    dev = torch.device("cuda:0")
-    _lib.ticket_board(dev)
-    assert 0 in _lib._BOARDS, "no ticket board was registered"
-    out = run_cases(dev, cases)
-    np.savez(path, **out)
-    print("cin_sigmoid_cases: %d arrays" % len(out))
-
-
-if __name__ == "__main__":
-    main(sys.argv[1], ACT_CASES if sys.argv[2:] == ["act"] else None)

@@ -1,9 +1,10 @@
 """GPU driver of the cases of head_ex_ref.py: one forward and backward of the output head through the C ABI
-(xdfm_head_fwd_ex / xdfm_head_bwd_ex, or the entry points without a mode) with every output inside guard cells.  Shared by
-test_gpu_head_ex.py and ticket_child_ex.py, so that the run with a ticket board and the run without one execute the very
-same calls."""
+(xdfm_head_fwd_ex / xdfm_head_bwd_ex, or the entry points without a mode) with every output inside guard cells.  Below it
+the fixed list of cases behind test_gpu_head_ex.py::test_head_ex_twice_in_a_row_bit_for_bit."""
+import numpy as np
 import torch
 
+import head_ex_ref as X
 import head_reg_drivers as D
 from head_reg_drivers import _p, _put, _stream
 
@@ -50,6 +51,23 @@ def run_head_ex(c, mode, dev, ex=True):
     if "dv" in out:
         out["dv"] = out["dv"].reshape(B, Kv)
     out["guards"] = all(D.guards_intact(v[0]) for v in bufs.values())
+    return out
+
+
+# the head's (identity, mse) and (sigmoid, mae) instantiations on a 17-row case and on one a row short of a grid stride
+REPEAT_MODES = [(X.LINK_IDENTITY, X.LOSS_MSE), (X.LINK_SIGMOID, X.LOSS_MAE)]
+REPEAT_CASES = ["c1111", "k4_k68_b2047"]
+
+
+def run_cases(dev):
+    """Every (mode, case) of the two lists twice in a row -> {"head/<mode>/<case>/<rep>/<output>": array}."""
+    out = {}
+    for mode in REPEAT_MODES:
+        for name in REPEAT_CASES:
+            c = X.make_ex_case(name, mode[0])
+            for rep in (0, 1):
+                for k, v in run_head_ex(c, mode, dev).items():
+                    out["head/%s/%s/%d/%s" % (X.mode_id(mode), name, rep, k)] = np.asarray(v)
     return out
 
 

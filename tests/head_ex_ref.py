@@ -2,7 +2,7 @@
 (identity link) and the mse / mae losses (csrc/reg.hip: head_link, head_term, head_g; C ABI xdfm_head_fwd_ex /
 xdfm_head_bwd_ex).  Built on head_reg_ref.py's helpers and error model: eps = 2^-24, gamma(n) = n eps / (1 - n eps) bounds
 the product of n factors (1 + delta), |delta| <= eps; "k rounded operations in a row are within k / 2 ulp", ulp the
-relative unit 2^-23.  Imported by test_head_ex_host.py (CPU), test_gpu_head_ex.py and ticket_child_ex.py.
+relative unit 2^-23.  Imported by test_head_ex_host.py (CPU), test_gpu_head_ex.py and head_ex_drivers.py.
 
 The kernels spell, with z the fp32 logit of head_reg_ref (dot products and adds in any order), t = y[b], gl = gloss[0]:
     p    = 1 / (1 + expf(-z))     (sigmoid link)          p = z     (identity link)

@@ -1,37 +1,17 @@
-"""The fixed list of cases behind test_gpu_head_reg.py::test_ticketed_finishes_match_two_launch_path_bit_for_bit.
+"""The fixed list of cases behind test_gpu_head_reg.py::test_finish_cases_repeat_bit_for_bit.
 
-run_cases(dev) runs every kernel family that has a ticketed finish (the Adam step over 70 tensors, the head, the column
-sums, a train step) twice in a row and returns all outputs as numpy
-arrays, plus the ticket board (when one is registered) read after every family.  As a program (python ticket_child.py
-OUT.npz, started by the test with XDFM_TICKETS=1 in a fresh process) it registers the board first and writes the arrays
-to OUT.npz; imported by the test, the same function runs on the two-launch path.  The board is registered once per
-process and changes every later launch, which is why the ticketed half never runs inside the pytest process."""
-import os
-import sys
-
+run_cases(dev) runs every kernel family of csrc/reg.hip and csrc/adam.hip that leaves per-block partials to a finish (the
+Adam step over 70 tensors, the head, the column sums) twice in a row, then six train steps of a small xDeepFM (eager, the
+capture, graph replays), and returns all outputs as numpy arrays."""
 import numpy as np
 
-if __name__ == "__main__":          # as a program: the paths conftest.py sets for the tests (its own directory is there already)
-    _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    for _p in (_ROOT, os.path.join(_ROOT, "xdeepfm-pytorch_amd")):
-        if _p not in sys.path:
-            sys.path.insert(0, _p)
-
-import adam_ref as A  # noqa: E402
-import head_reg_drivers as D  # noqa: E402
-import head_reg_ref as R  # noqa: E402
+import adam_ref as A
+import head_reg_drivers as D
+import head_reg_ref as R
 
 HEAD = ["c1111", "c0000", "k3_k4_b16", "k512_k200_b2048", "k516_k64_b2049", "k64_k4_b65536"]     # both kernels each way
-COLSUM = [(1000, 429), (4099, 63), (16, 65600)]                                                   # 65600: no ticket
+COLSUM = [(1000, 429), (4099, 63), (16, 65600)]
 TRAIN_STEPS = 6                # 2 eager steps, the capture, 3 replays
-
-
-def _board(out, tag):
-    import torch
-    from xdfm_amd import _lib
-    torch.cuda.synchronize()
-    if 0 in _lib._BOARDS:
-        out["board/" + tag] = _lib._BOARDS[0].cpu().numpy().copy()
 
 
 def _train(dev, out):
@@ -52,15 +32,14 @@ def _train(dev, out):
         out["train/step%d_pred" % s] = res[0].detach().cpu().numpy().copy()
         out["train/step%d_loss" % s] = res[1].detach().cpu().numpy().copy()
         out["train/step%d_total" % s] = res[2].detach().cpu().numpy().copy()
-        _board(out, "train_step%d" % s)
     for k, v in model.state_dict().items():
         out["train/final_" + k] = v.detach().cpu().numpy().copy()
     return model.__dict__["_graphed_step"].replays
 
 
 def _adam70(dev, out):
-    """The 70-tensor Adam step of test_gpu_adam.py (two launches; the L2 partials of both are summed by the last launch's
-    ticket or by the finish launch), with l2_value, twice in a row."""
+    """The 70-tensor Adam step of test_gpu_adam.py (two launches; the finish sums the L2 partials of both), with l2_value,
+    twice in a row."""
     state = A.make_state_70()
     for rep in (0, 1):
         snap, values = A.run_70(dev, True, state=state)
@@ -69,11 +48,9 @@ def _adam70(dev, out):
         small = [t for t, n in enumerate(A.SIZES_70) if n <= 40989]
         for k, name in enumerate("pmv"):
             out["adam70/%d/%s" % (rep, name)] = np.concatenate([snap[t][k] for t in small])
-    _board(out, "adam70")
 
 
 def run_cases(dev):
-    from xdfm_amd import _lib
     out = {}
     _adam70(dev, out)
     for name in HEAD:
@@ -84,7 +61,6 @@ def run_cases(dev):
         if c["lin"] is None:                                  # the backward of a case ops.Head cannot differentiate
             g, db = D.head_g_aux(out["head/%s/1/pred" % name], c["y"], c["gloss"], dev)
             out["head/%s/aux_g" % name], out["head/%s/aux_dbias" % name] = g, np.array(db)
-        _board(out, "head_" + name)
     for rows, cols in COLSUM:
         for relu in (False, True):
             g, y = R.make_colsum_case(rows, cols, relu)
@@ -94,25 +70,6 @@ def run_cases(dev):
                 out[tag + "/guards"] = np.array(int(r["guards"]))
                 if relu:
                     out[tag + "/gz"] = r["gz"]
-            _board(out, "colsum%s_%dx%d" % ("_relu" if relu else "", rows, cols))
     out["meta/replays"] = np.array(_train(dev, out))
-    _board(out, "end")
-    out["meta/board_registered"] = np.array(int(0 in _lib._BOARDS))
     return out
 
-
-def main(path):
-    import torch
-    from xdfm_amd import _lib
-    assert os.environ.get("XDFM_TICKETS") == "1", "start this program with XDFM_TICKETS=1"
-    dev = torch.device("cuda:0")
-    _lib.ticket_board(dev)                 # before the first launch: the head op does not pass through ops._need_cuda
-    assert 0 in _lib._BOARDS, "no ticket board was registered"
-    out = run_cases(dev)
-    np.savez(path, **out)
-    print("ticket_child: %d arrays, %d board readings, %d graph replays" % (
-        len(out), sum(k.startswith("board/") for k in out), int(out["meta/replays"])))
-
-
-if __name__ == "__main__":
-    main(sys.argv[1])

@@ -1,6 +1,5 @@
 """GPU drivers of the cases of head_reg_ref.py: run a case through ops / the C ABI and hand back numpy arrays.  Shared by
-test_gpu_head_reg.py and ticket_child.py, so that the run with a ticket board and the run without one execute the very
-same calls."""
+test_gpu_head_reg.py and head_reg_cases.py."""
 import ctypes
 
 import numpy as np

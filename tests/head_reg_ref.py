@@ -1,6 +1,6 @@
 """float64 references, error bounds and the shared case lists of the output head, the bias-gradient column sums and the
 L2 regulariser (csrc/reg.hip).  Imported by test_head_reg_reference.py (CPU), test_gpu_head_reg.py and, through
-head_reg_drivers.py (the GPU drivers of the same cases), ticket_child.py.
+head_reg_drivers.py (the GPU drivers of the same cases), head_reg_cases.py.
 
 Everything here is plain numpy on the CPU; the operands are float32 arrays (what the kernels read), widened to float64
 before any arithmetic.
@@ -219,7 +219,6 @@ def colsum_ref(g, y=None):
 #                rows   cols
 COLSUM_SHAPES = [(1, 1), (15, 63), (16, 64), (63, 65), (64, 429), (65, 1000), (1000, 429), (4099, 63), (4099, 1000),
                  (262144, 1), (262144, 64), (262144, 1000), (16, 65600)]
-COLSUM_TK_ROWS = 1024        # TK_ROWS of csrc/xdfm_internal.h: more column blocks than this -> no ticket, two launches
 
 
 def colsum_pitches(cols):

@@ -1,10 +1,12 @@
 """GPU driver of the cases of head_w_ref.py: one forward and backward of the output head through xdfm_head_fwd_w /
 xdfm_head_bwd_w (or the _ex entry points) with every output inside guard cells and both workspaces filled with NaN.
-Shared by test_gpu_head_w_abi.py and ticket_child_w.py, so that the run with a ticket board and the run without one
-execute the very same calls."""
+Below it the fixed list of cases behind test_gpu_head_w_abi.py::test_head_w_twice_in_a_row_bit_for_bit."""
+import numpy as np
 import torch
 
+import head_ex_ref as X
 import head_reg_drivers as D
+import head_w_ref as W
 from head_reg_drivers import _p, _put, _stream
 
 OUTPUTS = ("pred", "loss", "dlin", "du", "dv", "grads")
@@ -51,4 +53,22 @@ def run_head_w(c, mode, dev, w=None, entry="w"):
     if "dv" in out:
         out["dv"] = out["dv"].reshape(B, Kv)
     out["guards"] = all(D.guards_intact(v[0]) for v in bufs.values())
+    return out
+
+
+# the weighted head's (sigmoid, bce), (identity, mse) and (sigmoid, mae) instantiations on a vectorised and on a scalar case
+# that run more than one sweep
+REPEAT_MODES = [(X.LINK_SIGMOID, X.LOSS_BCE), (X.LINK_IDENTITY, X.LOSS_MSE), (X.LINK_SIGMOID, X.LOSS_MAE)]
+REPEAT_CASES = [(2049, 8, 32, True), (513, 7, 0, False)]
+
+
+def run_cases(dev):
+    """Every (mode, case) of the two lists twice in a row -> {"head/<mode>/<case>/<rep>/<output>": array}."""
+    out = {}
+    for mode in REPEAT_MODES:
+        for case in REPEAT_CASES:
+            c, w = W.make_w_case(case, mode[0])
+            for rep in (0, 1):
+                for k, v in run_head_w(c, mode, dev, w).items():
+                    out["head/%s/%s/%d/%s" % (W.mode_id(mode), W.w_case_id(case), rep, k)] = np.asarray(v)
     return out

@@ -2,7 +2,7 @@
 head_fwd_kernel / head_bwd_kernel / head_bwd_vec_kernel; C ABI xdfm_head_fwd_w / xdfm_head_bwd_w).  Built on
 head_reg_ref.py (error model: eps = 2^-24, gamma(n) = n eps / (1 - n eps), "k rounded operations in a row are within k / 2
 ulp", ulp the relative unit 2^-23) and head_ex_ref.py (the mse / mae pairs).  Imported by test_head_w_host.py (CPU),
-test_gpu_head_w_abi.py, ticket_child_w.py and test_gpu_sample_weight.py.
+test_gpu_head_w_abi.py, head_w_drivers.py and test_gpu_sample_weight.py.
 
 The weighted kernels differ from the unweighted ones in two products, each rounded on its own (never fused into the add
 or fma that consumes it):

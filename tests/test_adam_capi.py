@@ -32,7 +32,7 @@ def test_adam_symbols_are_declared_bound_and_exported():
     exported = {n for n in _lib.SIGNATURES if n.startswith("xdfm_adam_")}
     declared = set(re.findall(r"\b(xdfm_adam_\w+)\s*\(", header))
     assert exported == declared == set(ADAM)
-    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8          # no signature changed
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 9          # no signature changed
 
 
 def test_adam_structs_match_the_header():

@@ -29,7 +29,7 @@ def test_symbols_in_header_binding_and_library():
         assert re.search(r"\b%s\s*\(" % n, src), "include/xdfm.h does not declare %s" % n
         assert n in mod.SIGNATURES, "xdfm_amd/_lib.py does not bind %s" % n
         assert hasattr(lib, n), "libxdfm_hip.so lacks %s" % n
-    assert lib.xdfm_abi_version() == 8           # additive change
+    assert lib.xdfm_abi_version() == 9           # additive change
 
 
 def test_supported_envelope_edges():

@@ -26,7 +26,7 @@ def test_symbols_in_header_binding_and_library():
         assert re.search(r"\b%s\s*\(" % n, src), "include/xdfm.h does not declare %s" % n
         assert n in mod.SIGNATURES, "xdfm_amd/_lib.py does not bind %s" % n
         assert hasattr(lib, n), "libxdfm_hip.so lacks %s" % n
-    assert lib.xdfm_abi_version() == mod.ABI_VERSION == 8           # additions only
+    assert lib.xdfm_abi_version() == mod.ABI_VERSION == 9           # additions only
 
 
 def test_validation_before_device_work():

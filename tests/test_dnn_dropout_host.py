@@ -124,7 +124,7 @@ def test_symbols_in_header_binding_and_library():
         assert re.search(r"\b%s\s*\(" % n, src), "include/xdfm.h does not declare %s" % n
         assert n in mod.SIGNATURES, "xdfm_amd/_lib.py does not bind %s" % n
         assert hasattr(lib, n), "libxdfm_hip.so lacks %s" % n
-    assert lib.xdfm_abi_version() == mod.ABI_VERSION == 8           # additions only
+    assert lib.xdfm_abi_version() == mod.ABI_VERSION == 9           # additions only
     text = open(HEADER).read()
     for word in ("0x7feb352d", "0x846ca68b", "0x9E3779B1", "0x85EBCA77", "in distribution only", "1.0f / (1.0f - p_drop)"):
         assert word in text, "include/xdfm.h does not document %r" % word

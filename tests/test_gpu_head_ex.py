@@ -5,8 +5,7 @@ losses (csrc/reg.hip; xdfm_head_fwd_ex / xdfm_head_bwd_ex; ops.Head(link, loss);
       head_ex_ref.EX_CASES (both kernel families, both B = 1 cases, a ragged stride, the LDS limit, 32 strides, the
       misaligned fall-back; c0010 with exact zeros of pred - y), guard cells around every output;
   (b) the _ex entry points with (0, 0) against the entry points without a mode, bit for bit;
-  (c) the ticketed finish against the two-launch finish, bit for bit, for (identity, mse) and (sigmoid, mae), the board
-      in a child process (tests/ticket_child_ex.py);
+  (c) (identity, mse) and (sigmoid, mae) twice in a row, bit for bit (head_ex_drivers.run_cases);
   (d) the goldens of tests/golden/regression/ (the reference run with task="regression" / "mse" / "mae"), through
       model._loss_forward and through the stock tail, in both cin_math modes, at the bars of
       test_gpu_parity.py::test_model_vs_reference_golden;
@@ -18,8 +17,6 @@ fraction of each bar it used before it asserts."""
 import faulthandler
 import gc
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -34,7 +31,6 @@ pytestmark = pytest.mark.gpu
 T = torch.from_numpy
 
 STEP_LIMIT_S = 300          # a hang ends the process instead of blocking the run
-CHILD_LIMIT_S = 120
 
 
 @pytest.fixture(autouse=True)
@@ -137,41 +133,20 @@ def test_head_ex_with_sigmoid_bce_equals_the_entry_points_without_a_mode(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# (c) ticketed finishes
+# (c) twice in a row
 # ---------------------------------------------------------------------------------------------------------------------
-def test_ticketed_finish_matches_two_launch_finish_bit_for_bit(tmp_path):
-    """XDFM_TICKETS=1: the last block of head_fwd_kernel / head_bwd_kernel does the finish launch's work.  One fresh child
-    process (tests/ticket_child_ex.py) runs (identity, mse) and (sigmoid, mae) on c1111 and k4_k68_b2047 with a board
-    registered, every case twice; this process, which never registers one, runs the same calls: the same bits, intact
-    guards, and a board that reads all zero after every case."""
-    dev = _dev()
-    from xdfm_amd import _lib
-    import ticket_child_ex
-    assert os.environ.get("XDFM_TICKETS", "0") != "1" and not _lib._BOARDS, "this process must run without a ticket board"
-    out = str(tmp_path / "ticketed_ex.npz")
-    r = subprocess.run([sys.executable, os.path.abspath(ticket_child_ex.__file__), out], env={**os.environ, "XDFM_TICKETS": "1"},
-                       timeout=CHILD_LIMIT_S, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, "the ticketed child ended with status %d" % r.returncode
-    with np.load(out, allow_pickle=False) as z:
-        ticketed = {k: z[k] for k in z.files}
-    plain = ticket_child_ex.run_cases(dev)
-    assert not _lib._BOARDS
-    assert int(ticketed["meta/board_registered"]) == 1 and int(plain["meta/board_registered"]) == 0
-    boards = [k for k in ticketed if k.startswith("board/")]
-    assert len(boards) == 4 and not [k for k in plain if k.startswith("board/")]
-    for k in boards:
-        assert ticketed[k].size == 2048 and not ticketed[k].any(), "%s: tickets %s left non-zero" % (k, np.nonzero(ticketed[k])[0][:8])
-    keys = sorted(k for k in ticketed if k.startswith("head/"))
-    assert keys == sorted(k for k in plain if k.startswith("head/")) and len(keys) == 4 * 2 * 7
-    assert all(bool(ticketed[k]) and bool(plain[k]) for k in keys if k.endswith("/guards"))
-    diff = [k for k in keys if not _same_bits(ticketed[k], np.asarray(plain[k]))]
-    assert not diff, "ticketed and two-launch results differ in %s" % diff[:12]
+def test_head_ex_twice_in_a_row_bit_for_bit():
+    """head_ex_drivers.run_cases: (identity, mse) and (sigmoid, mae) on c1111 and k4_k68_b2047, every case twice in a row:
+    the same bits both times, intact guards, a finite non-zero loss and gradient."""
+    out = DX.run_cases(_dev())
+    keys = sorted(out)
+    assert len(keys) == 4 * 2 * 7
+    assert all(bool(out[k]) for k in keys if k.endswith("/guards"))
     for k in keys:
         if "/0/" in k:
-            assert _same_bits(ticketed[k], ticketed[k.replace("/0/", "/1/")]), k
+            assert _same_bits(out[k], out[k.replace("/0/", "/1/")]), k
         if k.endswith(("/loss", "/grads")):
-            assert np.isfinite(ticketed[k]).all() and np.abs(ticketed[k]).max() > 0, k
+            assert np.isfinite(out[k]).all() and np.abs(out[k]).max() > 0, k
 
 
 # ---------------------------------------------------------------------------------------------------------------------

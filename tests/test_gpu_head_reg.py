@@ -1,6 +1,6 @@
 """GPU tests (-m gpu) of the kernels of csrc/reg.hip -- the fused output head, the bias-gradient column sums and the
-multi-tensor L2 regulariser -- against the float64 references of tests/head_reg_ref.py, and of the ticketed finishes
-(XDFM_TICKETS=1) against the two-launch path, bit for bit.  The bars are derived in head_reg_ref.py's docstring; none
+multi-tensor L2 regulariser -- against the float64 references of tests/head_reg_ref.py, and of the families that leave
+partials to a finish twice in a row, bit for bit.  The bars are derived in head_reg_ref.py's docstring; none
 was fitted to what the kernels give.  Every test prints the fraction of each bar it used before it asserts.
 
 Head cases (head_reg_ref.HEAD_CASES; fwd / bwd kernel: V = float4 kernels head_fwd_kernel<true> + head_bwd_vec_kernel,
@@ -29,7 +29,7 @@ gloss cycles through 0.37, 1.0, -2.5, 1.75 by position in the list.  Every case 
 
 Column sums: head_reg_ref.COLSUM_SHAPES through the C ABI, on a column window of a wider matrix (plain: ld = cols + 5,
 window from column 2; ReLU: ldg = cols + 3 from column 2, ldy = cols + 8 from column 3); 65600 columns are 1025 column
-blocks, more than the ticket rows.  The ReLU variant leaves out 262144 x 1000 (three 1 GB operands).
+blocks.  The ReLU variant leaves out 262144 x 1000 (three 1 GB operands).
 L2: head_reg_ref.L2_CASES through ops.L2Reg, accumulate = 1 through the C ABI.  t1 and t2_big hold a 2^22 + 3 element
 tensor whose address and gradient slot are 16-byte aligned: 128 strides of l2_sumsq_kernel's float4 loop, 32 of
 l2_grad_kernel's, and a 3-element scalar tail; t2_big's second tensor (2^21 + 1 elements) and its gradient slot are
@@ -37,9 +37,6 @@ misaligned: the scalar loops over 256 / 64 strides.  The value is held to gamma(
 the kernels' own walk (head_reg_ref.l2_value_ref), the gradient to its bits.
 """
 import faulthandler
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -51,7 +48,6 @@ import head_reg_ref as R
 pytestmark = pytest.mark.gpu
 
 STEP_LIMIT_S = 300          # a hang ends the process instead of blocking the run
-CHILD_LIMIT_S = 240         # the ticket test: its child, then the same list in this process under a step limit of its own
 
 
 @pytest.fixture(autouse=True)
@@ -162,7 +158,6 @@ def test_relu_bwd_colsum_against_float64(rows, cols):
 def test_colsum_shapes_cover_the_sweep():
     assert {s[0] for s in R.COLSUM_SHAPES} == {1, 15, 16, 63, 64, 65, 1000, 4099, 262144}
     assert {s[1] for s in R.COLSUM_SHAPES} == {1, 63, 64, 65, 429, 1000, 65600}
-    assert -(-65600 // 64) > R.COLSUM_TK_ROWS
     for cols in {s[1] for s in R.COLSUM_SHAPES}:
         ld, ldg, ldy = R.colsum_pitches(cols)
         assert ld >= D.COL0_G + cols and ldg >= D.COL0_G + cols and ldy >= D.COL0_Y + cols and ldg != ldy
@@ -211,46 +206,35 @@ def test_l2_accumulate_against_float64(name):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# ticketed finishes
+# the families with a finish, twice in a row
 # ---------------------------------------------------------------------------------------------------------------------
-def test_ticketed_finishes_match_two_launch_path_bit_for_bit(tmp_path):
-    """XDFM_TICKETS=1 (xdfm_amd/_lib.py: ticket_board): the last block of a producer does the finish launch's work.  One
-    fresh child process (tests/ticket_child.py) runs a fixed list of cases with a board registered -- head forward and
-    backward on both kernels, both column sums (with the 65600-column shape that has no ticket), and a small xDeepFM
-    train step with both L2 terms, eager and graph-replayed (the CIN dOut / bias ticket rows and the Adam L2 sum) --
-    every family twice in a row, and stores every output and the board after every family.  This process, where the
-    variable is never set and no board is ever registered, runs the same list: every array must have the same bits, and
-    the board must read all zero every time it was looked at (a ticket left non-zero would corrupt the family's next
-    launch without a sound)."""
+def test_finish_cases_repeat_bit_for_bit():
+    """tests/head_reg_cases.py runs a fixed list of cases -- the 70-tensor Adam step with its L2 value, head forward and
+    backward on both kernels, both column sums (the 65600-column shape among them) -- every family twice in a row, then a
+    small xDeepFM train step with both L2 terms, eager and graph-replayed.  The second run in a row must give the first
+    one's bits (partials or a cell left behind by the first would not), no guard cell may be written, and the train steps
+    must have been replayed from the graph with finite results."""
     dev = _dev()
-    from xdfm_amd import _lib
-    import ticket_child
-    faulthandler.dump_traceback_later(CHILD_LIMIT_S + STEP_LIMIT_S, exit=True)      # replaces the fixture's: child + own run
-    assert os.environ.get("XDFM_TICKETS", "0") != "1" and not _lib._BOARDS, "this process must run without a ticket board"
-    out = str(tmp_path / "ticketed.npz")
-    env = {**os.environ, "XDFM_TICKETS": "1"}
-    r = subprocess.run([sys.executable, os.path.abspath(ticket_child.__file__), out], env=env, timeout=CHILD_LIMIT_S,
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, "the ticketed child ended with status %d" % r.returncode
-    with np.load(out, allow_pickle=False) as z:
-        ticketed = {k: z[k] for k in z.files}
-    plain = ticket_child.run_cases(dev)
-    assert not _lib._BOARDS
-    assert int(ticketed["meta/board_registered"]) == 1 and int(plain["meta/board_registered"]) == 0
-    assert int(ticketed["meta/replays"]) >= 3 and int(plain["meta/replays"]) >= 3
-    boards = [k for k in ticketed if k.startswith("board/")]
-    assert len(boards) >= 5 and "board/adam70" in boards
-    for k in boards:
-        assert ticketed[k].size == 2048 and not ticketed[k].any(), "%s: tickets %s left non-zero" % (k, np.nonzero(ticketed[k])[0][:8])
-    keys = sorted(k for k in ticketed if not k.startswith(("board/", "meta/")))
-    assert keys == sorted(k for k in plain if not k.startswith(("board/", "meta/"))) and len(keys) > 40
+    import head_reg_cases
+    out = head_reg_cases.run_cases(dev)
+    assert int(out["meta/replays"]) >= 3
+    keys = sorted(k for k in out if not k.startswith("meta/"))
+    assert len(keys) > 40
     adam = [k for k in keys if k.startswith("adam70/")]
-    assert len(adam) == 10 and all(np.isfinite(ticketed[k]).all() for k in adam)       # 2 runs x (2 L2 values + p, m, v)
-    for k in adam:
-        if k.startswith("adam70/0/"):          # the second run in a row gives the first one's bits (a ticket left behind would not)
-            assert ticketed[k].tobytes() == ticketed[k.replace("adam70/0/", "adam70/1/")].tobytes(), k
-            assert float(np.abs(ticketed[k]).max()) > 0
-    diff = [k for k in keys if not (ticketed[k].dtype == plain[k].dtype and ticketed[k].shape == plain[k].shape
-                                    and ticketed[k].tobytes() == plain[k].tobytes())]
-    assert not diff, "ticketed and two-launch results differ in %s" % diff[:12]
+    assert len(adam) == 10 and all(np.isfinite(out[k]).all() for k in adam)       # 2 runs x (2 L2 values + p, m, v)
+    assert all(float(np.abs(out[k]).max()) > 0 for k in adam)
+    first = [k for k in keys if "/0/" in k]
+    for fam, n in (("adam70/", 5), ("head/", len(head_reg_cases.HEAD)), ("colsum/", len(head_reg_cases.COLSUM)),
+                   ("colsum_relu/", len(head_reg_cases.COLSUM))):
+        assert sum(k.startswith(fam) for k in first) >= n, fam
+    diff = []
+    for k in first:
+        a, b = out[k], out[k.replace("/0/", "/1/")]
+        if not (a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()):
+            diff.append(k)
+    assert not diff, "the second run in a row differs from the first in %s" % diff[:12]
+    guards = [k for k in keys if k.endswith("/guards")]
+    assert len(guards) == 4 * len(head_reg_cases.COLSUM) and all(int(out[k]) == 1 for k in guards)
+    steps = [k for k in keys if k.startswith("train/step")]
+    assert len(steps) == 3 * head_reg_cases.TRAIN_STEPS and head_reg_cases.TRAIN_STEPS == 6
+    assert all(np.isfinite(out[k]).all() for k in keys if k.startswith("train/"))

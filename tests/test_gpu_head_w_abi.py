@@ -8,11 +8,8 @@ ones 512) x (Ku, Kv) in {(8, 32) vectorised, (7, 0) and (0, 516) scalar} x lin /
   (c) w = NULL and w = ones are xdfm_head_fwd_ex / xdfm_head_bwd_ex bit for bit;
   (d) guard cells around every output and workspace stay untouched and a NaN-filled workspace does no harm (every call of
       this file runs that way, head_w_drivers.run_head_w);
-  (e) XDFM_TICKETS=1 in a fresh child process (tests/ticket_child_w.py): the ticketed finish has the bits of the two-launch one."""
+  (e) three pairs twice in a row, bit for bit (head_w_drivers.run_cases)."""
 import faulthandler
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -26,7 +23,6 @@ import head_w_ref as W
 pytestmark = pytest.mark.gpu
 
 STEP_LIMIT_S = 300          # a hang ends the process instead of blocking the run
-CHILD_LIMIT_S = 120
 EXACT_MODES = [(X.LINK_IDENTITY, X.LOSS_MSE), (X.LINK_IDENTITY, X.LOSS_MAE)]
 
 
@@ -161,39 +157,17 @@ def test_null_weights_and_unit_weights_are_the_ex_call_bit_for_bit(mode, case):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# (e) ticketed finish
+# (e) twice in a row
 # ---------------------------------------------------------------------------------------------------------------------
-def test_ticketed_finish_matches_two_launch_finish_bit_for_bit(tmp_path):
-    """XDFM_TICKETS=1: the last block of the weighted head kernels does the finish launch's work.  One fresh child process
-    (tests/ticket_child_w.py) runs three pairs on a vectorised and a scalar case with a board registered, every case
-    twice; this process, which never registers one, runs the same calls: the same bits, intact guards, and a board that
-    reads all zero after every case."""
-    dev = _dev()
-    from xdfm_amd import _lib
-    import ticket_child_w
-    assert os.environ.get("XDFM_TICKETS", "0") != "1" and not _lib._BOARDS, "this process must run without a ticket board"
-    out = str(tmp_path / "ticketed_w.npz")
-    r = subprocess.run([sys.executable, os.path.abspath(ticket_child_w.__file__), out], env={**os.environ, "XDFM_TICKETS": "1"},
-                       timeout=CHILD_LIMIT_S, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    print(r.stdout[-3000:])
-    assert r.returncode == 0, "the ticketed child ended with status %d" % r.returncode
-    with np.load(out, allow_pickle=False) as z:
-        ticketed = {k: z[k] for k in z.files}
-    plain = ticket_child_w.run_cases(dev)
-    assert not _lib._BOARDS
-    assert int(ticketed["meta/board_registered"]) == 1 and int(plain["meta/board_registered"]) == 0
-    n = len(ticket_child_w.MODES) * len(ticket_child_w.CASES)
-    boards = [k for k in ticketed if k.startswith("board/")]
-    assert len(boards) == n and not [k for k in plain if k.startswith("board/")]
-    for k in boards:
-        assert not ticketed[k].any(), "%s: tickets %s left non-zero" % (k, np.nonzero(ticketed[k])[0][:8])
-    keys = sorted(k for k in ticketed if k.startswith("head/"))
-    assert keys == sorted(k for k in plain if k.startswith("head/")) and len(keys) >= n * 2 * 6
-    assert all(bool(ticketed[k]) and bool(plain[k]) for k in keys if k.endswith("/guards"))
-    diff = [k for k in keys if not _same_bits(ticketed[k], np.asarray(plain[k]))]
-    assert not diff, "ticketed and two-launch results differ in %s" % diff[:12]
+def test_head_w_twice_in_a_row_bit_for_bit():
+    """head_w_drivers.run_cases: three pairs on a vectorised and a scalar case, every case twice in a row: the same bits
+    both times, intact guards, a finite non-zero loss and gradient."""
+    out = DW.run_cases(_dev())
+    keys = sorted(out)
+    assert len(keys) >= len(DW.REPEAT_MODES) * len(DW.REPEAT_CASES) * 2 * 6
+    assert all(bool(out[k]) for k in keys if k.endswith("/guards"))
     for k in keys:
         if "/0/" in k:
-            assert _same_bits(ticketed[k], ticketed[k.replace("/0/", "/1/")]), k
+            assert _same_bits(out[k], out[k.replace("/0/", "/1/")]), k
         if k.endswith(("/loss", "/grads")):
-            assert np.isfinite(ticketed[k]).all() and np.abs(ticketed[k]).max() > 0, k
+            assert np.isfinite(out[k]).all() and np.abs(out[k]).max() > 0, k

@@ -89,7 +89,7 @@ def test_ex_symbols_and_signatures_match_the_header():
     src = open(HEADER).read()
     assert re.search(r"enum\s*\{\s*XDFM_LINK_SIGMOID\s*=\s*0\s*,\s*XDFM_LINK_IDENTITY\s*=\s*1\s*\}", src)
     assert re.search(r"enum\s*\{\s*XDFM_LOSS_BCE\s*=\s*0\s*,\s*XDFM_LOSS_MSE\s*=\s*1\s*,\s*XDFM_LOSS_MAE\s*=\s*2\s*\}", src)
-    assert re.search(r"#define\s+XDFM_ABI_VERSION\s+8\b", src) and lib.xdfm_abi_version() == 8
+    assert re.search(r"#define\s+XDFM_ABI_VERSION\s+%d\b" % _lib.ABI_VERSION, src) and lib.xdfm_abi_version() == _lib.ABI_VERSION
     ctype = lambda a: ctypes.c_void_p if "*" in a else {"int": ctypes.c_int}[a.split()[0]]
     for name in ("xdfm_head_fwd", "xdfm_head_bwd"):
         assert hasattr(lib, name + "_ex")

@@ -27,7 +27,7 @@ def _header_args(name):
 def test_w_symbols_and_signatures_match_the_header():
     from xdfm_amd import _lib
     lib = _lib.load()
-    assert re.search(r"#define\s+XDFM_ABI_VERSION\s+8\b", open(HEADER).read()) and lib.xdfm_abi_version() == 8
+    assert re.search(r"#define\s+XDFM_ABI_VERSION\s+%d\b" % _lib.ABI_VERSION, open(HEADER).read()) and lib.xdfm_abi_version() == _lib.ABI_VERSION
     ctype = lambda a: ctypes.c_void_p if "*" in a else {"int": ctypes.c_int}[a.split()[0]]
     strip = lambda a: a.rsplit(" ", 1)[0] if "*" not in a else a.rsplit("*", 1)[0] + "*"      # the type without the name
     for name in ("xdfm_head_fwd", "xdfm_head_bwd"):

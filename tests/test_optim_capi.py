@@ -20,7 +20,7 @@ def test_new_symbols_are_declared_bound_and_exported():
         assert re.search(r"\b%s\s*\(" % name, header), "include/xdfm.h lacks %s" % name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert "xdfm_opt_tensor" in header
-    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8          # additions only
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 9          # additions only
     # the descriptor as the header lays it out: three pointers, a long, a float (padded), a pointer
     assert ctypes.sizeof(_lib.OptTensor) == 48
     assert [f[0] for f in _lib.OptTensor._fields_] == ["param", "grad", "state", "numel", "l2", "grad_marks"]
@@ -43,7 +43,7 @@ def test_option_opt_bx_round_trips_and_adds_no_symbol():
         _lib.set_option("opt_bx", 0)
     assert _lib.get_option("adam_bx") == 0 and _lib.get_option("no_such_option") == -1
     # an option is no ABI change: the version and the entry points of this family are what they were
-    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 9
     assert sorted(k for k in _lib.SIGNATURES if k.startswith(("xdfm_opt_", "xdfm_sgd_", "xdfm_adagrad_", "xdfm_rmsprop_"))) == [
         "xdfm_adagrad_step", "xdfm_adagrad_step_deferred", "xdfm_opt_catchup_rows", "xdfm_opt_flush", "xdfm_opt_step_ws_elems",
         "xdfm_rmsprop_catchup_rows", "xdfm_rmsprop_flush", "xdfm_rmsprop_step", "xdfm_rmsprop_step_deferred", "xdfm_sgd_step",

@@ -21,7 +21,7 @@ def test_new_symbols_are_declared_bound_and_exported():
         assert re.search(r"\b%s\s*\(" % name, header), "include/xdfm.h lacks %s" % name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert "xdfm_opt_clock" in header and "xdfm_opt_rows" in header
-    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8          # additions only
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 9          # additions only
     assert ctypes.sizeof(_lib.OptTensor) == 48                      # `last` travels in a parallel array
     assert [f[0] for f in _lib.OptTensor._fields_] == ["param", "grad", "state", "numel", "l2", "grad_marks"]
     assert [f[0] for f in _lib.OptClock._fields_] == ["clock", "rates", "cap", "backlog", "cell"]

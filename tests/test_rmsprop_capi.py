@@ -23,7 +23,7 @@ def test_new_symbols_are_declared_bound_and_exported():
     for name in NEW:
         assert re.search(r"\b%s\s*\(" % name, header), "include/xdfm.h lacks %s" % name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
-    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8          # additions only
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 9          # additions only
     assert ctypes.sizeof(_lib.OptTensor) == 48
     assert [f[0] for f in _lib.OptTensor._fields_] == ["param", "grad", "state", "numel", "l2", "grad_marks"]
     # the existing signatures did not change

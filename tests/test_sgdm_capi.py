@@ -27,7 +27,7 @@ def test_new_symbols_are_declared_bound_and_exported():
         assert re.search(r"\b%s\s*\(" % name, header), "include/xdfm.h lacks %s" % name
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert "xdfm_sgdm_step, xdfm_sgdm_step_deferred, xdfm_sgdm_catchup_rows, xdfm_sgdm_flush" in text      # the ABI note
-    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 8          # additions only
+    assert lib.xdfm_abi_version() == _lib.ABI_VERSION == 9          # additions only
     assert ctypes.sizeof(_lib.OptTensor) == 48
     # the existing signatures did not change
     assert len(_lib.SIGNATURES["xdfm_sgd_step"][1]) == 7 and len(_lib.SIGNATURES["xdfm_rmsprop_step"][1]) == 9

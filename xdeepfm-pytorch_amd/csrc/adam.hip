@@ -50,8 +50,7 @@ static_assert(sizeof(AdamBatch) + 128 <= 8192, "the Adam kernels' argument block
 template <bool NT>
 __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
     const AdamBatch batch, int cnt, int slot0, double lr_arg, const double* __restrict__ lr_dev, double beta1, double beta2, double eps,
-    float* __restrict__ l2_part, const int* __restrict__ clock, const float* __restrict__ consts, float* __restrict__ l2_out,
-    int l2_total, unsigned* __restrict__ ticket) {
+    float* __restrict__ l2_part, const int* __restrict__ clock, const float* __restrict__ consts) {
     // the learning rate as a kernel argument, or read from device memory (a captured HIP graph then follows a
     // learning-rate schedule without being captured again)
     const double lr = lr_dev ? *lr_dev : lr_arg;
@@ -289,25 +288,7 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
         if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
         __syncthreads();
         // one slot per block of the step, in launch order: the finish kernel adds them in that fixed order
-        if (threadIdx.x == 0) xdfm_publish(&l2_part[slot0 + blockIdx.x], l2c * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])));
-        // the step's last launch: its last block adds up the partials of ALL launches (the earlier ones are complete: stream
-        // order), in slot order -- what adam_l2_finish_kernel does in a launch of its own
-        if (ticket && xdfm_last_block_done(ticket, gridDim.x)) {
-            __shared__ float acc[ADAM_THREADS];
-            // in that kernel's ORDER: its 1024 threads stride by 1024 and its tree's first two levels add thread t + 512,
-            // then t + 256 -- with more than 256 partials a stride of 256 would round differently (70 tensors: 1480 partials)
-            float vq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                for (int k = threadIdx.x + q * ADAM_THREADS; k < l2_total; k += 4 * ADAM_THREADS) vq[q] += xdfm_peer(l2_part + k);
-            acc[threadIdx.x] = (vq[0] + vq[2]) + (vq[1] + vq[3]);
-            __syncthreads();
-            for (int o = ADAM_THREADS / 2; o > 0; o >>= 1) {
-                if ((int)threadIdx.x < o) acc[threadIdx.x] += acc[threadIdx.x + o];
-                __syncthreads();
-            }
-            if (threadIdx.x == 0) l2_out[0] = acc[0];
-        }
+        if (threadIdx.x == 0) l2_part[slot0 + blockIdx.x] = l2c * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
     }
 }
 
@@ -455,8 +436,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_rows_kernel(
 __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_rows_kernel(
     const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
     AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
-    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell, float* __restrict__ l2_value,
-    unsigned* __restrict__ ticket) {
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell) {
     const int t = clock[0];
     const int QE = (D + 3) / 4 + ((D & 3) ? 1 : 0);
     const int QT = QE + (has_lin ? 1 : 0);
@@ -523,12 +503,6 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_rows_kernel(
         }
     }
     adam_backlog_add(sqv, cell);
-    // adam_rows_finish_kernel's job, by the block that finishes last (every block's integer add is in `cell` by then)
-    if (ticket && xdfm_last_block_done(ticket, gridDim.x) && threadIdx.x == 0) {
-        const unsigned long long tot = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (l2_value) l2_value[0] += (float)((double)(long long)tot / ADAM_FIX);
-        __hip_atomic_store(cell, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
 }
 
 // ---- by row (D % 4 == 0: a row is D / 4 whole chunks of its own; option "adam_rows") ----------------------------------
@@ -617,8 +591,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_by_row_kernel(
 __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_by_row_kernel(
     const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
     AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
-    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell, float* __restrict__ l2_value,
-    unsigned* __restrict__ ticket) {
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell) {
     const int t = clock[0];
     const int Q = D / 4;
     const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
@@ -695,12 +668,6 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_by_row_kernel(
         }
     }
     adam_backlog_add_fix(fix, cell);
-    // adam_rows_finish_kernel's job, by the block that finishes last (every block's integer add is in `cell` by then)
-    if (ticket && xdfm_last_block_done(ticket, gridDim.x) && threadIdx.x == 0) {
-        const unsigned long long tot = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (l2_value) l2_value[0] += (float)((double)(long long)tot / ADAM_FIX);
-        __hip_atomic_store(cell, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
 }
 
 __global__ void adam_rows_finish_kernel(unsigned long long* __restrict__ cell, float* __restrict__ l2_value) {
@@ -918,7 +885,6 @@ static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_ada
     if (clk) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, clk->clock, clk->consts, clk->cap, lr, lr_dev, beta1, beta2);
     // Launch composition: tensors sorted by size and dealt round-robin to the launches (tbl_launch_order)
     const int nlaunch = ceil_div(T, ADAM_CHUNK);
-    unsigned* ticket = xdfm_ticket(TK_ADAM_L2);
     const std::vector<int> order = tbl_launch_order(tensors, T);
     int slot0 = 0;
     for (int l = 0; l < nlaunch; ++l) {
@@ -929,17 +895,15 @@ static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_ada
         int cap = xdfm_opt(OPT_ADAM_BX);
         if (cap <= 0 || cap > ADAM_BX) cap = ADAM_BX;
         tbl_grid(batch, cnt, ADAM_BLOCK_ELEMS, cap);
-        unsigned* tk = (l2_value && l == nlaunch - 1) ? ticket : nullptr;
-        const int l2_total = slot0 + batch.first[cnt];
         if (xdfm_opt(OPT_DBG) & (1 << 17))              // experiment: ordinary (cached) loads and stores
             hipLaunchKernelGGL(adam_step_kernel<false>, dim3(batch.first[cnt]), dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr,
-                               lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts, l2_value, l2_total, tk);
+                               lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts);
         else
             hipLaunchKernelGGL(adam_step_kernel<true>, dim3(batch.first[cnt]), dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr,
-                               lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts, l2_value, l2_total, tk);
+                               lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts);
         slot0 += batch.first[cnt];
     }
-    if (l2_value && !ticket)
+    if (l2_value)
         if (int rc = xdfm_adam_l2_finish(l2_ws, slot0, l2_value, st)) return rc;
     return xdfm_check_launch("adam_step");
 }
@@ -982,15 +946,13 @@ int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const
     const long threads = (long)B * m * QT + 8L * m;
     const dim3 grid((unsigned)ceil_div(threads, (long)ADAM_THREADS));
     hipStream_t st = (hipStream_t)stream;
-    unsigned* ticket = nullptr;      // thousands of blocks: the finish stays a launch of its own (tickets on one address serialise)
     if (by_row)
         hipLaunchKernelGGL(adam_apply_by_row_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0,
-                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell), l2_value, ticket);
+                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell));
     else
         hipLaunchKernelGGL(adam_apply_rows_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0,
-                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell), l2_value, ticket);
-    if (!ticket)
-        if (int rc = xdfm_adam_rows_finish(reinterpret_cast<unsigned long long*>(l2_cell), l2_value, st)) return rc;
+                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell));
+    if (int rc = xdfm_adam_rows_finish(reinterpret_cast<unsigned long long*>(l2_cell), l2_value, st)) return rc;
     return xdfm_check_launch("adam_apply_rows");
 }
 

@@ -49,12 +49,6 @@ int xdfm_fail(int code, const char* fmt, ...) {
 int xdfm_opt(int idx) { return g_opts[idx]; }
 
 #define XDFM_MAX_DEVICES 16
-static unsigned* g_ticket_board[XDFM_MAX_DEVICES] = {nullptr};
-unsigned* xdfm_ticket(int slot) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= XDFM_MAX_DEVICES || !g_ticket_board[dev]) return nullptr;
-    return g_ticket_board[dev] + slot;
-}
 void xdfm_opt_note(int idx, int value) { g_opts[idx] = value; }
 
 // ---- finish batch (finish_batch.h) -------------------------------------------------------------------------------------
@@ -149,7 +143,6 @@ int xdfm_finish_defer(const FinishJob& job, hipStream_t st, bool* taken) {
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev != g_finish_dev)
         return xdfm_fail(XDFM_ERR_INVALID, "finish batch: opened on device %d, a finish arrives on device %d", g_finish_dev, dev);
-    if (g_ticket_board[dev]) return XDFM_OK;       // a registered ticket board takes precedence: nothing is collected
     FinishBatch& fb = g_finish[dev];
     if (fb.jobs.empty()) fb.st = st;
     else if (fb.st != st)
@@ -226,16 +219,6 @@ int xdfm_graph_node_census(void* graph, int* n_nodes, int* n_memset, int* n_unex
     return XDFM_OK;
 }
 
-int xdfm_set_ticket_board(unsigned* board, int slots) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return xdfm_fail(XDFM_ERR_NO_DEVICE, "set_ticket_board: %s", hipGetErrorString(e));
-    if (dev < 0 || dev >= XDFM_MAX_DEVICES) return xdfm_fail(XDFM_ERR_INVALID, "set_ticket_board: device %d", dev);
-    if (board && slots < TK_COUNT) return xdfm_fail(XDFM_ERR_INVALID, "set_ticket_board: %d slots, %d needed", slots, TK_COUNT);
-    g_ticket_board[dev] = board;
-    return XDFM_OK;
-}
-
 int xdfm_finish_batch_begin(void) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
@@ -253,7 +236,7 @@ int xdfm_finish_batch_begin(void) {
 
 int xdfm_finish_batch_active(void) {
     int dev = -1;
-    return (g_finish_dev >= 0 && hipGetDevice(&dev) == hipSuccess && dev == g_finish_dev && !g_ticket_board[dev]) ? 1 : 0;
+    return (g_finish_dev >= 0 && hipGetDevice(&dev) == hipSuccess && dev == g_finish_dev) ? 1 : 0;
 }
 
 int xdfm_finish_batch_run(void* stream) {

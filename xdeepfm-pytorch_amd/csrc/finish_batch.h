@@ -44,7 +44,7 @@ struct FinishTable {                          // the prefix table in front: one 
     FinishJob j[FINISH_MAX_JOBS];
 };
 
-// api.hip.  *taken = true: a batch is open on this device (and no ticket board is registered) and the job now waits for
+// api.hip.  *taken = true: a batch is open on this device and the job now waits for
 // xdfm_finish_batch_run; false: the caller launches its own finish kernel, as it always did.
 int xdfm_finish_defer(const FinishJob& job, hipStream_t st, bool* taken);
 // the families' finishes: deferred into the open batch, or their own launch (what the producers call after their main kernel)

@@ -55,7 +55,7 @@ def finish_batch_begin():
     lib = _lib.load()
     _lib.check(lib.xdfm_finish_batch_begin(), "finish_batch_begin")
     _FINISH_OPEN = True
-    _FINISH_KEEP = [] if lib.xdfm_finish_batch_active() else None      # option at 0, or a ticket board: nothing is recorded
+    _FINISH_KEEP = [] if lib.xdfm_finish_batch_active() else None      # option at 0: nothing is recorded
 
 
 def finish_batch_run(quiet=False):
@@ -106,8 +106,6 @@ def finish_keep(*tensors):
 
 
 def _need_cuda(t: torch.Tensor, name: str):
-    if t.is_cuda:
-        _lib.ticket_board(t.device)
     if not t.is_cuda:
         raise RuntimeError(
             "xdfm: %s is on %s -- the xDeepFM hot path only runs on an MI355X through libxdfm_hip.so; "
