@@ -74,6 +74,8 @@
  * launches) -- additions, the version stays 8.
  * ABI 9: the export that registered a device array for last-block finishes inside the producer kernels (added with ABI 7, opt-in,
  * measured slower) is removed; the finish batch saves those launches.  Nothing else changes.
+ * xdfm_ftrl_tensor, xdfm_ftrl_step (K7f: per-coordinate FTRL-Proximal, a descriptor with two state arrays) -- additions, the
+ * version stays 9.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -832,6 +834,39 @@ int xdfm_rmsprop_step(const xdfm_opt_tensor* tensors, int T, double lr, const do
  * device work, with the offending value in the message. */
 int xdfm_sgdm_step(const xdfm_opt_tensor* tensors, int T, double lr, const double* lr_dev, double mu, int nesterov, float* l2_ws,
                    float* l2_value, void* stream);
+/* FTRL-Proximal (K7f, csrc/ftrl.hip) -- per-coordinate, lr_power -0.5 (McMahan et al., "Ad click prediction: a view from the
+ * trenches", 2013); the reference has no counterpart, the host fallback (xdfm_amd.optim.TableFTRL) spells the same formulas in
+ * torch ops.  The same sweep, rate (`lr` / `lr_dev`), L2 term (`l2` of the descriptor, here l2m; `l2_ws` of
+ * xdfm_opt_step_ws_elems(T) floats, `l2_value`) and marks as above, over a descriptor with TWO state arrays, z and n:
+ *   g' = fma(2 l2m, p, g)
+ *   g' == 0:  p, z and n keep their bits                                   (the zero-gradient rule)
+ *   n' = fma(g', g', n);   r1 = sqrt(n'), r0 = sqrt(n)                     (IEEE)
+ *   sigma = (g' g') / (lr (r1 + r0))          -- the paper's (r1 - r0) / lr as a quotient: no cancellation of the roots
+ *   z' = fma(-sigma, p, z + g')
+ *   p' = |z'| <= l1 ? 0 : (sign(z') l1 - z') / ((beta + r1) / lr + l2)
+ * (one corner: n == 0 with |g'| < 2.6e-23, whose square underflows, takes r1 = |g'|, the root of the exact sum, and sigma = 0
+ * where the quotient is 0 / 0 -- no NaN from finite inputs)
+ * with l1, l2, beta and the rate rounded to float; the L2 term's value is taken of the weights BEFORE the update.  `l2` is the
+ * paper's lambda_2 and enters the denominator as it is (TensorFlow's l2_regularization_strength is half of it).  The L1 term
+ * clips a weight to exactly 0.0.  The zero-gradient rule is a select: an element without a gradient is not touched (no 0 / 0
+ * at n == 0, and a weight that never saw a gradient keeps its initial value), so the exact shortcut of K7s / K7g holds -- an
+ * unmarked chunk of a tensor with l2m == 0 is skipped without being read, one mark byte per 16 bytes of gradient -- and marks
+ * on / off give the same bits.  24 bytes per updated parameter (p, z, n read and written), plus 4 for a gradient read in full
+ * or 1/16 for its mark byte.  param, grad, z and n 16-byte aligned: the float4 path; anything else: a scalar path (z and n must
+ * be 4-byte aligned; with grad_marks all four must be 16-byte aligned).  Errors (NULL `tensors`, T <= 0, lr <= 0 -- whether or
+ * not lr_dev is given; the rate behind lr_dev is the caller's to keep above 0 --, l1 < 0, l2 < 0, beta < 0, a tensor without z
+ * or n, a misaligned state) are reported before any device work, with the offending value in the message. */
+typedef struct {
+    float* param;
+    float* grad;
+    float* z;                       /* the adjusted gradient sum */
+    float* n;                       /* the sum of squared gradients (starts at the initial accumulator value) */
+    long numel;
+    float l2;                       /* the model's L2 strength for the tensor (l2m), not FTRL's l2 */
+    unsigned char* grad_marks;      /* NULL: grad is read in full and left alone */
+} xdfm_ftrl_tensor;
+int xdfm_ftrl_step(const xdfm_ftrl_tensor* tensors, int T, double lr, const double* lr_dev, double l1, double l2, double beta,
+                   float* l2_ws, float* l2_value, void* stream);
 
 /* ------------------------------------------------------------------ deferred Adam for the tables (K7d)
  * Same arithmetic, same results, bit for bit, as the dense sweep above -- but the sweep's 24 bytes per table parameter

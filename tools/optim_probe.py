@@ -20,8 +20,13 @@ xdfm_amd.optim.TableSGD(momentum=MU) and hands the object to compile; `sweep` an
 `stock` with it off -- the fallback the class took before (flush, the L2 term by hand, torch.optim.SGD.step over dense
 gradients).  The switch is a module attribute that is set in front of every block.
 
-    python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad,rmsprop] [--arms sweep,deferred,stock]
-                                [--momentum 0.9 [--nesterov]] [--out FILE.json]
+`--optimizer ftrl` is xdfm_amd.optim.TableFTRL (K7f): `sweep` is its kernel, `stock` the same class on its torch-op step; it
+has no deferred arm.  Its two configurations: the model's default L2 on the tables (every element is updated, 24 B per
+parameter), and `--no_table_l2` (l2_reg_embedding = l2_reg_linear = 0 with FTRL's own l2: the step reads the marks and the
+batch's rows).  `--optimizers ftrl,adagrad` puts the native Adagrad step on the same model beside it.
+
+    python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad,rmsprop,ftrl] [--arms sweep,deferred,stock]
+                                [--momentum 0.9 [--nesterov]] [--no_table_l2] [--out FILE.json]
 """
 import argparse
 import json
@@ -44,13 +49,22 @@ def route(model):
     optim.SGD_MOMENTUM_NATIVE = getattr(model, "_probe_native", True)
 
 
-def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, nesterov=False):
+def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, nesterov=False, no_table_l2=False):
     from deepctr.inputs import DenseFeat, SparseFeat
     from deepctr.models import xDeepFM
     cols = [SparseFeat("C%d" % (i + 1), v, cfg["emb_dim"]) for i, v in enumerate(vocab)]
     cols += [DenseFeat("I%d" % (i + 1), 1) for i in range(cfg["n_dense"])]
-    model = xDeepFM(cols, cols, dnn_hidden_units=cfg["dnn"], cin_layer_size=cfg["cin"], l2_reg_dnn=1e-5, device=dev)
-    if optimizer == "sgd" and momentum:
+    l2_kw = dict(l2_reg_embedding=0.0, l2_reg_linear=0.0) if no_table_l2 else {}
+    model = xDeepFM(cols, cols, dnn_hidden_units=cfg["dnn"], cin_layer_size=cfg["cin"], l2_reg_dnn=1e-5, device=dev, **l2_kw)
+    if optimizer == "ftrl":
+        # `sweep`: K7f; `stock`: the same class sent down its torch-op step.  With --no_table_l2 FTRL's own (proximal) l2 stands
+        # in for the model's L2 on the tables: the recommended configuration, whose cost follows the batch
+        from xdfm_amd.optim import TableFTRL
+        opt = TableFTRL(model.parameters(), lr=1e-3, l2=1e-3 if no_table_l2 else 0.0)
+        model.compile(opt, "binary_crossentropy", metrics=[])
+        if stock:
+            opt._native = lambda: False
+    elif optimizer == "sgd" and momentum:
         from xdfm_amd.optim import TableSGD
         opt = TableSGD(model.parameters(), lr=0.01, momentum=momentum, nesterov=nesterov, deferred=bool(deferred))
         model.compile(opt, "binary_crossentropy", metrics=[])
@@ -63,7 +77,7 @@ def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, neste
         model.compile(optimizer, "binary_crossentropy", metrics=[])
         model.optim.deferred = bool(deferred)
     for pg in model.optim.param_groups:          # a rate at which a sum-reduced loss over 4096 rows stays finite
-        pg["lr"] = {"sgd": 1e-5 * (1.0 - momentum), "adagrad": 1e-3, "rmsprop": 1e-4}[optimizer]
+        pg["lr"] = {"sgd": 1e-5 * (1.0 - momentum), "adagrad": 1e-3, "rmsprop": 1e-4, "ftrl": 1e-3}[optimizer]
     model.train()
     return model
 
@@ -153,6 +167,8 @@ def main():
     ap.add_argument("--momentum", type=float, default=0.0, help="sgd only: SGD with this momentum, in (0, 1) (K7m)")
     ap.add_argument("--nesterov", action="store_true", help="with --momentum: Nesterov momentum")
     ap.add_argument("--arms", default="sweep,deferred,stock")
+    ap.add_argument("--no_table_l2", action="store_true",
+                    help="build the models with l2_reg_embedding = l2_reg_linear = 0 (ftrl: its own l2 = 1e-3 in their place)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if (args.momentum or args.nesterov) and args.optimizers != "sgd":
@@ -169,8 +185,9 @@ def main():
         batches = [(torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev))
                    for X, y in bench.synthetic_batches(8, B, vocab, cfg["n_dense"], seed=2025)]
         for optimizer in args.optimizers.split(","):
+            arms = [a for a in args.arms.split(",") if not (optimizer == "ftrl" and a == "deferred")]      # FTRL has no deferred form
             models = {a: build(cfg, vocab, dev, optimizer, stock=a == "stock", deferred=a == "deferred", momentum=args.momentum,
-                               nesterov=args.nesterov) for a in arms}
+                               nesterov=args.nesterov, no_table_l2=args.no_table_l2) for a in arms}
             kernel = "sgdm" if optimizer == "sgd" and args.momentum else optimizer
             for m in models.values():
                 timed(m, batches, args.warmup, 0)
@@ -186,7 +203,8 @@ def main():
                     secs[a] += dt
                     blocks[a].append(round(dt / n * 1e3, 4))
                 done += n
-            row = dict(vocab=preset, table_params=n_table, optimizer=optimizer, steps=args.steps, block=args.block)
+            row = dict(vocab=preset, table_params=n_table, optimizer=optimizer, steps=args.steps, block=args.block,
+                       table_l2=not args.no_table_l2)
             if args.momentum:
                 row.update(momentum=args.momentum, nesterov=args.nesterov)
             for a in arms:

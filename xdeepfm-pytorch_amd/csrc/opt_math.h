@@ -3,6 +3,7 @@
 // chunk missed by calling this very function with g = 0 (an opaque zero, as the sweep's unmarked chunks do) and the rate
 // the missed step used -- the bit identity of the two paths rests on there being nothing else that spells the arithmetic.
 // Both units are compiled with the same flags: sqrtf and / expand to hipcc's correctly rounded sequences in either.
+// At the end: the element update of the FTRL-Proximal step (K7f, ftrl.hip), which has two state values and no deferred form.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "xdfm_internal.h"     // xdfm_opt
@@ -71,4 +72,43 @@ template <int K>
 __device__ __forceinline__ void opt_four(float4& p, float4& s, const float4& g, float g2, float nlr, const OptHyper& h, float& sq) {
     opt_one<K>(p.x, s.x, g.x, g2, nlr, h, sq); opt_one<K>(p.y, s.y, g.y, g2, nlr, h, sq);
     opt_one<K>(p.z, s.z, g.z, g2, nlr, h, sq); opt_one<K>(p.w, s.w, g.w, g2, nlr, h, sq);
+}
+
+// ---------------------------------------------------------------------------------------------
+// FTRL-Proximal (K7f, ftrl.hip): per-coordinate, lr_power -0.5 (McMahan et al. 2013, algorithm 1 with eta = lr / (beta + sqrt(n)))
+// ---------------------------------------------------------------------------------------------
+// l1, the paper's lambda_2 (it enters the denominator as it is: TensorFlow's l2_regularization_strength is half of it) and beta,
+// as floats
+struct FtrlHyper { float l1, l2, beta; };
+static inline FtrlHyper ftrl_hyper(double l1, double l2, double beta) { return FtrlHyper{(float)l1, (float)l2, (float)beta}; }
+
+// One element: weight p, state z and n, gradient g; `lr` > 0 (the host refuses anything else: it is a divisor).
+//   sigma is the paper's (sqrt(n') - sqrt(n)) / lr written as a quotient, g'^2 / (lr (sqrt(n') + sqrt(n))): the same number
+//   without the cancellation of the two roots (the difference spends 6 times the z bar of the tests, the quotient 0.1 of it).
+//   An element with g' == 0 keeps the bits of p, z and n -- a select, not a product with 0: at n == 0 sigma is 0 / 0, and a
+//   weight that never saw a gradient must not jump from its initial value to the closed form's 0.  So an unmarked chunk of a
+//   tensor without an L2 term is skipped exactly, and marks on / off give the same bits.
+__device__ __forceinline__ void ftrl_one(float& p, float& z, float& n, float g, float g2, float lr, const FtrlHyper& h, float& sq) {
+#pragma clang fp contract(off)
+    sq = fmaf(p, p, sq);
+    const float gp = fmaf(g2, p, g);
+    const float n1 = fmaf(gp, gp, n);
+    // n' == 0 with g' != 0: n was 0 and g'^2 underflowed (|g'| < 2.6e-23).  The root of the exact sum is |g'| then, and the
+    // quotient's numerator has underflowed with its denominator: sigma = 0 instead of 0 / 0.  Everywhere else these two selects
+    // pass sqrt(n') and the quotient through.
+    const float r1 = n1 > 0.f ? sqrtf(n1) : fabsf(gp), r0 = sqrtf(n);
+    const float ds = lr * (r1 + r0);
+    const float sigma = ds > 0.f ? (gp * gp) / ds : 0.f;
+    const float z1 = fmaf(-sigma, p, z + gp);
+    const float den = (h.beta + r1) / lr + h.l2;
+    const float p1 = fabsf(z1) <= h.l1 ? 0.f : (copysignf(h.l1, z1) - z1) / den;
+    const bool live = gp != 0.f;
+    p = live ? p1 : p;
+    z = live ? z1 : z;
+    n = live ? n1 : n;
+}
+__device__ __forceinline__ void ftrl_four(float4& p, float4& z, float4& n, const float4& g, float g2, float lr, const FtrlHyper& h,
+                                          float& sq) {
+    ftrl_one(p.x, z.x, n.x, g.x, g2, lr, h, sq); ftrl_one(p.y, z.y, n.y, g.y, g2, lr, h, sq);
+    ftrl_one(p.z, z.z, n.z, g.z, g2, lr, h, sq); ftrl_one(p.w, z.w, n.w, g.w, g2, lr, h, sq);
 }

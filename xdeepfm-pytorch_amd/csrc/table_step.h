@@ -1,8 +1,8 @@
 // What the table optimizers' translation units share beside their arithmetic (adam_math.h, opt_math.h): K7 / K7d
-// (adam.hip), K7s / K7g / K7r (sgd_adagrad.hip) and K7sd / K7gd / K7rd (sgd_adagrad_deferred.hip).
+// (adam.hip), K7s / K7g / K7r (sgd_adagrad.hip), K7sd / K7gd / K7rd (sgd_adagrad_deferred.hip) and K7f (ftrl.hip).
 //   device: the streaming float4 accesses, and the claim of a deferred chunk (or of a row's chunks) through `last`
 //   host:   the composition of a launch -- which tensors it takes, and each tensor's share of its 1-D grid
-// Everything here is inlined into the kernels and launchers of the three files; none of it has a symbol of its own.
+// Everything here is inlined into the kernels and launchers of the four files; none of it has a symbol of its own.
 #pragma once
 #include "xdfm_internal.h"
 

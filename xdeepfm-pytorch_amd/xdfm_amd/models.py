@@ -702,7 +702,7 @@ class BaseModel(nn.Module):
         self._optim_capturable = False
         self._flush_optim()                # a previous optimizer may still owe table rows their latest steps
         self.optim = self._get_optim(optimizer)
-        # the table optimizers (optim.TableAdam / TableSGD / TableAdagrad / TableRMSprop), also when handed in as an object, e.g.
+        # the table optimizers (optim.TableAdam / TableSGD / TableAdagrad / TableRMSprop / TableFTRL), also when handed in as an object, e.g.
         # TableAdam(..., lazy_rows=True); an object of a stock torch class keeps the stock path
         if getattr(self.optim, "table_step", False):
             self._optim_capturable = all(p.is_cuda for g in self.optim.param_groups for p in g["params"])
@@ -734,6 +734,12 @@ class BaseModel(nn.Module):
         table = {"sgd": native("TableSGD", lambda p: torch.optim.SGD(p, lr=0.01)), "adam": adam,
                  "adagrad": native("TableAdagrad", torch.optim.Adagrad),
                  "rmsprop": native("TableRMSprop", torch.optim.RMSprop)}
+
+        def ftrl(params):
+            # per-coordinate FTRL-Proximal: the reference has none; TableFTRL on a CPU model too, where it takes its torch-op path
+            from .optim import TableFTRL
+            return TableFTRL(list(params))
+        table["ftrl"] = ftrl
         if optimizer not in table:
             raise NotImplementedError
         return table[optimizer](self.parameters())

@@ -21,7 +21,10 @@ marked gradients and device-resident learning rate; their state layout is that o
 Tables with an L2 term may take the deferred (exact) form of those steps (K7sd / K7gd / K7rd, `xdfm_sgd_step_deferred` /
 `xdfm_adagrad_step_deferred` / `xdfm_rmsprop_step_deferred`), as TableAdam's do.
 
-All four classes are the mixin `_TableStep` in front of the stock class: the host scaffold (fields, learning rate on the
+`TableFTRL` (K7f, `xdfm_ftrl_step`) is per-coordinate FTRL-Proximal, which torch does not have: the same sweep over two state
+arrays, `z` and `n`; its fallback is the class's own step in torch ops, and it has no deferred form.
+
+All five classes are the mixin `_TableStep` in front of the stock class (TableFTRL: of torch.optim.Optimizer): the host scaffold (fields, learning rate on the
 device, invalidation, flush, backlog, pickling, the armed L2 term) exists once; a class brings its clock, its C calls and
 what its kernel implements."""
 import ctypes
@@ -57,13 +60,13 @@ def _ptr_tables(struct, ts, ent, cols, tolerate, pad=0):
 
 
 class _TableStep(object):
-    """The host side of the four table optimizers, and what the model's train step duck-types on (`table_step`): `arm_l2`,
+    """The host side of the five table optimizers, and what the model's train step duck-types on (`table_step`): `arm_l2`,
     `owns`, `l2_value`, `grad_sources`, `sync_lr`, `generation`, `note_replay`, `flush`, `take_backlog`.  A mixin in front of
     the stock class.  A class brings its clock layout and C calls (`_deferred_state`, `_catchup`, `_flush_launch`), what its
     kernel implements (`_plain`, `_state_of`, `_hyper`) and the class attributes below; `step` here is the one of TableSGD,
-    TableAdagrad and TableRMSprop, TableAdam has its own."""
+    TableAdagrad, TableRMSprop and TableFTRL, TableAdam has its own."""
     table_step = True
-    _KERNEL = None               # "sgd" / "adagrad" / "rmsprop" ("sgdm" is TableSGD's second kernel: `_kind`)
+    _KERNEL = None               # "sgd" / "adagrad" / "rmsprop" / "ftrl" ("sgdm" is TableSGD's second kernel: `_kind`)
     _ENV = "XDFM_OPT"            # the environment's <_ENV>_DEFERRED / <_ENV>_FLUSH_EVERY
     _PATHS = ("scan",)           # keys of `path_counts`
     _FLOOR = "OPT_DEFER_MIN_NUMEL"      # the module constant "auto" compares with (by name: read when the decision is taken)
@@ -373,7 +376,7 @@ class _TableStep(object):
     def _plain(self, group):                    # hyper-parameters the kernel implements
         raise NotImplementedError
 
-    def _state_of(self, group, p):              # (accumulator or None, host step counter or None)
+    def _state_of(self, group, p):              # (accumulator or None, host step counter or None[, a second state array])
         raise NotImplementedError
 
     def _hyper(self, group):                    # what the replays of a deferred step assume beside the rate: a change flushes
@@ -382,13 +385,23 @@ class _TableStep(object):
     def _kind(self, group):                     # the kernel a group's step runs (TableSGD has two)
         return self._KERNEL
 
+    _DESC = _lib.OptTensor                      # the kernel's descriptor (TableFTRL: two state arrays, _lib.FtrlTensor)
+
+    def _set_state(self, desc, st):             # st: what `_state_of` gave -> the state pointers written into `desc`
+        desc.state = st[0].data_ptr() if st[0] is not None else None
+        return (desc.state,)
+
+    def _stock_step(self, closure):             # what the kernel does not implement: the stock class behind the mixin
+        return super().step(closure)
+
     def _native(self):
         """True when every group can take the kernel: plain hyper-parameters, dense contiguous fp32 CUDA tensors."""
         if getattr(self, "grad_scale", None) is not None or getattr(self, "found_inf", None) is not None:
             return False
         for group in self.param_groups:
-            if not self._plain(group) or not isinstance(group["lr"], float) or group["maximize"] or \
-                    group["differentiable"] or group["weight_decay"] != 0:
+            # (.get: TableFTRL's groups have none of the stock classes' three switches)
+            if not self._plain(group) or not isinstance(group["lr"], float) or group.get("maximize") or \
+                    group.get("differentiable") or group.get("weight_decay", 0) != 0:
                 return False
             for p in group["params"]:
                 g = p.grad
@@ -407,7 +420,7 @@ class _TableStep(object):
             self.flush()                               # the stock step updates every row: they must be current
             if armed:
                 self._l2_by_hand(armed)
-            return super().step(closure)
+            return self._stock_step(closure)
         self.sync_lr()
         lib = _lib.load()
         from . import ops                              # per-kernel timing hook of bench.py
@@ -424,16 +437,18 @@ class _TableStep(object):
             host_steps += [st[1] for st in states if st[1] is not None]
             T = len(params)
             l2 = tuple(armed.get(id(p), 0.0) for p in params) if armed else None
-            key = (tuple(p.data_ptr() for p in params), tuple(st[0].data_ptr() for st in states if st[0] is not None), l2)
+            key = (tuple(p.data_ptr() for p in params),
+                   tuple(s.data_ptr() for st in states for s in (st[0],) + tuple(st[2:]) if s is not None), l2)
             hit = self._desc.get(gi)
             if hit is None or hit[0] != key:
-                arr = (_lib.OptTensor * T)()
+                arr = (self._DESC * T)()
+                aligned = []                           # the tensor's state may be read by float4: a condition of the marks
                 for k in range(T):
                     arr[k].param, arr[k].numel = params[k].data_ptr(), params[k].numel()
-                    arr[k].state = states[k][0].data_ptr() if states[k][0] is not None else None
+                    aligned.append(all((q or 0) % 16 == 0 for q in self._set_state(arr[k], states[k])))
                     arr[k].l2 = l2[k] if l2 is not None else 0.0
-                hit = self._desc[gi] = (key, arr)
-            arr = hit[1]
+                hit = self._desc[gi] = (key, arr, aligned)
+            arr, state_aligned = hit[1], hit[2]
             arenas = [a for src in self.grad_sources for a in src.arenas() if a.pending]
             # Deferral: the tables of the gathers that feed this optimizer, in group 0, with an L2 term and marked gradients,
             # in a single process (a row-parallel run keeps the sweep).  With l2 == 0 the sweep's exact shortcut already
@@ -447,7 +462,7 @@ class _TableStep(object):
                 arr[k].grad, arr[k].grad_marks = gp, None
                 for a in arenas:                       # a view of a kept gradient buffer: read it by its marks
                     mp = a.marks_ptr(gp)
-                    if mp is not None and params[k].data_ptr() % 16 == 0 and (arr[k].state or 0) % 16 == 0:
+                    if mp is not None and params[k].data_ptr() % 16 == 0 and state_aligned[k]:
                         arr[k].grad_marks = mp
                         if defer_ok and l2[k] > 0.0 and params[k].data_ptr() in table_ptrs:
                             deferred_now.append(k)
@@ -491,7 +506,8 @@ class _TableStep(object):
                         last_arr[k] = d["tensors"][params[k].data_ptr()][1].data_ptr()
             nbytes = 0.0
             for k in range(T):
-                per = 8.0 if kind == "sgd" else 16.0   # the byte model of DESIGN.md (K7s / K7g / K7r / K7m)
+                # the byte model of DESIGN.md (K7s / K7g / K7r / K7m; K7f: p, z and n)
+                per = 8.0 if kind == "sgd" else 24.0 if kind == "ftrl" else 16.0
                 if arr[k].grad_marks:
                     # (RMSprop's accumulator decays in every step, the momentum buffer moves its weight in every step: no shortcut
                     # for a tensor without an L2 term)
@@ -533,6 +549,10 @@ class _TableStep(object):
             elif kind == "adagrad":
                 launch = lambda: lib.xdfm_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                        float(group["eps"]), ws_ptr, val_ptr, stream)
+            elif kind == "ftrl":
+                launch = lambda: lib.xdfm_ftrl_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
+                                                    float(group["l1"]), float(group["l2"]), float(group["beta"]), ws_ptr, val_ptr,
+                                                    stream)
             else:
                 launch = lambda: lib.xdfm_sgd_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                    ws_ptr, val_ptr, stream)
@@ -926,3 +946,101 @@ class TableRMSprop(_TableStep, torch.optim.RMSprop):
 
     def _hyper(self, group):
         return (float(group["alpha"]), float(group["eps"]))
+
+
+class TableFTRL(_TableStep, torch.optim.Optimizer):
+    """Per-coordinate FTRL-Proximal (McMahan et al., "Ad click prediction: a view from the trenches", 2013; lr_power -0.5)
+    whose step is K7f (`xdfm_ftrl_step`).  torch has no such class: this one stands on torch.optim.Optimizer, and what the
+    kernel does not take -- CPU parameters, closures, non-fp32 / non-contiguous / sparse tensors, tensor learning rates --
+    runs the same formulas in torch ops (`_stock_step`), with the armed L2 term applied by hand.  Per element, with the
+    model's armed L2 strength l2m for the tensor:
+
+        g' = g + 2 l2m p;   g' == 0: the element is not touched
+        n' = n + g'^2;   sigma = g'^2 / (lr (sqrt(n') + sqrt(n)));   z' = z + g' - sigma p
+        p' = 0 where |z'| <= l1, else (sign(z') l1 - z') / ((beta + sqrt(n')) / lr + l2)
+
+    `l1` clips weights to exactly 0.0.  `l2` is the paper's lambda_2 and enters the denominator as it is: TensorFlow's
+    `l2_regularization_strength` is HALF of it (tf.keras.optimizers.Ftrl(l2_regularization_strength=x) is l2 = 2 x here).  It
+    is proximal, not a gradient term: a row without a gradient does not move, so with the model's own L2 off
+    (l2_reg_embedding = l2_reg_linear = 0) the step reads the gradient marks and the batch's rows only.  sigma is the paper's
+    (sqrt(n') - sqrt(n)) / lr as a quotient, without the cancellation.  State per parameter: `z` and `n`, fp32 tensors of the
+    parameter's shape, `n` filled with `initial_accumulator_value`; created by the first eager step, never inside a capture.
+    There is no deferred form (`deferred` is False; `flush` and `take_backlog` are no-ops), no lr_power other than -0.5 and no
+    l2_shrinkage."""
+    _KERNEL = "ftrl"
+    _DESC = _lib.FtrlTensor
+
+    def __init__(self, params, lr=0.05, l1=0.0, l2=0.0, beta=1.0, initial_accumulator_value=0.1):
+        if not isinstance(lr, torch.Tensor) and not lr > 0.0:
+            raise ValueError("xdfm TableFTRL: lr %r is not above 0 (the step divides by it)" % (lr,))
+        for name, v in (("l1", l1), ("l2", l2), ("beta", beta), ("initial_accumulator_value", initial_accumulator_value)):
+            if not v >= 0.0:
+                raise ValueError("xdfm TableFTRL: %s %r is negative" % (name, v))
+        super().__init__(params, dict(lr=lr, l1=l1, l2=l2, beta=beta, initial_accumulator_value=initial_accumulator_value))
+        self._table_init(deferred=False)
+
+    @staticmethod
+    def _check_lr(lr):
+        if not (lr > 0.0 if isinstance(lr, float) else bool((torch.as_tensor(lr) > 0).all())):
+            raise ValueError("xdfm TableFTRL: lr %r is not above 0 (the step divides by it)" % (lr,))
+
+    def sync_lr(self):
+        for group in self.param_groups:         # a rate <= 0 never reaches the device scalar: the kernel divides by it
+            self._check_lr(group["lr"])
+        super().sync_lr()
+
+    def _plain(self, group):
+        return all(isinstance(group[k], (int, float)) and group[k] >= 0 for k in ("l1", "l2", "beta"))
+
+    def _hyper(self, group):
+        return (float(group["l1"]), float(group["l2"]), float(group["beta"]))
+
+    def _zn(self, group, p):
+        st = self.state[p]
+        if "z" not in st or "n" not in st:
+            if p.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("xdfm TableFTRL: the state is created by an eager step, not inside a HIP-graph capture")
+            like = dict(dtype=torch.float32, memory_format=torch.contiguous_format)
+            st["z"] = torch.zeros_like(p, **like)
+            st["n"] = torch.full_like(p, float(group["initial_accumulator_value"]), **like)
+        return st["z"], st["n"]
+
+    def _state_of(self, group, p):
+        z, n = self._zn(group, p)
+        if not all(s.is_cuda and s.dtype == torch.float32 and s.is_contiguous() for s in (z, n)):
+            raise RuntimeError("xdfm TableFTRL: z and n of a CUDA parameter must be contiguous fp32 CUDA tensors")
+        return z, None, n
+
+    def _set_state(self, desc, st):
+        desc.z, desc.n = st[0].data_ptr(), st[2].data_ptr()
+        return desc.z, desc.n
+
+    @torch.no_grad()
+    def _stock_step(self, closure):
+        """The formulas of the class docstring in torch ops, the zero-gradient rule included (fp32; float64 for a float64
+        parameter).  The armed L2 term is in the gradients already (`_l2_by_hand`)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            lr, l1, l2, beta = group["lr"], group["l1"], group["l2"], group["beta"]
+            self._check_lr(lr)
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                z, n = self._zn(group, p)
+                ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+                g = (p.grad.to_dense() if p.grad.is_sparse else p.grad).to(ct)
+                w, z0, n0 = p.to(ct), z.to(ct), n.to(ct)
+                live = g != 0
+                n1 = torch.addcmul(n0, g, g)
+                r1 = torch.where(n1 > 0, n1.sqrt(), g.abs())         # n' == 0: n == 0 and g'^2 underflowed; the exact root is |g'|
+                ds = lr * (r1 + n0.sqrt())
+                sigma = torch.where(ds > 0, (g * g) / ds, torch.zeros_like(ds))
+                z1 = torch.addcmul(z0 + g, sigma, w, value=-1.0)
+                w1 = torch.where(z1.abs() <= l1, torch.zeros_like(z1), (torch.sign(z1) * l1 - z1) / ((beta + r1) / lr + l2))
+                p.copy_(torch.where(live, w1, w))
+                z.copy_(torch.where(live, z1, z0))
+                n.copy_(torch.where(live, n1, n0))
+        return loss

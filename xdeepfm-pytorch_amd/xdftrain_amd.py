@@ -60,6 +60,9 @@ def _class_weight(args):
     return None if cw is None else {0: float(cw[0]), 1: float(cw[1])}
 
 
+FTRL_DEFAULTS = {"ftrl_l1": 0.0, "ftrl_l2": 0.0, "ftrl_beta": 1.0, "ftrl_init_acc": 0.1}       # TableFTRL's own
+
+
 def parse_args(argv=None, model=None, script=None):
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--data_path", type=str, default=None)
@@ -96,6 +99,13 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--momentum", type=float, default=0.0,
                    help="with --optimizer sgd: SGD with this momentum, in [0, 1) (0: plain SGD, as compile('sgd'))")
     p.add_argument("--nesterov", action="store_true", help="with --optimizer sgd and --momentum > 0: Nesterov momentum")
+    p.add_argument("--ftrl", action="store_true",
+                   help="per-coordinate FTRL-Proximal (xdfm_amd.optim.TableFTRL) in place of --optimizer; --learning_rate applies")
+    p.add_argument("--ftrl_l1", type=float, default=None, help="with --ftrl: L1 strength, >= 0 (default 0); clips weights to exactly 0")
+    p.add_argument("--ftrl_l2", type=float, default=None,
+                   help="with --ftrl: the proximal L2 strength, >= 0 (default 0; twice TensorFlow's l2_regularization_strength)")
+    p.add_argument("--ftrl_beta", type=float, default=None, help="with --ftrl: beta of the per-coordinate rate, >= 0 (default 1)")
+    p.add_argument("--ftrl_init_acc", type=float, default=None, help="with --ftrl: initial accumulator value, >= 0 (default 0.1)")
     p.add_argument("--class_weight", type=float, nargs=2, default=None, metavar=("W0", "W1"),
                    help="weights of the negative and the positive examples in the training loss, e.g. 1 4 for a log whose "
                         "negatives were down-sampled (fit(class_weight={0: W0, 1: W1})); default: none")
@@ -123,6 +133,18 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--autodis_buckets", type=int, default=16)
     p.add_argument("--use_light_version", action="store_true")
     args = p.parse_args(argv)
+    given = [k for k in FTRL_DEFAULTS if getattr(args, k) is not None]
+    if args.ftrl and (args.momentum != 0.0 or args.nesterov):
+        p.error("--ftrl does not go with --momentum / --nesterov")
+    if given and not args.ftrl:
+        p.error("%s need(s) --ftrl" % ", ".join("--" + k for k in given))
+    for k, v in FTRL_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+        elif not getattr(args, k) >= 0.0:
+            p.error("--%s %g is negative" % (k, getattr(args, k)))
+    if args.ftrl and not args.learning_rate > 0.0:
+        p.error("--ftrl needs --learning_rate > 0 (got %g): the step divides by it" % args.learning_rate)
     if (args.momentum != 0.0 or args.nesterov) and args.optimizer != "sgd":
         p.error("--momentum / --nesterov need --optimizer sgd (got --optimizer %s)" % args.optimizer)
     if not 0.0 <= args.momentum < 1.0:
@@ -264,7 +286,14 @@ def build_model(args, cols):
 
 def make_optimizer(args, model):
     """What compile() gets: the optimizer's name, or -- SGD with a momentum, which no name of compile() stands for -- the object:
-    xdfm_amd.optim.TableSGD (K7m) for a model on a GPU, torch.optim.SGD on the CPU.  The rate is set after compile()."""
+    xdfm_amd.optim.TableSGD (K7m) for a model on a GPU, torch.optim.SGD on the CPU; with --ftrl a xdfm_amd.optim.TableFTRL (K7f).
+    The rate is set after compile()."""
+    if args.ftrl:                                       # on the CPU too: the class brings its own torch-op step
+        from xdfm_amd.optim import TableFTRL
+        return TableFTRL(list(model.parameters()), lr=args.learning_rate, l1=args.ftrl_l1, l2=args.ftrl_l2, beta=args.ftrl_beta,
+                         initial_accumulator_value=args.ftrl_init_acc)
+    if args.optimizer != "sgd" or args.momentum == 0.0:
+        return args.optimizer
     if args.optimizer != "sgd" or args.momentum == 0.0:
         return args.optimizer
     params = list(model.parameters())
