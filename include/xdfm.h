@@ -151,6 +151,14 @@ int xdfm_device_count(void);                /* <0: HIP error code negated */
  * (one claim per `last` word of the row, the row's chunks in turn) instead of one thread per 16-byte chunk; 0 = by chunk,
  * which is what every other D runs.  Same bits either way; read when the call issues its launch.  Probe "last_adam_rows":
  * 1 / 0 = the last of those two calls launched the by-row / the by-chunk kernel, -1 before the first call. */
+/* "colaunch" (bit mask, default 7): bodies that do not depend on each other go out as workgroup ranges of one launch.
+ * Bit 0 = xdfm_colaunch_adam_step runs the step's workgroups and the rows update's in one launch
+ * (adam_step_rows_kernel); clear, it issues the launches of xdfm_adam_step_deferred followed by xdfm_adam_apply_rows.
+ * Bit 1 = xdfm_cin_pack_defer records the CIN weight packs for the catch-up and the gather to carry; clear, it launches them.
+ * Bit 2 = xdfm_rider_begin opens a rider scope (below); clear, it opens none.  At 0 every body
+ * leaves in the launch it had before the option existed.  Same bits either way; read when a call issues its launch.  Probes:
+ * "last_colaunch" 1 / 0 = the last xdfm_colaunch_adam_step issued the shared launch / the two, -1 before the first call;
+ * "last_riders" = slab sums the last host launch (pre-pass or scatter) took as riders, -1 before the first. */
 /* "opt_bx" (default 0), the counterpart of "adam_bx" for xdfm_sgd_step / _adagrad_step / _rmsprop_step, their _deferred forms
  * and xdfm_opt_flush / xdfm_rmsprop_flush: the most workgroups one tensor gets in a launch.  0, negative values and values
  * above the built-in caps (512 in the sweep and in the deferred step's scan, 4096 in the flush) mean those caps.  Read when
@@ -195,6 +203,29 @@ int xdfm_finish_batch_run(void* stream);
 int xdfm_finish_batch_active(void);
 int xdfm_finish(int kind, const void* part, const void* part2, void* out, void* out2, void* out3, long n0, long n1, int i0, int i1,
                 void* stream);
+/* Riders: a small body that depends on nothing near it leaves inside the next suitable launch instead of alone.
+ * Between xdfm_rider_begin() and xdfm_rider_flush(stream), xdfm_cin_level_bwd_w / _prepared on the f16x3 / bf16 path do not
+ * launch the ordered sum of their n-split slabs into dW but record it (up to 4; a fifth is launched as before).  A host
+ * launch on the same stream takes the recorded sums as extra workgroups of its own grid (a job table in the kernel
+ * arguments: no copy, capturable).  Hosts: xdfm_cin_bwd_prep where it takes the f16x3 / bf16 pre-pass, and
+ * xdfm_embed_scatter_bwd / _marked (at most 512 rider workgroups: what fits beside the scatter; a longer table stays
+ * recorded).  xdfm_rider_flush issues whatever nobody carried as ONE launch and closes the scope.  One thread per element,
+ * the splits in their fixed order: dW is bit-identical.
+ *   - dW of a recorded level and the workspace `ws` that holds its slabs are undefined / must stay allocated and untouched
+ *     until the carrying launch or xdfm_rider_flush has been issued on the stream.
+ *   - xdfm_rider_begin with a scope open is XDFM_ERR_INVALID; xdfm_rider_flush on another stream than the recorded jobs'
+ *     drops them and returns XDFM_ERR_INVALID; without an open scope or without jobs it launches nothing.
+ *   - ONE scope per process, and its state is not locked (the finish batch has the same rule): the calls between _begin
+ *     and _flush must come from one backward pass at a time.  Two passes that overlap -- on two devices' autograd threads,
+ *     or a backward nested in another -- would find the scope open already (XDFM_ERR_INVALID from the second _begin) or
+ *     mix their jobs; the model's own train step opens one scope around its one backward.
+ *   - Option "colaunch" bit 2 clear: _begin opens nothing and every sum is launched by its own call, as without a scope.
+ * xdfm_rider_pending: the number of recorded sums that no launch has taken yet.  xdfm_rider_active: 1 while a scope is open
+ * and records, else 0. */
+int xdfm_rider_begin(void);
+int xdfm_rider_flush(void* stream);
+int xdfm_rider_pending(void);
+int xdfm_rider_active(void);
 /* [host] node types of a captured hipGraph_t (the host side replays the train step from a HIP graph):
  * memset nodes are counted separately because they are not ordered reliably against neighbouring kernel
  * nodes on ROCm 7.2 / gfx950 (tools/graph_memset_probe.py) -- a graph with n_memset > 0 must not be replayed;
@@ -516,6 +547,21 @@ typedef struct {
 } xdfm_cin_pack_job;
 int xdfm_cin_pack_all_supported(int H, int Hp, int m);
 int xdfm_cin_pack_all(const xdfm_cin_pack_job* jobs, int L, void* stream);
+/* xdfm_cin_pack_all whose launches may leave as riders (option "colaunch" bit 1; clear: exactly xdfm_cin_pack_all).  The packs
+ * depend on the weights only, so a train step can announce them before its embedding gather: the call records the jobs, and
+ *   - the next xdfm_adam_catchup_rows on `stream` carries the partial |W| maxima as extra workgroups of its launch (one
+ *     256-thread workgroup per level and part: the same slots, and a maximum does not depend on the order);
+ *   - the next xdfm_embed_gather_fwd / _ld on `stream` carries the packs (if no catch-up ran, the maxima leave in a launch
+ *     of their own in front of it);
+ *   - xdfm_cin_pack_flush(stream) issues what no launch carried, as xdfm_cin_pack_all's own launches; a second _defer
+ *     flushes an earlier one first.  The packs are defined once the gather or the flush has been issued on the stream: call
+ *     the flush before the first xdfm_cin_level_fwd that reads them.  Byte-identical packs and headers on every route.
+ * The job arrays' buffers must stay allocated until then.  One set of deferred packs per process, not locked (as the
+ * rider scope below).  xdfm_cin_pack_pending: 0 = nothing deferred, 1 = maxima and packs, 2 = packs.  Probe
+ * "last_pack_riders" (reset by _defer): bit 0 = a catch-up carried the maxima, bit 1 = a gather carried the packs. */
+int xdfm_cin_pack_defer(const xdfm_cin_pack_job* jobs, int L, void* stream);
+int xdfm_cin_pack_flush(void* stream);
+int xdfm_cin_pack_pending(void);
 
 /* ------------------------------------------------------------------ dense-layer bias gradient
  * replaces: autograd of deepctr/layers/core.py:120-134 w.r.t. the bias, grad_bias[c] = sum_r g[r][c].
@@ -923,6 +969,17 @@ int xdfm_adam_catchup_rows(const float* X, long ldx, int B, const int* cols, con
 int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
                          const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                          double beta1, double beta2, double eps, float* l2_cell, float* l2_value, void* stream);
+/* xdfm_adam_step_deferred over `tensors` and xdfm_adam_apply_rows over the rows of X, as ONE call: the step and the rows
+ * update touch different tensors and both only read what the clock's tick wrote, so nothing orders them.  With option
+ * "colaunch" bit 0 set (the default) the tick stays a launch of its own in front, then ONE launch runs the step's
+ * workgroups followed by the rows update's (with more than 64 tensors: behind those of the first of the step's launches),
+ * then the two finishes as the separate calls issue them.  With the bit clear (and under "dbg" bit 17) the call IS the two
+ * calls, launch for launch.  Same arithmetic, same sums, same bits either way.  Errors: those of the two calls, all
+ * reported before any device work. */
+int xdfm_colaunch_adam_step(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double lr,
+                            const double* lr_dev, double beta1, double beta2, double eps, float* l2_ws, float* l2_value,
+                            const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
+                            const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, float* l2_cell, void* stream);
 /* Brings every chunk of the XDFM_ADAM_DEFERRED tensors up to the clock, then resets the clock (clock[1] += clock[0],
  * clock[0] = 0, every `last` byte 0).  Errors (NULL tensors / clock / backlog, a NULL clock member, cap outside 3 .. 256,
  * T <= 0 or T > 65535, a deferred tensor with a NULL pointer, an unaligned backlog) are reported before any device work. */

@@ -18,6 +18,7 @@
 #include "xdfm_internal.h"
 #include "finish_batch.h"
 #include "adam_math.h"
+#include "cin_x3_pack.h"   // the catch-up carries the |W| maxima of the CIN weight packs as a rider
 #include "table_step.h"    // the streaming accesses, the chunk claim, the launch order and the grid composer
 
 #define ADAM_THREADS 256
@@ -47,16 +48,18 @@ static inline AdamDev adam_dev(const xdfm_adam_tensor& t) {
 struct AdamBatch { AdamDev t[ADAM_CHUNK]; int first[ADAM_CHUNK + 1]; };
 static_assert(sizeof(AdamBatch) + 128 <= 8192, "the Adam kernels' argument block");
 
+// The step's body for workgroup `bid` of the launch's 1-D grid (adam_step_kernel: every workgroup; adam_step_rows_kernel: the
+// workgroups in front of the rows body's).  Inlined, so that `batch` stays in the kernel's argument block.
 template <bool NT>
-__global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
-    const AdamBatch batch, int cnt, int slot0, double lr_arg, const double* __restrict__ lr_dev, double beta1, double beta2, double eps,
-    float* __restrict__ l2_part, const int* __restrict__ clock, const float* __restrict__ consts) {
+__device__ __forceinline__ void adam_step_body(
+    const AdamBatch& batch, int cnt, int slot0, double lr_arg, const double* __restrict__ lr_dev, double beta1, double beta2, double eps,
+    float* __restrict__ l2_part, const int* __restrict__ clock, const float* __restrict__ consts, const int bid) {
     // the learning rate as a kernel argument, or read from device memory (a captured HIP graph then follows a
     // learning-rate schedule without being captured again)
     const double lr = lr_dev ? *lr_dev : lr_arg;
     int ti = 0;                                        // wave-uniform search over <= ADAM_CHUNK (64) entries
-    for (int k = 1; k < cnt; ++k) ti += (int)blockIdx.x >= batch.first[k] ? 1 : 0;
-    const int lb = (int)blockIdx.x - batch.first[ti];  // this block among the tensor's nb blocks
+    for (int k = 1; k < cnt; ++k) ti += bid >= batch.first[k] ? 1 : 0;
+    const int lb = bid - batch.first[ti];  // this block among the tensor's nb blocks
     const int nb = batch.first[ti + 1] - batch.first[ti];
     const AdamDev& d = batch.t[ti];
     float* __restrict__ p = d.param;
@@ -288,8 +291,15 @@ __global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
         if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
         __syncthreads();
         // one slot per block of the step, in launch order: the finish kernel adds them in that fixed order
-        if (threadIdx.x == 0) l2_part[slot0 + blockIdx.x] = l2c * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
+        if (threadIdx.x == 0) l2_part[slot0 + bid] = l2c * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
     }
+}
+
+template <bool NT>
+__global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_kernel(
+    const AdamBatch batch, int cnt, int slot0, double lr_arg, const double* __restrict__ lr_dev, double beta1, double beta2, double eps,
+    float* __restrict__ l2_part, const int* __restrict__ clock, const float* __restrict__ consts) {
+    adam_step_body<NT>(batch, cnt, slot0, lr_arg, lr_dev, beta1, beta2, eps, l2_part, clock, consts, (int)blockIdx.x);
 }
 
 __global__ __launch_bounds__(1024) void adam_l2_finish_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
@@ -400,7 +410,9 @@ __device__ __forceinline__ AdamClaim adam_claim_chunk(long idx, const float* __r
 __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_rows_kernel(
     const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
     AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
-    double beta1, double beta2, double eps, unsigned long long* __restrict__ backlog) {
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ backlog, int own_blocks, const X3PackJobs riders) {
+    // workgroups past the catch-up's own run a rider and return: the partial |W| maxima of the CIN weight packs (cin_x3_pack.h)
+    if ((int)blockIdx.x >= own_blocks) { x3_absmax_rider(riders, (long)((int)blockIdx.x - own_blocks)); return; }
     const int t = clock[0];
     const int QE = (D + 3) / 4 + ((D & 3) ? 1 : 0);     // chunks a row of D floats can straddle
     const int QT = QE + (has_lin ? 1 : 0);
@@ -433,14 +445,16 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_rows_kernel(
 // The step's update of the deferred tables, by the batch's rows (single process: every marked chunk belongs to a row
 // of X).  Threads [0, B*m*QT): one per (example, field, chunk of the row), first come first served through `last` as in
 // the catch-up; then 4 * m threads per table kind for the numel % 4 tail elements, which no chunk covers.
-__global__ __launch_bounds__(ADAM_THREADS) void adam_apply_rows_kernel(
+// (the body for workgroup `bid` of the rows grid: the kernel of its own below, and the workgroups of adam_step_rows_kernel
+// behind the step's; the pointer tables BY VALUE: taken by reference they go to scratch, see adam_rows_pick)
+__device__ __forceinline__ void adam_apply_rows_body(
     const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
-    AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
-    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell) {
+    const AdamRowsDev emb, const AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell, const long bid) {
     const int t = clock[0];
     const int QE = (D + 3) / 4 + ((D & 3) ? 1 : 0);
     const int QT = QE + (has_lin ? 1 : 0);
-    const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
+    const long idx = bid * ADAM_THREADS + threadIdx.x;
     const long nrow = (long)B * m * QT;
     const float ss = consts[ADAM_CONSTS_PER_STEP * t], bc = consts[ADAM_CONSTS_PER_STEP * t + 1];
     const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
@@ -504,6 +518,12 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_rows_kernel(
     }
     adam_backlog_add(sqv, cell);
 }
+__global__ __launch_bounds__(ADAM_THREADS) void adam_apply_rows_kernel(
+    const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
+    AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell) {
+    adam_apply_rows_body(X, ldx, B, cols, vocab, m, D, emb, lin, has_lin, clock, consts, beta1, beta2, eps, cell, (long)blockIdx.x);
+}
 
 // ---- by row (D % 4 == 0: a row is D / 4 whole chunks of its own; option "adam_rows") ----------------------------------
 // Threads [0, m * B): one per (field, example), the FIELD outermost, and the whole row is the thread's: one claim per `last`
@@ -547,7 +567,9 @@ __device__ __forceinline__ unsigned long long adam_row_claim(const AdamRow& r, u
 __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_by_row_kernel(
     const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
     AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
-    double beta1, double beta2, double eps, unsigned long long* __restrict__ backlog) {
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ backlog, int own_blocks, const X3PackJobs riders) {
+    // workgroups past the catch-up's own run a rider and return: the partial |W| maxima of the CIN weight packs (cin_x3_pack.h)
+    if ((int)blockIdx.x >= own_blocks) { x3_absmax_rider(riders, (long)((int)blockIdx.x - own_blocks)); return; }
     const int t = clock[0];
     const int Q = D / 4;
     const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
@@ -588,13 +610,13 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_by_row_kernel(
 }
 
 // ... and the step's update: as adam_apply_rows_kernel, the 8 * m tail threads behind the row and linear threads
-__global__ __launch_bounds__(ADAM_THREADS) void adam_apply_by_row_kernel(
+__device__ __forceinline__ void adam_apply_by_row_body(
     const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
-    AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
-    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell) {
+    const AdamRowsDev emb, const AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell, const long bid) {
     const int t = clock[0];
     const int Q = D / 4;
-    const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
+    const long idx = bid * ADAM_THREADS + threadIdx.x;
     const long nrow = (long)B * m * (has_lin ? 2 : 1);
     const float ss = consts[ADAM_CONSTS_PER_STEP * t], bc = consts[ADAM_CONSTS_PER_STEP * t + 1];
     const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
@@ -668,6 +690,40 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_apply_by_row_kernel(
         }
     }
     adam_backlog_add_fix(fix, cell);
+}
+__global__ __launch_bounds__(ADAM_THREADS) void adam_apply_by_row_kernel(
+    const float* __restrict__ X, long ldx, int B, const int* __restrict__ cols, const int* __restrict__ vocab, int m, int D,
+    AdamRowsDev emb, AdamRowsDev lin, int has_lin, const int* __restrict__ clock, const float* __restrict__ consts,
+    double beta1, double beta2, double eps, unsigned long long* __restrict__ cell) {
+    adam_apply_by_row_body(X, ldx, B, cols, vocab, m, D, emb, lin, has_lin, clock, consts, beta1, beta2, eps, cell, (long)blockIdx.x);
+}
+
+// The step and the rows update in ONE launch (xdfm_colaunch_adam_step, option "colaunch" bit 0).  The two touch
+// different tensors -- the rows update owns the tables whose `param` its pointer arrays hold, the step everything else -- and
+// both only read what adam_tick_kernel wrote, so nothing orders them; alone, either leaves most of the chip idle (the step:
+// some 94 waves in long dependent chains; the rows: a claim / replay / update chain per row).  Workgroups [0, first[cnt]) run
+// the step's body: its chains are the long ones, they start first, and their L2 partials keep their slots.  The workgroups
+// behind them run the rows body with the block index rebased.  Same arithmetic, same sums: the bits of the two launches.
+struct AdamRowsArgs {
+    const float* X; long ldx; int B; const int* cols; const int* vocab; int m; int D;
+    AdamRowsDev emb, lin; int has_lin; unsigned long long* cell;
+};
+static_assert(sizeof(AdamBatch) + sizeof(AdamRowsArgs) + 128 <= 8192, "adam_step_rows_kernel's argument block");
+template <bool BY_ROW>
+__global__ __launch_bounds__(ADAM_THREADS, 3) void adam_step_rows_kernel(
+    const AdamBatch batch, int cnt, int slot0, double lr_arg, const double* __restrict__ lr_dev, double beta1, double beta2, double eps,
+    float* __restrict__ l2_part, const int* __restrict__ clock, const float* __restrict__ consts, const AdamRowsArgs r) {
+    const int own = batch.first[cnt];
+    if ((int)blockIdx.x < own) {
+        // NT = true always: xdfm_colaunch_adam_step leaves the cached-access experiment ("dbg" bit 17) to the two launches
+        adam_step_body<true>(batch, cnt, slot0, lr_arg, lr_dev, beta1, beta2, eps, l2_part, clock, consts, (int)blockIdx.x);
+        return;
+    }
+    const long bid = (long)blockIdx.x - own;
+    if constexpr (BY_ROW)
+        adam_apply_by_row_body(r.X, r.ldx, r.B, r.cols, r.vocab, r.m, r.D, r.emb, r.lin, r.has_lin, clock, consts, beta1, beta2, eps, r.cell, bid);
+    else
+        adam_apply_rows_body(r.X, r.ldx, r.B, r.cols, r.vocab, r.m, r.D, r.emb, r.lin, r.has_lin, clock, consts, beta1, beta2, eps, r.cell, bid);
 }
 
 __global__ void adam_rows_finish_kernel(unsigned long long* __restrict__ cell, float* __restrict__ l2_value) {
@@ -844,8 +900,10 @@ int xdfm_adam_step(const xdfm_adam_tensor* tensors, int T, double lr, double bet
     return xdfm_adam_step_lr(tensors, T, lr, nullptr, beta1, beta2, eps, l2_ws, l2_value, stream);
 }
 
+// rows != nullptr: the rows update rides behind the first launch's workgroups (adam_step_rows_kernel)
 static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double lr, const double* lr_dev,
-                          double beta1, double beta2, double eps, float* l2_ws, float* l2_value, void* stream);
+                          double beta1, double beta2, double eps, float* l2_ws, float* l2_value, void* stream,
+                          const AdamRowsArgs* rows = nullptr, bool rows_by_row = false, int rows_blocks = 0);
 
 int xdfm_adam_step_lr(const xdfm_adam_tensor* tensors, int T, double lr, const double* lr_dev, double beta1, double beta2,
                       double eps, float* l2_ws, float* l2_value, void* stream) {
@@ -862,7 +920,8 @@ int xdfm_adam_step_deferred(const xdfm_adam_tensor* tensors, int T, const xdfm_a
 }
 
 static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double lr, const double* lr_dev,
-                          double beta1, double beta2, double eps, float* l2_ws, float* l2_value, void* stream) {
+                          double beta1, double beta2, double eps, float* l2_ws, float* l2_value, void* stream,
+                          const AdamRowsArgs* rows, bool rows_by_row, int rows_blocks) {
     XDFM_REQUIRE(tensors, "adam_step: null pointer");
     XDFM_REQUIRE(T > 0 && T <= 65535, "adam_step: bad tensor count %d", T);
     XDFM_REQUIRE(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "adam_step: bad hyper-parameters");
@@ -895,7 +954,15 @@ static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_ada
         int cap = xdfm_opt(OPT_ADAM_BX);
         if (cap <= 0 || cap > ADAM_BX) cap = ADAM_BX;
         tbl_grid(batch, cnt, ADAM_BLOCK_ELEMS, cap);
-        if (xdfm_opt(OPT_DBG) & (1 << 17))              // experiment: ordinary (cached) loads and stores
+        if (rows && l == 0) {                           // the step's workgroups, then the rows update's
+            const dim3 grid((unsigned)(batch.first[cnt] + rows_blocks));
+            if (rows_by_row)
+                hipLaunchKernelGGL(adam_step_rows_kernel<true>, grid, dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev, beta1,
+                                   beta2, eps, l2_value ? l2_ws : nullptr, clock, consts, *rows);
+            else
+                hipLaunchKernelGGL(adam_step_rows_kernel<false>, grid, dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev, beta1,
+                                   beta2, eps, l2_value ? l2_ws : nullptr, clock, consts, *rows);
+        } else if (xdfm_opt(OPT_DBG) & (1 << 17))       // experiment: ordinary (cached) loads and stores
             hipLaunchKernelGGL(adam_step_kernel<false>, dim3(batch.first[cnt]), dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr,
                                lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts);
         else
@@ -920,40 +987,82 @@ int xdfm_adam_catchup_rows(const float* X, long ldx, int B, const int* cols, con
     const bool by_row = adam_by_row(D);
     const int QT = by_row ? (lin ? 2 : 1) : (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);      // threads per (example, field)
     const long threads = (long)B * m * QT;
-    const dim3 grid((unsigned)ceil_div(threads, (long)ADAM_THREADS));
+    dim3 grid((unsigned)ceil_div(threads, (long)ADAM_THREADS));
+    // rider: deferred |W| maxima of the CIN weight packs (xdfm_cin_pack_defer) go out as workgroups behind the catch-up's own
+    const int own_blocks = (int)grid.x;
+    X3PackJobs riders = {};
+    grid.x += (unsigned)x3_pack_take_absmax((hipStream_t)stream, &riders);
     if (by_row)
         hipLaunchKernelGGL(adam_catchup_by_row_kernel, grid, dim3(ADAM_THREADS), 0, (hipStream_t)stream, X, ldx, B, cols, vocab, m, D,
-                           e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog));
+                           e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog),
+                           own_blocks, riders);
     else
         hipLaunchKernelGGL(adam_catchup_rows_kernel, grid, dim3(ADAM_THREADS), 0, (hipStream_t)stream, X, ldx, B, cols, vocab, m, D,
-                           e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog));
+                           e, l, lin ? 1 : 0, clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog),
+                           own_blocks, riders);
     return xdfm_check_launch("adam_catchup_rows");
+}
+
+// the checks of xdfm_adam_apply_rows (and of the rows half of xdfm_colaunch_adam_step), before any device work
+static int adam_apply_rows_check(const char* what, const float* X, const int* cols, const int* vocab, int B, int m, int D,
+                                 const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk, float* l2_cell) {
+    XDFM_REQUIRE(X && cols && vocab && emb && clk && l2_cell, "%s: null pointer", what);
+    if (int rc = adam_clock_ok(what, clk)) return rc;
+    XDFM_REQUIRE(emb->last && (!lin || lin->last), "%s: `last` tables missing", what);
+    XDFM_REQUIRE(emb->grad && emb->marks && (!lin || (lin->grad && lin->marks)), "%s: gradient / mark tables missing", what);
+    XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "%s: bad shape B=%d m=%d D=%d", what, B, m, D);
+    XDFM_REQUIRE((((size_t)l2_cell) & 7) == 0, "%s: l2_cell must be 8-byte aligned", what);
+    return XDFM_OK;
+}
+// ... and its kernel arguments; -> the workgroups of the rows grid
+static int adam_apply_rows_args(AdamRowsArgs& a, bool by_row, const float* X, long ldx, int B, const int* cols, const int* vocab, int m,
+                                int D, const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, float* l2_cell) {
+    const AdamRowsDev e = {emb->param, emb->exp_avg, emb->exp_avg_sq, emb->last, emb->l2, emb->grad, emb->marks};
+    const AdamRowsDev l = lin ? AdamRowsDev{lin->param, lin->exp_avg, lin->exp_avg_sq, lin->last, lin->l2, lin->grad, lin->marks} : e;
+    a = AdamRowsArgs{X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0, reinterpret_cast<unsigned long long*>(l2_cell)};
+    const int QT = by_row ? (lin ? 2 : 1) : (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);
+    const long threads = (long)B * m * QT + 8L * m;
+    return (int)ceil_div(threads, (long)ADAM_THREADS);
 }
 
 int xdfm_adam_apply_rows(const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
                          const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, const xdfm_adam_clock* clk,
                          double beta1, double beta2, double eps, float* l2_cell, float* l2_value, void* stream) {
-    XDFM_REQUIRE(X && cols && vocab && emb && clk && l2_cell, "adam_apply_rows: null pointer");
-    if (int rc = adam_clock_ok("adam_apply_rows", clk)) return rc;
-    XDFM_REQUIRE(emb->last && (!lin || lin->last), "adam_apply_rows: `last` tables missing");
-    XDFM_REQUIRE(emb->grad && emb->marks && (!lin || (lin->grad && lin->marks)), "adam_apply_rows: gradient / mark tables missing");
-    XDFM_REQUIRE(B > 0 && m > 0 && D > 0, "adam_apply_rows: bad shape B=%d m=%d D=%d", B, m, D);
-    XDFM_REQUIRE((((size_t)l2_cell) & 7) == 0, "adam_apply_rows: l2_cell must be 8-byte aligned");
-    const AdamRowsDev e = {emb->param, emb->exp_avg, emb->exp_avg_sq, emb->last, emb->l2, emb->grad, emb->marks};
-    const AdamRowsDev l = lin ? AdamRowsDev{lin->param, lin->exp_avg, lin->exp_avg_sq, lin->last, lin->l2, lin->grad, lin->marks} : e;
+    if (int rc = adam_apply_rows_check("adam_apply_rows", X, cols, vocab, B, m, D, emb, lin, clk, l2_cell)) return rc;
     const bool by_row = adam_by_row(D);
-    const int QT = by_row ? (lin ? 2 : 1) : (D + 3) / 4 + ((D & 3) ? 1 : 0) + (lin ? 1 : 0);
-    const long threads = (long)B * m * QT + 8L * m;
-    const dim3 grid((unsigned)ceil_div(threads, (long)ADAM_THREADS));
+    AdamRowsArgs a;
+    const dim3 grid((unsigned)adam_apply_rows_args(a, by_row, X, ldx, B, cols, vocab, m, D, emb, lin, l2_cell));
     hipStream_t st = (hipStream_t)stream;
     if (by_row)
-        hipLaunchKernelGGL(adam_apply_by_row_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0,
-                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell));
+        hipLaunchKernelGGL(adam_apply_by_row_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, a.emb, a.lin, a.has_lin,
+                           clk->clock, clk->consts, beta1, beta2, eps, a.cell);
     else
-        hipLaunchKernelGGL(adam_apply_rows_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, e, l, lin ? 1 : 0,
-                           clk->clock, clk->consts, beta1, beta2, eps, reinterpret_cast<unsigned long long*>(l2_cell));
+        hipLaunchKernelGGL(adam_apply_rows_kernel, grid, dim3(ADAM_THREADS), 0, st, X, ldx, B, cols, vocab, m, D, a.emb, a.lin, a.has_lin,
+                           clk->clock, clk->consts, beta1, beta2, eps, a.cell);
     if (int rc = xdfm_adam_rows_finish(reinterpret_cast<unsigned long long*>(l2_cell), l2_value, st)) return rc;
     return xdfm_check_launch("adam_apply_rows");
+}
+
+int xdfm_colaunch_adam_step(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double lr,
+                            const double* lr_dev, double beta1, double beta2, double eps, float* l2_ws, float* l2_value,
+                            const float* X, long ldx, int B, const int* cols, const int* vocab, int m, int D,
+                            const xdfm_adam_rows* emb, const xdfm_adam_rows* lin, float* l2_cell, void* stream) {
+    // both halves' arguments are checked before either launches
+    XDFM_REQUIRE(!(clk && clk->clock && clk->consts && clk->cap > 256), "colaunch_adam_step: bad clock (cap %d > 256)", clk->cap);
+    if (int rc = adam_apply_rows_check("colaunch_adam_step", X, cols, vocab, B, m, D, emb, lin, clk, l2_cell)) return rc;
+    // option "colaunch" bit 0 clear (or the cached-access experiment of "dbg"): the two calls, launch for launch
+    const bool pair = (xdfm_opt(OPT_COLAUNCH) & 1) && !(xdfm_opt(OPT_DBG) & (1 << 17));
+    xdfm_opt_note(OPT_LAST_COLAUNCH, pair ? 1 : 0);
+    if (!pair) {
+        if (int rc = xdfm_adam_step_deferred(tensors, T, clk, lr, lr_dev, beta1, beta2, eps, l2_ws, l2_value, stream)) return rc;
+        return xdfm_adam_apply_rows(X, ldx, B, cols, vocab, m, D, emb, lin, clk, beta1, beta2, eps, l2_cell, l2_value, stream);
+    }
+    const bool by_row = adam_by_row(D);
+    AdamRowsArgs a;
+    const int rows_blocks = adam_apply_rows_args(a, by_row, X, ldx, B, cols, vocab, m, D, emb, lin, l2_cell);
+    if (int rc = adam_step_impl(tensors, T, clk, lr, lr_dev, beta1, beta2, eps, l2_ws, l2_value, stream, &a, by_row, rows_blocks)) return rc;
+    if (int rc = xdfm_adam_rows_finish(reinterpret_cast<unsigned long long*>(l2_cell), l2_value, (hipStream_t)stream)) return rc;
+    return xdfm_check_launch("colaunch_adam_step");
 }
 
 int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double beta1, double beta2,

@@ -35,8 +35,12 @@ static int g_opts[OPT_COUNT] = {
     /* OPT_LAST_ADAM_ROWS */ -1,
     /* OPT_OPT_BX */ 0,
     /* OPT_FINISH_BATCH */ 1,
+    /* OPT_COLAUNCH */ 7,
+    /* OPT_LAST_COLAUNCH */ -1,
+    /* OPT_LAST_RIDERS */ -1,
+    /* OPT_LAST_PACK_RIDERS */ -1,
 };
-static const char* const g_opt_names[OPT_COUNT] = {"fwd_nf", "bww_nsplit", "bww_slab", "bww_mt", "dbg", "cin_math", "x3_fwd_mt", "x3_bwx_rows", "x3_waves", "bww_phase", "adam_bx", "last_fwd_kernel", "last_bwx_kernel", "last_bww_kernel", "last_sym", "x3_sym", "bww_xcd", "last_fwd_inst", "last_bwx_inst", "last_bww_inst", "last_fwd_f32", "last_bwx_f32", "last_bww_f32", "adam_rows", "last_adam_rows", "opt_bx", "finish_batch"};
+static const char* const g_opt_names[OPT_COUNT] = {"fwd_nf", "bww_nsplit", "bww_slab", "bww_mt", "dbg", "cin_math", "x3_fwd_mt", "x3_bwx_rows", "x3_waves", "bww_phase", "adam_bx", "last_fwd_kernel", "last_bwx_kernel", "last_bww_kernel", "last_sym", "x3_sym", "bww_xcd", "last_fwd_inst", "last_bwx_inst", "last_bww_inst", "last_fwd_f32", "last_bwx_f32", "last_bww_f32", "adam_rows", "last_adam_rows", "opt_bx", "finish_batch", "colaunch", "last_colaunch", "last_riders", "last_pack_riders"};
 
 int xdfm_fail(int code, const char* fmt, ...) {
     va_list ap;

@@ -453,6 +453,25 @@ int xdfm_cin_pack_all(const xdfm_cin_pack_job* jobs, int L, void* stream) {
     return x3_pack_all(jobs, L, (hipStream_t)stream);
 }
 
+static int cin_pack_jobs_ok(const char* what, const xdfm_cin_pack_job* jobs, int L) {
+    XDFM_REQUIRE(jobs && L > 0 && L <= 8, "%s: 1..8 jobs", what);
+    for (int l = 0; l < L; ++l) {
+        XDFM_REQUIRE(jobs[l].W && (jobs[l].fwd_pack || jobs[l].bwd_pack), "%s: job %d has no weight / output", what, l);
+        XDFM_REQUIRE(xdfm_cin_pack_all_supported(jobs[l].H, jobs[l].Hp, jobs[l].m),
+                     "%s: level %d (H=%d Hp=%d m=%d) has no f16x3 kernels in both directions", what, l, jobs[l].H,
+                     jobs[l].Hp, jobs[l].m);
+        XDFM_REQUIRE(((((size_t)jobs[l].fwd_pack) | ((size_t)jobs[l].bwd_pack)) & 15) == 0, "%s: packs must be 16-byte aligned", what);
+    }
+    return XDFM_OK;
+}
+int xdfm_cin_pack_defer(const xdfm_cin_pack_job* jobs, int L, void* stream) {
+    if (int rc = cin_pack_jobs_ok("cin_pack_defer", jobs, L)) return rc;
+    xdfm_opt_note(OPT_LAST_PACK_RIDERS, 0);
+    return x3_pack_defer(jobs, L, (hipStream_t)stream);
+}
+int xdfm_cin_pack_flush(void* stream) { return x3_pack_flush((hipStream_t)stream); }
+int xdfm_cin_pack_pending(void) { return x3_pack_pending(); }
+
 int xdfm_cin_level_fwd(const float* xp, const float* x0, const float* Wf, const float* bias, int H, int Hp,
                        int m, long N, int act, float* out, void* stream) {
     XDFM_REQUIRE(xp && x0 && Wf && bias && out, "cin_level_fwd: null pointer");

@@ -13,6 +13,7 @@
 //
 // This file: the forward kernel (K3) and its weight pack.  deepctr/layers/interaction.py:218-229.
 #include "cin_x3_fwd.h"
+#include "cin_x3_pack.h"      // the pack bodies and the job table of all levels (shared with the launches that carry them as riders)
 
 
 // ---------------------------------------------------------------------------------------------
@@ -62,8 +63,6 @@ bool x3_fwd_usable(int H, int Hp, int m) {
 // |W| maximum: every block stores its partial maximum in header slot X3_HDR_PART + blockIdx.x (plain stores,
 // no zero-initialised cell and no atomics: nothing here depends on a memset node inside a captured graph);
 // the pack kernels reduce the <= X3_ABSMAX_BLOCKS partials themselves.
-#define X3_ABSMAX_BLOCKS 64
-#define X3_HDR_PART 64
 __global__ __launch_bounds__(1024) void x3_absmax_kernel(const float* __restrict__ W, long total, float* __restrict__ hdr) {
     __shared__ float red[16];
     float v = 0.f;
@@ -94,100 +93,6 @@ static inline int x3_absmax_blocks(long total) {
 
 static void x3_launch_absmax(const float* W, long total, float* pack, hipStream_t st) {
     hipLaunchKernelGGL(x3_absmax_kernel, dim3(x3_absmax_blocks(total)), dim3(1024), 0, st, W, total, pack);
-}
-
-__device__ __forceinline__ float x3_weight_scale(const float* __restrict__ hdr, int nparts) {
-    float mx = 0.f;
-    for (int k = 0; k < nparts; ++k) mx = fmaxf(mx, hdr[X3_HDR_PART + k]);
-    return x3_pow2_scale(mx, 15);
-}
-
-// pack layout (after the X3_HDR-float header: [0] = sW, [1] = 1/sW, [64..127] = partial maxima of |W|):
-//   [mb][g < NS+2][mt < MT][p: 0 = hi, 1 = lo][lane][8 halves]   -- 1 KB per (mt, p) fragment
-// element t of lane (r = lane & 31, hh = lane >> 5) of step g = (blk, s):
-//   row = (mb*MT + mt)*32 + r,  q = 8s + t,  il = q / m,  j = q % m,  i = blk*8 + hh*RH + il
-// bf16 (nt == 1): no scale (sW = 1), one fragment per (g, mt): the bf16 bit patterns of W
-__device__ __forceinline__ void x3_fwd_pack_one(const float* __restrict__ W, int H, int Hp, int m, const X3Geom& G,
-                                                int nparts, float* __restrict__ pack, long idx, int nt) {
-    const float sW = nt == 3 ? x3_weight_scale(pack, nparts) : 1.f;
-    if (idx == 0) { pack[0] = sW; pack[1] = 1.f / sW; }
-    const int lane = (int)(idx & 63);
-    long rest = idx >> 6;
-    const int mt = (int)(rest % G.MT); rest /= G.MT;
-    const int g = (int)(rest % G.NSA);
-    const int mb = (int)(rest / G.NSA);
-    const int r = lane & 31, hh = lane >> 5;
-    const int row = (mb * G.MT + mt) * 32 + r;
-    int blk, s, RH;
-    if (g < G.FB * G.MP) { blk = g / G.MP; s = g - blk * G.MP; RH = 4; }
-    else { blk = G.FB; s = g - G.FB * G.MP; RH = G.RH; }
-    h8 hi, lo;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int q = 8 * s + t, il = q / m, j = q - il * m;
-        const int i = blk * 8 + hh * RH + il;
-        float v = 0.f;
-        if (g < G.NS && row < H && il < RH && i < Hp) v = W[(long)row * ((long)Hp * m) + (long)i * m + j] * sW;
-        if (nt == 3) {
-            const _Float16 a = (_Float16)v;
-            hi[t] = a;
-            lo[t] = (_Float16)(v - (float)a);
-        } else {
-            hi[t] = __builtin_bit_cast(_Float16, (__bf16)v);
-        }
-    }
-    if (nt == 3) {
-        h8* dst = reinterpret_cast<h8*>(pack + X3_HDR) + (((long)mb * G.NSA + g) * G.MT + mt) * 128 + lane;
-        dst[0] = hi;
-        dst[64] = lo;
-    } else {
-        reinterpret_cast<h8*>(pack + X3_HDR)[(((long)mb * G.NSA + g) * G.MT + mt) * 64 + lane] = hi;
-    }
-}
-
-// folded pack of level 0 (x3_sym_*), same fragment layout with the SYM geometry; its own header: the folded weights
-// reach twice the maximum, so their scale is half the one of the plain pack ([0] = sW/2, [1] = 2/sW).  `hdr` = the plain
-// pack's header (partial maxima of |W|).
-__device__ __forceinline__ void x3_fwd_pack_sym_one(const float* __restrict__ W, int H, int m, const X3Geom& G, int nparts,
-                                                    const float* __restrict__ hdr, float* __restrict__ pack, long idx, int nt) {
-    const float sW = nt == 3 ? 0.5f * x3_weight_scale(hdr, nparts) : 1.f;
-    if (idx == 0) { pack[0] = sW; pack[1] = 1.f / sW; }
-    const int lane = (int)(idx & 63);
-    long rest = idx >> 6;
-    const int mt = (int)(rest % G.MT); rest /= G.MT;
-    const int g = (int)(rest % G.NSA);
-    const int mb = (int)(rest / G.NSA);
-    const int r = lane & 31, hh = lane >> 5;
-    const int row = (mb * G.MT + mt) * 32 + r;
-    const float* __restrict__ Wr = W + (long)(row < H ? row : 0) * ((long)m * m);
-    h8 hi, lo;
-    int i = x3_sym_i(m, 8 * g), j = x3_sym_j(m, 8 * g);        // slot 8g; the next ones follow along the list's rows
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int q = 8 * g + t;
-        float v = 0.f;
-        if (t > 0 && ++j > m - 1 - i) { ++i; j = i; }
-        if (g < G.NS && row < H && q < x3_sym_pairs(m)) {
-            const int a = hh ? m - 1 - i : i, b = hh ? m - 1 - j : j;
-            if (a == b) v = Wr[a * m + a];
-            else if (!(hh && i + j == m - 1)) v = Wr[a * m + b] + Wr[b * m + a];
-            v *= sW;
-        }
-        if (nt == 3) {
-            const _Float16 x = (_Float16)v;
-            hi[t] = x;
-            lo[t] = (_Float16)(v - (float)x);
-        } else {
-            hi[t] = __builtin_bit_cast(_Float16, (__bf16)v);
-        }
-    }
-    if (nt == 3) {
-        h8* dst = reinterpret_cast<h8*>(pack + X3_HDR) + (((long)mb * G.NSA + g) * G.MT + mt) * 128 + lane;
-        dst[0] = hi;
-        dst[64] = lo;
-    } else {
-        reinterpret_cast<h8*>(pack + X3_HDR)[(((long)mb * G.NSA + g) * G.MT + mt) * 64 + lane] = hi;
-    }
 }
 
 __global__ void x3_fwd_pack_sym_kernel(const float* __restrict__ W, int H, int m, X3Geom G, int nparts,
@@ -278,87 +183,6 @@ bool x3_bwx_usable(int H, int Hp, int m) {
     return nt != 0 && H > (nt == 3 ? 16 : 32) && H <= 256;
 }
 
-// pack: [tile = iblk*m + j][hb < HBT][p][lane][8 halves]; element t of lane (r, hh):
-//   W[h = 16*hb + 8*hh + t][(iblk*32 + r)*m + j] * sW   (0 outside); two dummy stages appended.
-__device__ __forceinline__ void x3_bwx_pack_one(const float* __restrict__ W, int H, int Hp, int m, const X3BwxGeom& G,
-                                                int nparts, float* __restrict__ pack, long idx, int nt) {
-    const float sW = nt == 3 ? x3_weight_scale(pack, nparts) : 1.f;
-    if (idx == 0) { pack[0] = sW; pack[1] = 1.f / sW; }
-    const int lane = (int)(idx & 63);
-    long rest = idx >> 6;
-    const int hb = (int)(rest % G.HBT);
-    const long tile = rest / G.HBT;
-    const int j = (int)(tile % m);
-    const int iblk = (int)(tile / m);
-    const int r = lane & 31, hh = lane >> 5;
-    const int i = iblk * 32 + r;
-    h8 hi, lo;
-#pragma unroll
-    for (int t = 0; t < 8; ++t) {
-        const int h = 16 * hb + 8 * hh + t;
-        float v = 0.f;
-        if (tile < G.NT && h < H && i < Hp) v = W[(long)h * ((long)Hp * m) + (long)i * m + j] * sW;
-        if (nt == 3) {
-            const _Float16 a = (_Float16)v;
-            hi[t] = a;
-            lo[t] = (_Float16)(v - (float)a);
-        } else {
-            hi[t] = __builtin_bit_cast(_Float16, (__bf16)v);
-        }
-    }
-    if (nt == 3) {
-        h8* dst = reinterpret_cast<h8*>(pack + X3_HDR) + (tile * G.HBT + hb) * 128 + lane;
-        dst[0] = hi;
-        dst[64] = lo;
-    } else {
-        reinterpret_cast<h8*>(pack + X3_HDR)[(tile * G.HBT + hb) * 64 + lane] = hi;
-    }
-}
-
-// folded pack of level 0 for the dX kernel of cin_x3_bwx_sym.hip: [tile t < m/2][hb < HBT][p][lane][8 halves]; row r of
-// tile t is the pair (i = r, j = t) for r <= t, (i = 31-r, j = m-1-t) for r >= 32-m+t, nothing in between; element
-// W'[h = 16*hb + 8*hh + e][(i, j)] * sW / 2 with W'(i, j) = W(i, j) + W(j, i), W(i, i) on the diagonal.  Own header as in
-// the forward's folded pack; `hdr` = the plain pack's header (partial maxima of |W|).
-__device__ __forceinline__ void x3_bwx_pack_sym_one(const float* __restrict__ W, int H, int m, const X3BwxGeom& G, int nparts,
-                                                    const float* __restrict__ hdr, float* __restrict__ pack, long idx, int nt) {
-    const float sW = nt == 3 ? 0.5f * x3_weight_scale(hdr, nparts) : 1.f;
-    if (idx == 0) { pack[0] = sW; pack[1] = 1.f / sW; }
-    const int lane = (int)(idx & 63);
-    long rest = idx >> 6;
-    const int hb = (int)(rest % G.HBT);
-    const int t = (int)(rest / G.HBT);
-    const int r = lane & 31, hh = lane >> 5;
-    int i = -1, j = 0;
-    if (t < m / 2) {
-        if (r <= t) { i = r; j = t; }
-        else if (31 - r <= m - 1 - t) { i = 31 - r; j = m - 1 - t; }
-    }
-    h8 hi, lo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const int h = 16 * hb + 8 * hh + e;
-        float v = 0.f;
-        if (i >= 0 && h < H) {
-            const float* __restrict__ Wr = W + (long)h * ((long)m * m);
-            v = (i == j ? Wr[i * m + i] : Wr[i * m + j] + Wr[j * m + i]) * sW;
-        }
-        if (nt == 3) {
-            const _Float16 x = (_Float16)v;
-            hi[e] = x;
-            lo[e] = (_Float16)(v - (float)x);
-        } else {
-            hi[e] = __builtin_bit_cast(_Float16, (__bf16)v);
-        }
-    }
-    if (nt == 3) {
-        h8* dst = reinterpret_cast<h8*>(pack + X3_HDR) + ((long)t * G.HBT + hb) * 128 + lane;
-        dst[0] = hi;
-        dst[64] = lo;
-    } else {
-        reinterpret_cast<h8*>(pack + X3_HDR)[((long)t * G.HBT + hb) * 64 + lane] = hi;
-    }
-}
-
 __global__ void x3_bwx_pack_sym_kernel(const float* __restrict__ W, int H, int m, X3BwxGeom G, long total, int nparts,
                                        const float* __restrict__ hdr, float* __restrict__ pack, int nt) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -372,70 +196,8 @@ __global__ void x3_bwx_pack_kernel(const float* __restrict__ W, int H, int Hp, i
 }
 
 // ---- all levels, both directions, in two launches (the packs depend on the weights only) ----------------------
-#define X3_MAXJOBS 8
-struct X3PackJobs {
-    const float* W[X3_MAXJOBS];
-    float* fwd[X3_MAXJOBS];
-    float* bwd[X3_MAXJOBS];
-    float* fsym[X3_MAXJOBS];                 // folded forward pack of a level with Hp == m (null otherwise)
-    float* bsym[X3_MAXJOBS];                 // folded dX pack, likewise
-    int H[X3_MAXJOBS], Hp[X3_MAXJOBS], m[X3_MAXJOBS], nparts[X3_MAXJOBS];
-    long nW[X3_MAXJOBS], fthreads[X3_MAXJOBS], bthreads[X3_MAXJOBS], sthreads[X3_MAXJOBS], bsthreads[X3_MAXJOBS];
-    int nt;
-    X3Geom fg[X3_MAXJOBS], sg[X3_MAXJOBS];
-    X3BwxGeom bg[X3_MAXJOBS];
-};
-
-__global__ __launch_bounds__(1024) void x3_absmax_multi_kernel(const X3PackJobs J) {
-    const int l = blockIdx.y;
-    if ((int)blockIdx.x >= J.nparts[l]) return;
-    __shared__ float red[16];
-    const float* __restrict__ W = J.W[l];
-    const long total = J.nW[l], nv = total >> 2;
-    const long stride = (long)J.nparts[l] * blockDim.x;
-    float v = 0.f;
-    const bool vec = (((size_t)W) & 15) == 0;
-    if (vec) {
-        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
-            const float4 a = reinterpret_cast<const float4*>(W)[i];
-            v = fmaxf(fmaxf(v, fmaxf(fabsf(a.x), fabsf(a.y))), fmaxf(fabsf(a.z), fabsf(a.w)));
-        }
-    }
-    for (long i = (vec ? nv * 4 : 0) + (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) v = fmaxf(v, fabsf(W[i]));
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x < 16) {
-        v = red[threadIdx.x];
-        for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-        if (threadIdx.x == 0) {
-            if (J.fwd[l]) J.fwd[l][X3_HDR_PART + blockIdx.x] = v;
-            if (J.bwd[l]) J.bwd[l][X3_HDR_PART + blockIdx.x] = v;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void x3_pack_multi_kernel(const X3PackJobs J) {
-    const int l = blockIdx.y >> 2, dir = blockIdx.y & 3;
-    const long stride = (long)gridDim.x * blockDim.x;
-    if (dir == 3) {
-        if (!J.bsym[l]) return;
-        for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < J.bsthreads[l]; idx += stride)
-            x3_bwx_pack_sym_one(J.W[l], J.H[l], J.m[l], J.bg[l], J.nparts[l], J.bwd[l], J.bsym[l], idx, J.nt);
-    } else if (dir == 2) {
-        if (!J.fsym[l]) return;
-        for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < J.sthreads[l]; idx += stride)
-            x3_fwd_pack_sym_one(J.W[l], J.H[l], J.m[l], J.sg[l], J.nparts[l], J.fwd[l], J.fsym[l], idx, J.nt);
-    } else if (dir == 0) {
-        if (!J.fwd[l]) return;
-        for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < J.fthreads[l]; idx += stride)
-            x3_fwd_pack_one(J.W[l], J.H[l], J.Hp[l], J.m[l], J.fg[l], J.nparts[l], J.fwd[l], idx, J.nt);
-    } else {
-        if (!J.bwd[l]) return;
-        for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < J.bthreads[l]; idx += stride)
-            x3_bwx_pack_one(J.W[l], J.H[l], J.Hp[l], J.m[l], J.bg[l], J.nparts[l], J.bwd[l], idx, J.nt);
-    }
-}
+__global__ __launch_bounds__(1024) void x3_absmax_multi_kernel(const X3PackJobs J) { x3_absmax_part(J, blockIdx.y, blockIdx.x); }
+__global__ __launch_bounds__(256) void x3_pack_multi_kernel(const X3PackJobs J) { x3_pack_block(J, blockIdx.x, blockIdx.y, gridDim.x); }
 
 template <int HBT, int NW, int NT = 3>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void cin_bwd_x3_kernel(
@@ -765,8 +527,7 @@ int x3_level_bwd_x(const X3DoutSrc& dOut, const float* xp, const float* x0, cons
 // every level through the f16x3 kernels in both directions?  (then xdfm_cin_pack_all can prepare a whole step)
 bool x3_pack_all_usable(int H, int Hp, int m) { return x3_fwd_usable(H, Hp, m) && x3_bwx_usable(H, Hp, m); }
 
-int x3_pack_all(const xdfm_cin_pack_job* jobs, int L, hipStream_t st) {
-    X3PackJobs J;
+static void x3_pack_jobs(const xdfm_cin_pack_job* jobs, int L, X3PackJobs& J) {
     long maxthreads = 0;
     int maxparts = 0;
     for (int l = 0; l < X3_MAXJOBS; ++l) {
@@ -792,9 +553,62 @@ int x3_pack_all(const xdfm_cin_pack_job* jobs, int L, hipStream_t st) {
         }
     }
     J.nt = x3_terms();
-    if (J.nt == 3) hipLaunchKernelGGL(x3_absmax_multi_kernel, dim3(maxparts, L), dim3(1024), 0, st, J);
     int gx = ceil_div(maxthreads, 256);
     if (gx > 1024) gx = 1024;
-    hipLaunchKernelGGL(x3_pack_multi_kernel, dim3(gx, 4 * L), dim3(256), 0, st, J);
+    J.L = L; J.maxparts = maxparts; J.gx = gx;
+}
+static void x3_pack_launch_absmax(const X3PackJobs& J, hipStream_t st) {
+    hipLaunchKernelGGL(x3_absmax_multi_kernel, dim3(J.maxparts, J.L), dim3(1024), 0, st, J);
+}
+static void x3_pack_launch_pack(const X3PackJobs& J, hipStream_t st) {
+    hipLaunchKernelGGL(x3_pack_multi_kernel, dim3(J.gx, 4 * J.L), dim3(256), 0, st, J);
+}
+
+int x3_pack_all(const xdfm_cin_pack_job* jobs, int L, hipStream_t st) {
+    X3PackJobs J;
+    x3_pack_jobs(jobs, L, J);
+    if (J.nt == 3) x3_pack_launch_absmax(J, st);
+    x3_pack_launch_pack(J, st);
     return xdfm_check_launch("cin_pack_all");
+}
+
+// Deferred packs (xdfm_cin_pack_defer): what is still to be issued -- 1 = the maxima and the packs, 2 = the packs -- for the
+// hosts that carry them as riders (x3_pack_take_*) or for x3_pack_flush
+static struct { int stage; hipStream_t st; X3PackJobs J; } g_pack = {0, nullptr, {}};
+
+int x3_pack_flush(hipStream_t st) {
+    if (g_pack.stage == 0) return XDFM_OK;
+    const int stage = g_pack.stage;
+    g_pack.stage = 0;
+    if (st != g_pack.st) return xdfm_fail(XDFM_ERR_INVALID, "cin_pack_flush: stream %p, the packs were deferred on stream %p (dropped)", (void*)st, (void*)g_pack.st);
+    if (stage == 1) x3_pack_launch_absmax(g_pack.J, st);
+    x3_pack_launch_pack(g_pack.J, st);
+    return xdfm_check_launch("cin_pack_flush");
+}
+int x3_pack_pending() { return g_pack.stage; }
+
+int x3_pack_defer(const xdfm_cin_pack_job* jobs, int L, hipStream_t st) {
+    if (g_pack.stage != 0)
+        if (int rc = x3_pack_flush(g_pack.st)) return rc;      // an earlier announcement nobody used
+    if (!(xdfm_opt(OPT_COLAUNCH) & 2)) return x3_pack_all(jobs, L, st);
+    x3_pack_jobs(jobs, L, g_pack.J);
+    g_pack.st = st;
+    g_pack.stage = g_pack.J.nt == 3 ? 1 : 2;
+    return XDFM_OK;
+}
+
+long x3_pack_take_absmax(hipStream_t st, X3PackJobs* out) {
+    if (g_pack.stage != 1 || g_pack.st != st) return 0;
+    *out = g_pack.J;
+    g_pack.stage = 2;
+    xdfm_opt_note(OPT_LAST_PACK_RIDERS, xdfm_opt(OPT_LAST_PACK_RIDERS) | 1);
+    return (long)g_pack.J.maxparts * g_pack.J.L;
+}
+long x3_pack_take_pack(hipStream_t st, X3PackJobs* out) {
+    if (g_pack.stage == 0 || g_pack.st != st) return 0;
+    if (g_pack.stage == 1) x3_pack_launch_absmax(g_pack.J, st);     // no catch-up carried the maxima: their own launch, in front
+    *out = g_pack.J;
+    g_pack.stage = 0;
+    xdfm_opt_note(OPT_LAST_PACK_RIDERS, xdfm_opt(OPT_LAST_PACK_RIDERS) | 2);
+    return (long)g_pack.J.gx * 4 * g_pack.J.L;
 }

@@ -14,6 +14,7 @@
 // removes its split's scales from the accumulators before it stores its slab).  The stand-alone entry point
 // (xdfm_cin_level_bwd_w on a dOut that somebody else produced) keeps passes 1 and 2 with one header for all splits.
 #include "xdfm_internal.h"
+#include "rider.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));      // 16 bytes of MFMA operand (fp16 halves, or bf16 bit patterns)
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -440,57 +441,17 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void cin_bwd_w_x3_kernel(
         }
 }
 
-// dW[h][i*m+j] = sum over n-splits of dWt[split][j][h][i], in split order (the kernel removed each split's scales)
+// the ordered slab sums (bodies: rider.h, where they are shared with the launches that carry them as riders)
 __global__ void x3_bww_unpack_kernel(const float* __restrict__ dWt, int H, int Hp, int m,
                                      int Hpad, int IPAD, int nslab, long slab_stride, float* __restrict__ dW) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    const long total = (long)m * Hpad * IPAD;
-    if (idx >= total) return;
-    const int i = (int)(idx % IPAD);
-    const long jh = idx / IPAD;
-    const int h = (int)(jh % Hpad), j = (int)(jh / Hpad);
-    if (i >= Hp || h >= H) return;
-    float acc = 0.f;
-    int k = 0;
-    for (; k + 8 <= nslab; k += 8) {                    // 8 slab loads in flight; the sum keeps its fixed order
-        float t[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) t[q] = dWt[(long)(k + q) * slab_stride + idx];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += t[q];
-    }
-    for (; k < nslab; ++k) acc += dWt[(long)k * slab_stride + idx];
-    dW[(long)h * ((long)Hp * m) + (long)i * m + j] = acc;
+    x3_bww_unpack_one(dWt, H, Hp, m, Hpad, IPAD, nslab, slab_stride, dW, (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
-
-// folded level 0: dW[h][i*m+j] = dW[h][j*m+i] = sum over n-splits of slab[split][t][h][r], (i, j) the pair of lane r in
-// combined tile t.  One thread per slab element (coalesced reads of every split), two 4-byte stores.
 __global__ void x3_bww_unpack_sym_kernel(const float* __restrict__ dWt, int H, int m,
                                          int Hpad, int nslab, long slab_stride, float* __restrict__ dW) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)(m / 2) * Hpad * 32) return;
-    const int r = (int)(idx & 31);
-    const int h = (int)((idx >> 5) % Hpad), t = (int)((idx >> 5) / Hpad);
-    int i, j;
-    if (r <= t) { i = r; j = t; }
-    else if (31 - r <= m - 1 - t) { i = 31 - r; j = m - 1 - t; }
-    else return;
-    if (h >= H) return;
-    float acc = 0.f;
-    int k = 0;
-    for (; k + 8 <= nslab; k += 8) {                    // 8 slab loads in flight; the sum keeps its fixed order
-        float v[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = dWt[(long)(k + q) * slab_stride + idx];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc += v[q];
-    }
-    for (; k < nslab; ++k) acc += dWt[(long)k * slab_stride + idx];
-    const float v = acc;
-    float* __restrict__ row = dW + (long)h * ((long)m * m);
-    row[i * m + j] = v;
-    if (i != j) row[j * m + i] = v;
+    x3_bww_unpack_sym_one(dWt, H, m, Hpad, nslab, slab_stride, dW, (long)blockIdx.x * blockDim.x + threadIdx.x);
 }
+static_assert(sizeof(X3UnpackRiders) + 512 <= 8192, "x3_bwd_prep_kernel's argument block");
+__global__ __launch_bounds__(256) void x3_unpack_rider_kernel(const X3UnpackRiders R) { x3_unpack_rider(R, (long)blockIdx.x); }
 
 // ---------------------------------------------------------------------------------------------
 static inline int x3_bww_waves() { return xdfm_opt(OPT_X3_WAVES) == 4 ? 4 : 8; }
@@ -586,7 +547,9 @@ __global__ __launch_bounds__(256) void x3_bwd_prep_kernel(
     const float* __restrict__ dDir, int dir_mode, long lddir, int dir_off, int dir0, int dir_rows,
     float* __restrict__ dOut, float* __restrict__ slots,
     const float* __restrict__ xp, const float* __restrict__ x0, int Hp, int m, int Hpad, int IPAD,
-    int n_per_split, X3Magic divS, int KS, int nsplit, float* __restrict__ hdr2, long HS, char* __restrict__ planes, long NP) {
+    int n_per_split, X3Magic divS, int KS, int nsplit, float* __restrict__ hdr2, long HS, char* __restrict__ planes, long NP,
+    int own_y, const X3UnpackRiders riders) {
+    if ((int)blockIdx.y >= own_y) { x3_unpack_rider(riders, (long)((int)blockIdx.y - own_y) * gridDim.x + blockIdx.x); return; }
     __shared__ unsigned seg_max[X3_PREP_COLS / 32 + 1];
     __shared__ float wsum[4];
     const int y = blockIdx.y;
@@ -813,6 +776,50 @@ static BwwGeom x3_bww_launch_geometry(const float* xp, const float* x0, int H, i
     return *sym ? x3_bww_geometry_sym(H, m, N, NW) : x3_bww_geometry(H, Hp, m, N, NW);
 }
 
+// The riders recorded since xdfm_rider_begin (one scope at a time per process, as the finish batch)
+static struct { bool open; hipStream_t st; X3UnpackRiders r; } g_riders = {false, nullptr, {}};
+static long x3_riders_blocks(int threads) {
+    long b = 0;
+    for (int k = 0; k < g_riders.r.n; ++k) b += ceil_div(g_riders.r.j[k].slab_stride, (long)threads);
+    return b;
+}
+// what nobody carried, as one launch of its own
+static int x3_riders_launch(hipStream_t st) {
+    if (g_riders.r.n > 0) {
+        hipLaunchKernelGGL(x3_unpack_rider_kernel, dim3((unsigned)x3_riders_blocks(256)), dim3(256), 0, st, g_riders.r);
+        g_riders.r.n = 0;
+        return xdfm_check_launch("rider_flush");
+    }
+    return XDFM_OK;
+}
+long x3_riders_take(hipStream_t st, int threads, long max_blocks, X3UnpackRiders* out) {
+    out->n = 0;
+    xdfm_opt_note(OPT_LAST_RIDERS, 0);
+    if (g_riders.r.n == 0 || g_riders.st != st) return 0;
+    const long blocks = x3_riders_blocks(threads);
+    if (blocks > max_blocks) return 0;
+    *out = g_riders.r;
+    g_riders.r.n = 0;
+    xdfm_opt_note(OPT_LAST_RIDERS, out->n);
+    return blocks;
+}
+extern "C" int xdfm_rider_begin(void) {
+    if (g_riders.open || g_riders.r.n) return xdfm_fail(XDFM_ERR_INVALID, "rider_begin: a scope is open already (xdfm_rider_flush closes it)");
+    g_riders.open = (xdfm_opt(OPT_COLAUNCH) & 4) != 0;  // bit clear: nothing is recorded, every launch stays where it was
+    g_riders.st = nullptr;
+    return XDFM_OK;
+}
+extern "C" int xdfm_rider_pending(void) { return g_riders.r.n; }
+extern "C" int xdfm_rider_active(void) { return g_riders.open ? 1 : 0; }
+extern "C" int xdfm_rider_flush(void* stream) {
+    g_riders.open = false;
+    if (g_riders.r.n && g_riders.st != (hipStream_t)stream) {
+        g_riders.r.n = 0;
+        return xdfm_fail(XDFM_ERR_INVALID, "rider_flush: stream %p, the jobs were recorded on stream %p (dropped)", stream, (void*)g_riders.st);
+    }
+    return x3_riders_launch((hipStream_t)stream);
+}
+
 // cin_dout + the dW kernel's operands (see x3_bwd_prep_kernel).  slots: H * x3_bwd_prep_slots() floats of dbias partials
 // (the caller adds them up in block order).  ws: the dW workspace.
 int x3_bwd_prep_blocks(bool xp_is_x0, int H, int Hp, int m, long N) {
@@ -833,18 +840,24 @@ int x3_bwd_prep(const float* A, const unsigned* mask, long mask_ld, int H, long 
     float* hdr2 = ws;
     char* planes = reinterpret_cast<char*>(ws + w.hdr + w.parts);
     const int KS = g.n_per_split >= X3_PREP_COLS ? 1 : (int)(X3_PREP_COLS / g.n_per_split);
-    const dim3 grid(ceil_div(g.nsplit, KS), g.Hpad + g.IPAD + m);
+    dim3 grid(ceil_div(g.nsplit, KS), g.Hpad + g.IPAD + m);
     XDFM_REQUIRE(grid.y <= 65535, "cin_bwd_prep: %d header rows", (int)grid.y);
     XDFM_REQUIRE(N < (1L << 31) && g.n_per_split < (1L << 30), "cin_bwd_prep: N = %ld columns", N);
     const X3Magic divD = x3_magic(D), divS = x3_magic(g.n_per_split);
+    // riders: the slab sums recorded on this stream run in workgroup rows behind the pre-pass's own (a table that would
+    // not fit the grid stays recorded, for a later host or the flush)
+    const int own_y = (int)grid.y;
+    X3UnpackRiders riders = {};
+    const long rblocks = x3_riders_take(st, 256, (long)(65535 - own_y) * grid.x, &riders);
+    grid.y = (unsigned)(own_y + ceil_div(rblocks, (long)grid.x));
     if (x3_terms() == 3)
         hipLaunchKernelGGL(x3_bwd_prep_kernel<3>, grid, dim3(256), 0, st, A, mask, mask_ld, H, N, divD, act, dHid, hid0, hid_rows, dDir, dir_mode, lddir,
                            dir_off, dir0, dir_rows, dOut, slots, xp, x0, Hp, m, g.Hpad, g.IPAD, (int)g.n_per_split, divS, KS, g.nsplit, hdr2,
-                           w.HS, planes, w.NP);
+                           w.HS, planes, w.NP, own_y, riders);
     else
         hipLaunchKernelGGL(x3_bwd_prep_kernel<1>, grid, dim3(256), 0, st, A, mask, mask_ld, H, N, divD, act, dHid, hid0, hid_rows, dDir, dir_mode, lddir,
                            dir_off, dir0, dir_rows, dOut, slots, xp, x0, Hp, m, g.Hpad, g.IPAD, (int)g.n_per_split, divS, KS, g.nsplit, hdr2,
-                           w.HS, planes, w.NP);
+                           w.HS, planes, w.NP, own_y, riders);
     return xdfm_check_launch("cin_bwd_prep (f16x3 / bf16)");
 }
 
@@ -906,7 +919,11 @@ int x3_level_bwd_w(const float* dOut, const float* xp, const float* x0, int H, i
     rc = xdfm_check_launch("cin_level_bwd_w (f16x3)");
     if (rc) return rc;
     }
-    if ((phase == 0 || phase == 3) && sym) {
+    if (phase == 0 && g_riders.open && g_riders.r.n < X3_RIDERS && (g_riders.r.n == 0 || g_riders.st == st)) {
+    // inside a rider scope: recorded, for the next host launch on this stream (or xdfm_rider_flush) to carry
+    g_riders.st = st;
+    g_riders.r.j[g_riders.r.n++] = X3UnpackJob{slabs, dW, g.slab, H, Hp, m, g.Hpad, g.IPAD, g.nsplit, sym ? 1 : 0};
+    } else if ((phase == 0 || phase == 3) && sym) {
     hipLaunchKernelGGL(x3_bww_unpack_sym_kernel, dim3(ceil_div(g.slab, 256)), dim3(256), 0, st, slabs, H, m,
                        g.Hpad, g.nsplit, g.slab, dW);
     rc = xdfm_check_launch("cin_level_bwd_w unpack (folded level 0)");

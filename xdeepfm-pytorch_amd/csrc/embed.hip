@@ -11,6 +11,8 @@
 //            --> emb_fm[j][b0*D .. (b0+EB)*D)  contiguous EB*D floats per field   (FM layout)
 // so both outputs are written in long contiguous runs although the rows arrive in id order.
 #include "xdfm_internal.h"
+#include "cin_x3_pack.h"   // the gather carries the CIN weight packs as a rider
+#include "rider.h"           // the scatter carries the dW slab sum of CIN level 0 as a rider
 
 #define EMB_THREADS 256
 
@@ -24,7 +26,10 @@ __global__ __launch_bounds__(EMB_THREADS) void embed_gather_kernel(
     const float* const* __restrict__ lin_tables, const int* __restrict__ cols, const int* __restrict__ vocab,
     int m, int D, const int* __restrict__ dense_cols, const float* __restrict__ dense_w, int nd, int EB,
     float* __restrict__ emb_fm, float* __restrict__ dnn_in, long ldd, int dense_off, float* __restrict__ lin_out,
-    int* __restrict__ err_flag) {
+    int* __restrict__ err_flag, int own_blocks, const X3PackJobs riders) {
+    // workgroups past the gather's own run a rider and return: the CIN weight packs (cin_x3_pack.h), which depend on the
+    // weights only and which the first CIN level reads behind this launch
+    if ((int)blockIdx.x >= own_blocks) { x3_pack_rider(riders, (long)((int)blockIdx.x - own_blocks)); return; }
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* tile = smem;                                                    // [EB][m][D]
     float* linv = smem + (size_t)EB * m * D;                               // [EB][m]
@@ -184,6 +189,7 @@ __global__ __launch_bounds__(EMB_THREADS) void embed_gather_kernel(
 #define SC_ROWS 4096          // examples per chunk = SC_THREADS windows of SC_W
 #define SC_W 8                // list positions per window
 #define SC_SW 4               // embedding columns per workgroup slice (one float4 per row and lane)
+#define SC_RIDER_BLOCKS 512   // most rider workgroups a scatter launch carries: about two rounds at one workgroup per CU (see the take)
 #define SC_NC 4               // components per lane (a linear-table workgroup uses component 0 only)
 #define SC_EMPTY 0xffffffffu
 
@@ -205,6 +211,7 @@ __host__ __device__ inline size_t sc_lds_bytes(int npad) {
            (size_t)npad * 4 * sizeof(float);                   // + the staged row pieces [npad][4]
 }
 
+static_assert(sizeof(X3UnpackRiders) + 512 <= 8192, "embed_scatter_grouped_kernel's argument block");
 template <int VEC>
 __global__ __launch_bounds__(SC_THREADS) void embed_scatter_grouped_kernel(
     const float* __restrict__ X, long ldx, int b0, int nb, long Btot, const int* __restrict__ cols,
@@ -212,7 +219,10 @@ __global__ __launch_bounds__(SC_THREADS) void embed_scatter_grouped_kernel(
     const float* __restrict__ d_dnn_in, long ld_dnn, const float* __restrict__ d_lin, long ld_lin,
     float* __restrict__ d_flat, const long* __restrict__ tab_off, const long* __restrict__ lin_off,
     unsigned char* __restrict__ marks, int npad, int nlin, const int* __restrict__ dense_cols, int nd,
-    float* __restrict__ d_dense_w, long dense_mark_base, int dbg) {
+    float* __restrict__ d_dense_w, long dense_mark_base, int dbg, int own_blocks, const X3UnpackRiders riders) {
+    // workgroups past the scatter's own run a rider (rider.h) and return: the scatter's 143 workgroups of the Criteo step
+    // leave 113 CUs idle, each of its workgroups holding a CU's LDS
+    if ((int)blockIdx.x >= own_blocks) { x3_unpack_rider(riders, (long)((int)blockIdx.x - own_blocks)); return; }
     // dbg: timing experiments only (xdfm option "dbg" bits 12..16; results become wrong): 1 = no grouping,
     // 2 = no row loads, 4 = no read-modify-writes, 8 = no cross-window phases, 16 = ids without reading X
     extern __shared__ __attribute__((aligned(16))) char sc_smem[];
@@ -685,9 +695,15 @@ int xdfm_embed_gather_fwd_ld(const float* X, long ldx, int B, const float* const
     XDFM_REQUIRE(EB <= EMB_THREADS, "embed_gather_fwd: internal");
     dim3 grid(ceil_div(B, EB));
     hipStream_t st = (hipStream_t)stream;
+    // rider: deferred CIN weight packs (xdfm_cin_pack_defer) go out as workgroups behind the gather's own
+    static_assert(EMB_THREADS == 256, "the pack bodies' grid is counted in 256-thread workgroups");
+    const int own_blocks = (int)grid.x;
+    X3PackJobs riders = {};
+    grid.x += (unsigned)x3_pack_take_pack(st, &riders);
 #define LAUNCH(V)                                                                                              \
     hipLaunchKernelGGL((embed_gather_kernel<V>), grid, dim3(EMB_THREADS), lds, st, X, ldx, B, tables, lin_tables, \
-                       cols, vocab, m, D, dense_cols, dense_w, nd, EB, emb_fm, dnn_in, ld_dnn, dense_off, lin_out, err_flag)
+                       cols, vocab, m, D, dense_cols, dense_w, nd, EB, emb_fm, dnn_in, ld_dnn, dense_off, lin_out, err_flag, \
+                       own_blocks, riders)
     if (D % 4 == 0) LAUNCH(4);
     else if (D % 2 == 0) LAUNCH(2);
     else LAUNCH(1);
@@ -734,17 +750,24 @@ int xdfm_embed_scatter_bwd_marked(const float* X, long ldx, int B, const int* co
         int npad = 8;
         while (npad < nb) npad <<= 1;
         const size_t lds = sc_lds_bytes(npad);
-        const dim3 grid(m * nslice + nlin + (dense ? nd : 0));
+        dim3 grid(m * nslice + nlin + (dense ? nd : 0));
+        // riders: recorded slab sums of the CIN backward run in workgroups behind the first chunk's own.  Every workgroup of
+        // this launch holds a CU's LDS, riders included (they use none), so they run one to a CU; SC_RIDER_BLOCKS bounds them
+        // to about two rounds on the chip, the second of which runs behind the scatter's own workgroups, not beside them.  A
+        // longer table stays recorded.
+        const int own_blocks = (int)grid.x;
+        X3UnpackRiders riders = {};
+        if (b0 == 0) grid.x += (unsigned)x3_riders_take(st, SC_THREADS, SC_RIDER_BLOCKS, &riders);
         const long mark_base = marks && dense ? (long)(d_dense_w - d_flat) : 0L;
         const int dbg = (xdfm_opt(OPT_DBG) >> 12) & 31;
         if (vec4)
             hipLaunchKernelGGL((embed_scatter_grouped_kernel<4>), grid, dim3(SC_THREADS), lds, st, X, ldx, (int)b0, nb, (long)B,
                                cols, vocab, m, D, nslice, d_emb_fm, d_dnn_in, ld_dnn, d_lin, ld_lin, d_flat, tab_off, lin_off,
-                               marks, npad, nlin, dense_cols, dense ? nd : 0, d_dense_w, mark_base, dbg);
+                               marks, npad, nlin, dense_cols, dense ? nd : 0, d_dense_w, mark_base, dbg, own_blocks, riders);
         else
             hipLaunchKernelGGL((embed_scatter_grouped_kernel<1>), grid, dim3(SC_THREADS), lds, st, X, ldx, (int)b0, nb, (long)B,
                                cols, vocab, m, D, nslice, d_emb_fm, d_dnn_in, ld_dnn, d_lin, ld_lin, d_flat, tab_off, lin_off,
-                               marks, npad, nlin, dense_cols, dense ? nd : 0, d_dense_w, mark_base, dbg);
+                               marks, npad, nlin, dense_cols, dense ? nd : 0, d_dense_w, mark_base, dbg, own_blocks, riders);
         const int rc = xdfm_check_launch("embed_scatter_bwd");
         if (rc) return rc;
     }

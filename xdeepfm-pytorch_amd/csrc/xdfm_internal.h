@@ -43,6 +43,14 @@ enum {
     OPT_OPT_BX,          // 0 = default (512 / 512 / 4096: OPT_BX, OPTD_BX, OPTD_FLUSH_BX); most blocks one tensor gets in the
                          //   SGD / Adagrad / RMSprop sweep, deferred step scan and flush
     OPT_FINISH_BATCH,    // 1 (default) = xdfm_finish_batch_begin opens a batch; 0 = it opens none and every finish stays its own launch
+    OPT_COLAUNCH,        // bit mask, default 5: bodies that do not depend on each other leave as workgroup ranges of ONE launch.
+                         //   bit 0 = xdfm_colaunch_adam_step: the step and the rows update; bit 2 = inside xdfm_rider_begin / _flush the
+                         //   dW slab sum of a CIN level rides on the next level's pre-pass (bit 1 is not in use).  0 = every body in
+                         //   the launch it had before.  Same bits either way
+    OPT_LAST_COLAUNCH,   // read-only probe: 1 / 0 = the last xdfm_colaunch_adam_step issued the shared launch / the two, -1 before
+    OPT_LAST_RIDERS,     // read-only probe: slab sums the last rider host launch (pre-pass, scatter) took (0: none), -1 before the first
+    OPT_LAST_PACK_RIDERS,// read-only probe, reset by xdfm_cin_pack_defer: bit 0 = a catch-up carried the deferred |W| maxima, bit 1 = a
+                         //   gather carried the packs (0: both left in launches of their own), -1 before the first
     OPT_COUNT
 };
 // value of the instance probes: row tiles (forward MT, dX HBT, dW MT) * 1000 + waves * 100 + MFMA terms * 10 + folded level 0
@@ -291,6 +299,9 @@ int x3_bwd_prep(const float* A, const unsigned* mask, long mask_ld, int H, long 
 
 bool x3_pack_all_usable(int H, int Hp, int m);
 int x3_pack_all(const xdfm_cin_pack_job* jobs, int L, hipStream_t st);
+int x3_pack_defer(const xdfm_cin_pack_job* jobs, int L, hipStream_t st);     // cin_x3.hip: deferred packs, see cin_x3_pack.h
+int x3_pack_flush(hipStream_t st);
+int x3_pack_pending();
 
 // LDS-DMA (global_load_lds) issued as inline assembly.  Through the builtin, hipcc books the instruction on vmcnt AND on
 // lgkmcnt ("flat access that may touch LDS") and, while one is pending -- always, with a ring kept several stages ahead --

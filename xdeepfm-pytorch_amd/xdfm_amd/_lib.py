@@ -27,6 +27,10 @@ SIGNATURES = {
     "xdfm_finish_batch_begin": (c_int, []),
     "xdfm_finish_batch_run": (c_int, [P]),
     "xdfm_finish_batch_active": (c_int, []),
+    "xdfm_rider_begin": (c_int, []),
+    "xdfm_rider_flush": (c_int, [P]),
+    "xdfm_rider_pending": (c_int, []),
+    "xdfm_rider_active": (c_int, []),
     "xdfm_finish": (c_int, [c_int, P, P, P, P, P, c_long, c_long, c_int, c_int, P]),
     "xdfm_embed_gather_fwd": (c_int, [P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, c_int, P, P, P, P, P]),
     "xdfm_embed_gather_fwd_ld": (c_int, [P, c_long, c_int, P, P, P, P, c_int, c_int, P, P, c_int, P, P, c_long, c_int, P, P, P]),
@@ -43,6 +47,9 @@ SIGNATURES = {
     "xdfm_cin_fwd_pack": (c_int, [P, c_int, c_int, c_int, P, P]),
     "xdfm_cin_pack_all_supported": (c_int, [c_int, c_int, c_int]),
     "xdfm_cin_pack_all": (c_int, [P, c_int, P]),
+    "xdfm_cin_pack_defer": (c_int, [P, c_int, P]),
+    "xdfm_cin_pack_flush": (c_int, [P]),
+    "xdfm_cin_pack_pending": (c_int, []),
     "xdfm_cin_level_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_long, c_int, P, P]),
     "xdfm_cin_direct_sum": (c_int, [P, c_int, c_int, c_int, c_int, P, c_long, c_int, P]),
     "xdfm_cin_dout": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, c_int, c_long, c_int, c_int,
@@ -88,6 +95,8 @@ SIGNATURES = {
     "xdfm_adam_step_deferred": (c_int, [P, c_int, P, c_double, P, c_double, c_double, c_double, P, P, P]),
     "xdfm_adam_catchup_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, c_double, c_double, P, P]),
     "xdfm_adam_apply_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, c_double, c_double, P, P, P]),
+    "xdfm_colaunch_adam_step": (c_int, [P, c_int, P, c_double, P, c_double, c_double, c_double, P, P,
+                                        P, c_long, c_int, P, P, c_int, c_int, P, P, P, P]),
     "xdfm_adam_flush": (c_int, [P, c_int, P, c_double, c_double, c_double, P, P]),
     "xdfm_adam_selftest": (c_int, [c_int, ctypes.c_ulonglong, ctypes.c_ulonglong, c_double, c_double, c_double, c_double, P, P]),
     "xdfm_opt_step_ws_elems": (c_size_t, [c_int]),

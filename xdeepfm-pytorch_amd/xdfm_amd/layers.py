@@ -47,6 +47,10 @@ class _CINBase(nn.Module):
         return ops.cin_stack(x0_fm, B, D, self.layer_size, self.split_half, self.activation, pool,
                              [c.weight for c in self.conv1ds], [c.bias for c in self.conv1ds])
 
+    def announce_pack(self):
+        """Before the step's embedding gather: this stack's weight packs may ride on it (ops.cin_announce_pack)."""
+        ops.cin_announce_pack([c.weight for c in self.conv1ds], self.field_nums[0], self.layer_size, self.split_half)
+
     @staticmethod
     def _check3d(inputs):
         if len(inputs.shape) != 3:

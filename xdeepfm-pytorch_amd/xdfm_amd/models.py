@@ -666,13 +666,21 @@ class BaseModel(nn.Module):
         the step's last line; a further term (aux_loss, `_step_extra`) is added to it on the device, so the batch runs first."""
         ops.finish_batch_begin()
         try:
+            cin = getattr(self, "cin", None)
+            if getattr(self, "use_cin", False) and x.is_cuda and hasattr(cin, "announce_pack"):
+                cin.announce_pack()                     # the CIN weight packs ride on the catch-up and the gather
             y_pred, loss = self._loss_forward(x, y) if sw is None else self._loss_forward(x, y, sw)
+            ops.cin_pack_drop()                         # (no CIN forward took them: issued all the same)
             self.optim.arm_l2(*fuse)
             if not self._aux_unset or self.__dict__.get("_step_extra") is not None:
                 ops.finish_batch_flush()
             total_loss = loss if self._aux_unset else loss + self.aux_loss
             total_loss = self._with_step_extra(total_loss)
+            # the dW slab sums of the CIN levels ride on later launches of the backward; until the flush nothing may read a CIN
+            # weight gradient (zero_grad left `.grad` None: no accumulation kernel, no hooks here) -- see ops.rider_begin
+            ops.rider_begin()
             total_loss.backward(self._unit_grad(total_loss))
+            ops.rider_flush()
             ops.finish_batch_run()
             if dp is not None:
                 dp.reduce_dense_grads(self)
@@ -684,6 +692,8 @@ class BaseModel(nn.Module):
                 total_loss = ops.finish_add(a, l2)      # behind the finish that leaves the value, in the optimizer's batch
             ops.finish_batch_run()
         except BaseException:
+            ops.cin_pack_drop(quiet=True)
+            ops.rider_flush(quiet=True)
             ops.finish_batch_run(quiet=True)
             raise
         return y_pred.detach(), loss.detach(), total_loss.detach()

@@ -67,11 +67,41 @@ def finish_batch_run(quiet=False):
         rc = _lib.load().xdfm_finish_batch_run(_stream())
         if not quiet:
             _lib.check(rc, "finish_batch_run")
+            assert _lib.load().xdfm_rider_pending() == 0, "a rider job is pending at the end of a finish batch"
     except Exception:            # noqa: BLE001
         if not quiet:
             raise
     finally:
         _FINISH_OPEN, _FINISH_KEEP = False, None
+
+
+# Rider scope (include/xdfm.h, xdfm_rider_begin; option "colaunch" bit 2): around the model's own backward the ordered sum of
+# a CIN level's dW slabs is not launched by its dW call but rides on a later launch of the backward -- the next level's
+# pre-pass, the embedding scatter behind level 0 -- and rider_flush issues what nobody carried.  The dW workspaces (they hold
+# the slabs) of a scope stay alive until its flush.
+_RIDER_KEEP = None               # list while a scope is open and records (option bit set), else None
+
+
+def rider_begin():
+    """Inside the scope a recorded level's dW is returned by CINStack.backward BEFORE the launch that writes it is issued (the
+    carrying launch or rider_flush does that).  Nothing may read it until the flush: no tensor hook or retain_grad on a CIN
+    weight, no accumulation into an existing `.grad` (the model's step leaves `.grad` None, so autograd only takes the
+    tensor over)."""
+    global _RIDER_KEEP
+    lib = _lib.load()
+    _lib.check(lib.xdfm_rider_begin(), "rider_begin")
+    _RIDER_KEEP = [] if lib.xdfm_rider_active() else None
+
+
+def rider_flush(quiet=False):
+    """Issues the recorded jobs that no launch carried and closes the scope (no-op without one); `quiet`: never raises."""
+    global _RIDER_KEEP
+    try:
+        rc = _lib.load().xdfm_rider_flush(_stream())
+        if not quiet:
+            _lib.check(rc, "rider_flush")
+    finally:
+        _RIDER_KEEP = None
 
 
 def finish_batch_flush():
@@ -651,6 +681,56 @@ def cin_lean_allowed(act: int) -> bool:
     return act != ACT_CODES["sigmoid"]
 
 
+_PACK_ANNOUNCED = None           # (key, forward packs, dX packs, weights) of cin_announce_pack until the forward that takes it
+
+
+def _cin_pack_key(W2s, levels, m):
+    return (tuple((w.data_ptr(), w._version) for w in W2s), tuple((H, Hp) for (H, Hp, *_r) in levels), m, _lib.get_option("cin_math"))
+
+
+def _cin_pack_jobs(lib, W2s, levels, m, need_bwd, dev):
+    """(job array, forward packs, dX packs) of xdfm_cin_pack_all / _defer for the levels' weights [H, Hp * m]."""
+    jobs = (_lib.PackJob * len(levels))()
+    wfs, wzs = [None] * len(levels), [None] * len(levels)
+    for l, (H, Hp, *_r) in enumerate(levels):
+        wfs[l] = torch.empty(lib.xdfm_cin_fwd_pack_elems(H, Hp, m), dtype=torch.float32, device=dev)
+        if need_bwd:
+            wzs[l] = torch.empty(lib.xdfm_cin_bwd_pack_elems(H, Hp, m), dtype=torch.float32, device=dev)
+        jobs[l].W, jobs[l].H, jobs[l].Hp, jobs[l].m = W2s[l].data_ptr(), H, Hp, m
+        jobs[l].fwd_pack = wfs[l].data_ptr()
+        jobs[l].bwd_pack = wzs[l].data_ptr() if need_bwd else None
+    return jobs, wfs, wzs
+
+
+def cin_announce_pack(weights, m, layer_size, split_half):
+    """The model's train step, before its embedding gather: the packs CINStack.forward would launch for these weights are
+    deferred (xdfm_cin_pack_defer; option "colaunch" bit 1), so that deferred Adam's catch-up carries the |W| maxima and the
+    gather the packs; CINStack.forward then takes the buffers and issues what nobody carried.  Nothing happens where the
+    forward would not pack all levels at once.  Pair with cin_pack_drop behind the forward."""
+    global _PACK_ANNOUNCED
+    cin_pack_drop()
+    lib = _lib.load()
+    levels, _ = cin_geometry(m, layer_size, split_half)
+    if not weights or not weights[0].is_cuda or len(levels) > 8 or \
+            not all(lib.xdfm_cin_pack_all_supported(H, Hp, m) for (H, Hp, *_r) in levels):
+        return
+    W2s = [w.detach().reshape(H, Hp * m).contiguous() for w, (H, Hp, *_r) in zip(weights, levels)]
+    jobs, wfs, wzs = _cin_pack_jobs(lib, W2s, levels, m, True, W2s[0].device)
+    _lib.check(lib.xdfm_cin_pack_defer(ctypes.cast(jobs, ctypes.c_void_p), len(levels), _stream()), "cin_pack_defer")
+    _PACK_ANNOUNCED = (_cin_pack_key(W2s, levels, m), wfs, wzs, W2s)
+
+
+def cin_pack_drop(quiet=False):
+    """An announcement no forward took: its packs are issued (the buffers may be in use by a captured graph) and forgotten."""
+    global _PACK_ANNOUNCED
+    if _PACK_ANNOUNCED is None:
+        return
+    _PACK_ANNOUNCED = None
+    rc = _lib.load().xdfm_cin_pack_flush(_stream())
+    if not quiet:
+        _lib.check(rc, "cin_pack_flush")
+
+
 class CINStack(torch.autograd.Function):
     """All CIN levels.  x0 is FM layout [m, B*D].
 
@@ -678,17 +758,17 @@ class CINStack(torch.autograd.Function):
             _need_cuda(params[2 * l], "cin weight")
             W2s.append(params[2 * l].reshape(H, Hp * m).contiguous())
         wfs, wzs = [None] * len(levels), None
-        if len(levels) <= 8 and all(lib.xdfm_cin_pack_all_supported(H, Hp, m) for (H, Hp, *_r) in levels):
+        global _PACK_ANNOUNCED
+        ann, _PACK_ANNOUNCED = _PACK_ANNOUNCED, None
+        if ann is not None:
+            # packs announced before the gather (cin_announce_pack): the catch-up and the gather have carried them; what
+            # they did not carry leaves now.  An announcement for other weights is issued all the same and not used.
+            _lib.check(lib.xdfm_cin_pack_flush(_stream()), "cin_pack_flush")
+        if ann is not None and ann[0] == _cin_pack_key(W2s, levels, m):
+            wfs, wzs = ann[1], (ann[2] if any(ctx.needs_input_grad) else None)
+        elif len(levels) <= 8 and all(lib.xdfm_cin_pack_all_supported(H, Hp, m) for (H, Hp, *_r) in levels):
             need_bwd = any(ctx.needs_input_grad)
-            jobs = (_lib.PackJob * len(levels))()
-            wzs = [None] * len(levels)
-            for l, (H, Hp, *_r) in enumerate(levels):
-                wfs[l] = torch.empty(lib.xdfm_cin_fwd_pack_elems(H, Hp, m), dtype=torch.float32, device=dev)
-                if need_bwd:
-                    wzs[l] = torch.empty(lib.xdfm_cin_bwd_pack_elems(H, Hp, m), dtype=torch.float32, device=dev)
-                jobs[l].W, jobs[l].H, jobs[l].Hp, jobs[l].m = W2s[l].data_ptr(), H, Hp, m
-                jobs[l].fwd_pack = wfs[l].data_ptr()
-                jobs[l].bwd_pack = wzs[l].data_ptr() if need_bwd else None
+            jobs, wfs, wzs = _cin_pack_jobs(lib, W2s, levels, m, need_bwd, dev)
             _lib.check(lib.xdfm_cin_pack_all(ctypes.cast(jobs, ctypes.c_void_p), len(levels), _stream()), "cin_pack_all")
             if not need_bwd:
                 wzs = None
@@ -779,6 +859,8 @@ class CINStack(torch.autograd.Function):
             dws = torch.empty(lib.xdfm_cin_bwd_prep_ws_elems(H, Hp, m, B, D), dtype=torch.float32, device=dev)   # fixed-order dbias
             ws = torch.empty(lib.xdfm_cin_bwd_w_ws_elems(H, Hp, m, N), dtype=torch.float32, device=dev) if need_dw else None
             finish_keep(dws)
+            if _RIDER_KEEP is not None and ws is not None:
+                _RIDER_KEEP.append(ws)                  # its slabs are read by whichever launch carries the level's sum
             prepared = ctypes.c_int(0)
             _lib.check(_run("cin_dout", 0.0, lambda: lib.xdfm_cin_bwd_prep(
                 _ptr(A), _ptr(mk), mk.shape[1] if mk is not None else 0, H, B, D, act, _ptr(dhid) if has_hid else None, 0, hid if has_hid else 0, _ptr(g),

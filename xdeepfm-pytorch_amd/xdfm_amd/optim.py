@@ -816,17 +816,14 @@ class TableAdam(_TableStep, torch.optim.Adam):
                     cols, vocab, _, _ = plan.on(X.device)
 
                     def launch():
-                        rc = lib.xdfm_adam_step_deferred(
+                        # the step over `rest` and the rows update: one launch behind the tick (option "colaunch" bit 0)
+                        return lib.xdfm_colaunch_adam_step(
                             ctypes.cast(arr2, ctypes.c_void_p), len(rest), ctypes.byref(d["clk"]), float(group["lr"]),
                             lr_dev[1].data_ptr() if lr_dev is not None else None, float(beta1), float(beta2), float(group["eps"]),
-                            ws.data_ptr() if ws is not None else None, val.data_ptr() if val is not None else None, stream)
-                        if rc:
-                            return rc
-                        return lib.xdfm_adam_apply_rows(
+                            ws.data_ptr() if ws is not None else None, val.data_ptr() if val is not None else None,
                             X.data_ptr(), X.stride(0), X.shape[0], cols.data_ptr(), vocab.data_ptr(), plan.m, plan.D,
-                            ctypes.byref(e_struct), ctypes.byref(l_struct) if l_struct is not None else None, ctypes.byref(d["clk"]),
-                            float(beta1), float(beta2), float(group["eps"]), d["cell"].data_ptr(),
-                            val.data_ptr() if val is not None else None, stream)
+                            ctypes.byref(e_struct), ctypes.byref(l_struct) if l_struct is not None else None,
+                            d["cell"].data_ptr(), stream)
                     _lib.check(ops._run("adam_step[bytes]", nbytes, launch), "adam_step_deferred (rows)")
                 if not capturing:
                     self._since += 1
