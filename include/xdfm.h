@@ -76,6 +76,8 @@
  * measured slower) is removed; the finish batch saves those launches.  Nothing else changes.
  * xdfm_ftrl_tensor, xdfm_ftrl_step (K7f: per-coordinate FTRL-Proximal, a descriptor with two state arrays) -- additions, the
  * version stays 9.
+ * XDFM_ROWWISE_MAX_DIM, xdfm_rowwise_tensor, xdfm_rowwise_adagrad_step (K7w: row-wise Adagrad, one accumulator per table row) --
+ * additions, the version stays 9.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -913,6 +915,54 @@ typedef struct {
 } xdfm_ftrl_tensor;
 int xdfm_ftrl_step(const xdfm_ftrl_tensor* tensors, int T, double lr, const double* lr_dev, double l1, double l2, double beta,
                    float* l2_ws, float* l2_value, void* stream);
+
+/* Row-wise Adagrad (K7w, csrc/rowwise.hip) -- the rule large CTR embedding tables are usually trained with (the DLRM / TorchRec
+ * default, FBGEMM's "exact row-wise Adagrad"); the reference has no counterpart, the host fallback
+ * (xdfm_amd.optim.TableRowwiseAdagrad) spells the same formulas in torch ops.  A tensor is [rows, dim], row-major and dense;
+ * `state` holds ONE accumulator per row ([rows] floats): 1 / dim of Adagrad's state, and 8 + 8 / dim bytes per parameter and
+ * sweep where K7g moves 16.  The same rate (`lr` / `lr_dev`), L2 term (`l2` of the descriptor, here l2m; `l2_ws` of
+ * xdfm_opt_step_ws_elems(T) floats; `l2_value` = sum_t l2_t * sum(w_t^2) of the weights BEFORE the update), option "opt_bx"
+ * and launch composition as above.  Per row, in fp32 unless said otherwise:
+ *   g'_d = fma(2 l2m, p_d, g_d)                                  d = 0 .. dim-1
+ *   S    = sum_d (double)g'_d * (double)g'_d                     exact products, added in double, in THE ORDER below
+ *   ms   = (float)(S / (double)dim)
+ *   s'   = s + ms                                                ms == 0: s keeps its bits
+ *   den  = sqrtf(s') + eps                                       IEEE sqrt; eps > 0
+ *   p_d' = fma(-lr, g'_d / den, p_d)                             IEEE division; g'_d == 0: p_d keeps its bits
+ * THE ORDER of S, fixed per dim and the same on every path (float4 or scalar, marks on or off, any grid), so that all paths
+ * give the same bits: the row is cut into chunks of four consecutive elements (the last chunk has dim % 4 when that is not 0);
+ * a chunk's squares are added left to right, ((x0 + x1) + x2) + x3; the ceil(dim / 4) chunk sums are padded with zeros to the
+ * next power of two and added as a balanced tree, neighbouring pairs first (t[j] = t[2j] + t[2j + 1] until one is left).
+ * The zero-gradient rule: a row whose g' is all zeros keeps the bits of s and p (two selects, see csrc/opt_math.h), so with
+ * l2m == 0 a row none of whose chunks is marked is skipped without being read -- the step costs the mark bytes and the batch's
+ * rows.  With l2m > 0 every row is a real update; an unmarked chunk enters with g = 0.  Marks on / off give the same bits.  A
+ * row whose squares underflow even in double's mean (ms == 0 with g' != 0) keeps s and moves p by lr g' / (sqrt(s) + eps): no
+ * NaN from finite inputs.  dim == 1 IS Adagrad: the call gives the bits of xdfm_adagrad_step on the same data (it runs that
+ * kernel's element update).
+ * Marks (`grad_marks`: one byte per 16-byte chunk of `grad`, ceil(rows dim / 4) of them; needs 16-byte aligned param and grad):
+ * marked chunks are read, re-zeroed and unmarked, unmarked ones are never read.  Every chunk is read and re-zeroed by the same
+ * thread: for dim in {4, 8, 16, 32, 64} a chunk lies inside one row; for every other dim the owner is a unit of four
+ * consecutive rows, which is exactly dim whole chunks.  The rows % 4 tail rows of such a tensor are always read in full, zeroed
+ * and unmarked (the numel % 4 rule of the other kernels): their gradient must be real.
+ * Paths: dim in {4, 8, 16, 32, 64} with 16-byte aligned param and grad -- dim / 4 lanes hold a row in registers, streaming
+ * float4 accesses; anything else (dim % 4 != 0, other multiples of 4, unaligned pointers) -- one thread per four rows, scalar
+ * accesses, correct rather than fast.  `state` needs 4-byte alignment only.
+ * Errors, reported before any device work with the offending value in the message: NULL `tensors`, T outside [1, 65535], a NULL
+ * param / grad / state, rows < 0, dim outside [1, XDFM_ROWWISE_MAX_DIM], l2 < 0, lr < 0, eps <= 0, l2_value without l2_ws,
+ * a state that is not 4-byte aligned, grad_marks with a param or grad that is not 16-byte aligned.
+ * Not covered: a deferred form, lr_decay, weight decay, FBGEMM's weighted / counter variants. */
+#define XDFM_ROWWISE_MAX_DIM 1024
+typedef struct {
+    float* param;                   /* [rows, dim] */
+    float* grad;                    /* [rows, dim] */
+    float* state;                   /* [rows]: the row's accumulator ("sum") */
+    long rows;
+    int dim;
+    float l2;                       /* the model's L2 strength for the tensor (l2m) */
+    unsigned char* grad_marks;      /* NULL: grad is read in full and left alone */
+} xdfm_rowwise_tensor;
+int xdfm_rowwise_adagrad_step(const xdfm_rowwise_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
+                              float* l2_ws, float* l2_value, void* stream);
 
 /* ------------------------------------------------------------------ deferred Adam for the tables (K7d)
  * Same arithmetic, same results, bit for bit, as the dense sweep above -- but the sweep's 24 bytes per table parameter

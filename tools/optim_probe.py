@@ -25,7 +25,13 @@ has no deferred arm.  Its two configurations: the model's default L2 on the tabl
 parameter), and `--no_table_l2` (l2_reg_embedding = l2_reg_linear = 0 with FTRL's own l2: the step reads the marks and the
 batch's rows).  `--optimizers ftrl,adagrad` puts the native Adagrad step on the same model beside it.
 
-    python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad,rmsprop,ftrl] [--arms sweep,deferred,stock]
+`--optimizer rowwise_adagrad` is xdfm_amd.optim.TableRowwiseAdagrad (K7w for the tables, K7g for the rest): `sweep` is its
+kernels, `stock` the same class on its torch-op step, and a further arm, `adagrad`, is the native Adagrad step
+(compile("adagrad")) at its own best path -- deferred where "auto" chooses it -- timed in the same alternating blocks.  No
+deferred arm.  With the model's default L2 on the tables every row is updated (8 + 8 / D bytes per parameter); with
+`--no_table_l2` the step reads the marks and the batch's rows.  Every row also reports the bytes of optimizer state.
+
+    python tools/optim_probe.py [--steps 256] [--vocab mid,criteo-card] [--optimizers sgd,adagrad,rmsprop,ftrl,rowwise_adagrad] [--arms sweep,deferred,stock,adagrad]
                                 [--momentum 0.9 [--nesterov]] [--no_table_l2] [--out FILE.json]
 """
 import argparse
@@ -49,7 +55,7 @@ def route(model):
     optim.SGD_MOMENTUM_NATIVE = getattr(model, "_probe_native", True)
 
 
-def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, nesterov=False, no_table_l2=False):
+def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, nesterov=False, no_table_l2=False, auto=False):
     from deepctr.inputs import DenseFeat, SparseFeat
     from deepctr.models import xDeepFM
     cols = [SparseFeat("C%d" % (i + 1), v, cfg["emb_dim"]) for i, v in enumerate(vocab)]
@@ -64,6 +70,11 @@ def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, neste
         model.compile(opt, "binary_crossentropy", metrics=[])
         if stock:
             opt._native = lambda: False
+    elif optimizer == "rowwise_adagrad":
+        # `sweep`: K7w + K7g; `stock`: the same class sent down its torch-op step
+        model.compile("rowwise_adagrad", "binary_crossentropy", metrics=[])
+        if stock:
+            model.optim._native = lambda: False
     elif optimizer == "sgd" and momentum:
         from xdfm_amd.optim import TableSGD
         opt = TableSGD(model.parameters(), lr=0.01, momentum=momentum, nesterov=nesterov, deferred=bool(deferred))
@@ -75,9 +86,10 @@ def build(cfg, vocab, dev, optimizer, stock, deferred=False, momentum=0.0, neste
         model.compile(opt, "binary_crossentropy", metrics=[])
     else:
         model.compile(optimizer, "binary_crossentropy", metrics=[])
-        model.optim.deferred = bool(deferred)
+        if not auto:                             # (auto: the class's own choice, "auto" unless the environment says otherwise)
+            model.optim.deferred = bool(deferred)
     for pg in model.optim.param_groups:          # a rate at which a sum-reduced loss over 4096 rows stays finite
-        pg["lr"] = {"sgd": 1e-5 * (1.0 - momentum), "adagrad": 1e-3, "rmsprop": 1e-4, "ftrl": 1e-3}[optimizer]
+        pg["lr"] = {"sgd": 1e-5 * (1.0 - momentum), "adagrad": 1e-3, "rmsprop": 1e-4, "ftrl": 1e-3, "rowwise_adagrad": 1e-3}[optimizer]
     model.train()
     return model
 
@@ -185,10 +197,13 @@ def main():
         batches = [(torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev))
                    for X, y in bench.synthetic_batches(8, B, vocab, cfg["n_dense"], seed=2025)]
         for optimizer in args.optimizers.split(","):
-            arms = [a for a in args.arms.split(",") if not (optimizer == "ftrl" and a == "deferred")]      # FTRL has no deferred form
-            models = {a: build(cfg, vocab, dev, optimizer, stock=a == "stock", deferred=a == "deferred", momentum=args.momentum,
-                               nesterov=args.nesterov, no_table_l2=args.no_table_l2) for a in arms}
-            kernel = "sgdm" if optimizer == "sgd" and args.momentum else optimizer
+            # FTRL and row-wise Adagrad have no deferred form; the `adagrad` arm stands beside row-wise Adagrad only
+            arms = [a for a in args.arms.split(",") if not (optimizer in ("ftrl", "rowwise_adagrad") and a == "deferred")
+                    and not (optimizer != "rowwise_adagrad" and a == "adagrad")]
+            models = {a: build(cfg, vocab, dev, "adagrad" if a == "adagrad" else optimizer, stock=a == "stock",
+                               deferred=a == "deferred", momentum=args.momentum, nesterov=args.nesterov,
+                               no_table_l2=args.no_table_l2, auto=a == "adagrad") for a in arms}
+            kernel = "sgdm" if optimizer == "sgd" and args.momentum else "rowwise" if optimizer == "rowwise_adagrad" else optimizer
             for m in models.values():
                 timed(m, batches, args.warmup, 0)
             native = models.get("sweep", models.get("deferred"))
@@ -220,6 +235,16 @@ def main():
                 nbytes, ksecs = kernel_rate(models["sweep"], batches, kernel)
                 row.update(replays=step.replays, graph_nodes=nodes[0] if nodes else None, sweep_bytes=int(nbytes),
                            sweep_us=round(ksecs * 1e6, 2), sweep_TBps=round(nbytes / ksecs / 1e12, 3))
+            for a in arms:                               # bytes of optimizer state (after the steps that created it)
+                if a != "stock":
+                    row["state_bytes_" + a] = sum(v.numel() * v.element_size() for st in models[a].optim.state.values()
+                                                  for v in st.values() if torch.is_tensor(v) and v.is_cuda)
+            if "adagrad" in models:
+                opt = models["adagrad"].optim
+                row["adagrad_deferred_steps"] = opt.path_counts["scan"]
+                nbytes, ksecs = kernel_rate(models["adagrad"], batches, "adagrad")
+                row.update(adagrad_step_bytes=int(nbytes), adagrad_step_us=round(ksecs * 1e6, 2))
+                opt.flush()
             if "stock" in models:
                 row["launches_stock"] = eager_launches(models["stock"], batches)
                 if "sweep" in models:

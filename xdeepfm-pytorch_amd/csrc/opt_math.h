@@ -112,3 +112,54 @@ __device__ __forceinline__ void ftrl_four(float4& p, float4& z, float4& n, const
     ftrl_one(p.x, z.x, n.x, g.x, g2, lr, h, sq); ftrl_one(p.y, z.y, n.y, g.y, g2, lr, h, sq);
     ftrl_one(p.z, z.z, n.z, g.z, g2, lr, h, sq); ftrl_one(p.w, z.w, n.w, g.w, g2, lr, h, sq);
 }
+
+// ---------------------------------------------------------------------------------------------
+// Row-wise Adagrad (K7w, rowwise.hip): one accumulator per row of a [rows, D] tensor
+// ---------------------------------------------------------------------------------------------
+//   g'_d = fma(2 l2m, p_d, g_d);   S = sum_d (double)g'_d (double)g'_d;   ms = (float)(S / (double)D)
+//   s' = s + ms;   den = sqrtf(s') + eps;   p_d' = fma(-lr, g'_d / den, p_d)
+// THE ORDER OF S, the same on every path of the kernel (the products are exact in double, so only the additions round):
+//   1. the row is cut into chunks of four consecutive elements (the last one has D % 4 when that is not 0); a chunk's squares
+//      are added left to right, ((x0 + x1) + x2) + x3;
+//   2. the C = ceil(D / 4) chunk sums are padded with zeros to the next power of two and added as a balanced tree, neighbouring
+//      pairs first: t[j] = t[2j] + t[2j + 1] until one value is left.
+// The zero-gradient rule is two selects, not arithmetic on zeros: ms == 0 keeps the bits of s (s + 0 would turn a -0 into +0),
+// g'_d == 0 keeps the bits of p_d (fma(-lr, -0 / den, -0) is +0).  So a row without a gradient in a tensor without an L2 term is
+// skipped exactly, and marks on / off give the same bits.  A row whose squares underflow even in the mean (ms == 0 with g' != 0)
+// keeps s and still moves p by lr g' / (sqrt(s) + eps): nothing divides by zero because eps > 0.
+#define RW_LEVELS 8            // log2 of the most chunk sums a row has: XDFM_ROWWISE_MAX_DIM / 4 = 256
+static_assert((4 << RW_LEVELS) == XDFM_ROWWISE_MAX_DIM, "RW_LEVELS follows the cap on D");
+
+// g' of one element; `sq` collects p^2 of the weight BEFORE the update
+__device__ __forceinline__ float rw_gp(float p, float g, float g2, float& sq) {
+#pragma clang fp contract(off)
+    sq = fmaf(p, p, sq);
+    return fmaf(g2, p, g);
+}
+// acc + g'^2 in double (the product of two floats is exact there: an fma and a multiply-add give the same bits)
+__device__ __forceinline__ double rw_sq(double acc, float gp) {
+#pragma clang fp contract(off)
+    return acc + (double)gp * (double)gp;
+}
+__device__ __forceinline__ double rw_add(double a, double b) { return a + b; }
+// one chunk of four: g' into `gp`, -> the chunk's sum of squares
+__device__ __forceinline__ double rw_chunk(const float4& p, const float4& g, float g2, float4& gp, float& sq) {
+    gp.x = rw_gp(p.x, g.x, g2, sq); gp.y = rw_gp(p.y, g.y, g2, sq);
+    gp.z = rw_gp(p.z, g.z, g2, sq); gp.w = rw_gp(p.w, g.w, g2, sq);
+    return rw_sq(rw_sq(rw_sq(rw_sq(0.0, gp.x), gp.y), gp.z), gp.w);
+}
+// the row's accumulator after the step
+__device__ __forceinline__ float rw_acc(float s, double S, int D) {
+#pragma clang fp contract(off)
+    const float ms = (float)(S / (double)D);
+    return ms > 0.f ? s + ms : s;
+}
+// one element of the row, den = sqrtf(s') + eps
+__device__ __forceinline__ float rw_one(float p, float gp, float den, float nlr) {
+#pragma clang fp contract(off)
+    return gp != 0.f ? fmaf(nlr, gp / den, p) : p;
+}
+__device__ __forceinline__ void rw_apply(float4& p, const float4& gp, float den, float nlr) {
+    p.x = rw_one(p.x, gp.x, den, nlr); p.y = rw_one(p.y, gp.y, den, nlr);
+    p.z = rw_one(p.z, gp.z, den, nlr); p.w = rw_one(p.w, gp.w, den, nlr);
+}

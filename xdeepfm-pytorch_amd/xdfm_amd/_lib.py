@@ -115,6 +115,7 @@ SIGNATURES = {
     "xdfm_sgdm_catchup_rows": (c_int, [P, c_long, c_int, P, P, c_int, c_int, P, P, P, c_double, c_int, P]),
     "xdfm_sgdm_flush": (c_int, [P, P, c_int, P, c_double, c_int, P]),
     "xdfm_ftrl_step": (c_int, [P, c_int, c_double, P, c_double, c_double, c_double, P, P, P]),
+    "xdfm_rowwise_adagrad_step": (c_int, [P, c_int, c_double, P, c_double, P, P, P]),
     "xdfm_vocab_lse_update": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_softmax_grad": (c_int, [P, c_long, c_int, c_int, P, P, P]),
     "xdfm_vocab_ce_x3_supported": (c_int, [c_int]),
@@ -201,6 +202,12 @@ class OptTensor(ctypes.Structure):
 class FtrlTensor(ctypes.Structure):
     """xdfm_ftrl_tensor of include/xdfm.h (FTRL-Proximal: two state arrays)"""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("z", c_void_p), ("n", c_void_p), ("numel", c_long), ("l2", ctypes.c_float),
+                ("grad_marks", c_void_p)]
+
+
+class RowwiseTensor(ctypes.Structure):
+    """xdfm_rowwise_tensor of include/xdfm.h (row-wise Adagrad: `state` is [rows])"""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("state", c_void_p), ("rows", c_long), ("dim", c_int), ("l2", ctypes.c_float),
                 ("grad_marks", c_void_p)]
 
 

@@ -712,7 +712,7 @@ class BaseModel(nn.Module):
         self._optim_capturable = False
         self._flush_optim()                # a previous optimizer may still owe table rows their latest steps
         self.optim = self._get_optim(optimizer)
-        # the table optimizers (optim.TableAdam / TableSGD / TableAdagrad / TableRMSprop / TableFTRL), also when handed in as an object, e.g.
+        # the table optimizers (optim.TableAdam / TableSGD / TableAdagrad / TableRMSprop / TableFTRL / TableRowwiseAdagrad), also when handed in as an object, e.g.
         # TableAdam(..., lazy_rows=True); an object of a stock torch class keeps the stock path
         if getattr(self.optim, "table_step", False):
             self._optim_capturable = all(p.is_cuda for g in self.optim.param_groups for p in g["params"])
@@ -750,6 +750,11 @@ class BaseModel(nn.Module):
             from .optim import TableFTRL
             return TableFTRL(list(params))
         table["ftrl"] = ftrl
+        if optimizer == "rowwise_adagrad":
+            # row-wise Adagrad: the reference has none; its groups come from the model (tables row-wise, the rest element-wise), on
+            # a CPU model too, where it takes its torch-op path
+            from .optim import TableRowwiseAdagrad
+            return TableRowwiseAdagrad.for_model(self)
         if optimizer not in table:
             raise NotImplementedError
         return table[optimizer](self.parameters())

@@ -24,7 +24,10 @@ Tables with an L2 term may take the deferred (exact) form of those steps (K7sd /
 `TableFTRL` (K7f, `xdfm_ftrl_step`) is per-coordinate FTRL-Proximal, which torch does not have: the same sweep over two state
 arrays, `z` and `n`; its fallback is the class's own step in torch ops, and it has no deferred form.
 
-All five classes are the mixin `_TableStep` in front of the stock class (TableFTRL: of torch.optim.Optimizer): the host scaffold (fields, learning rate on the
+`TableRowwiseAdagrad` (K7w, `xdfm_rowwise_adagrad_step`) is row-wise Adagrad, the usual rule for large CTR embedding tables: one
+accumulator per table row for the groups marked `rowwise`, K7g for everything else; torch-op fallback, no deferred form.
+
+All six classes are the mixin `_TableStep` in front of the stock class (TableFTRL, TableRowwiseAdagrad: of torch.optim.Optimizer): the host scaffold (fields, learning rate on the
 device, invalidation, flush, backlog, pickling, the armed L2 term) exists once; a class brings its clock, its C calls and
 what its kernel implements."""
 import ctypes
@@ -60,13 +63,13 @@ def _ptr_tables(struct, ts, ent, cols, tolerate, pad=0):
 
 
 class _TableStep(object):
-    """The host side of the five table optimizers, and what the model's train step duck-types on (`table_step`): `arm_l2`,
+    """The host side of the six table optimizers, and what the model's train step duck-types on (`table_step`): `arm_l2`,
     `owns`, `l2_value`, `grad_sources`, `sync_lr`, `generation`, `note_replay`, `flush`, `take_backlog`.  A mixin in front of
     the stock class.  A class brings its clock layout and C calls (`_deferred_state`, `_catchup`, `_flush_launch`), what its
     kernel implements (`_plain`, `_state_of`, `_hyper`) and the class attributes below; `step` here is the one of TableSGD,
-    TableAdagrad, TableRMSprop and TableFTRL, TableAdam has its own."""
+    TableAdagrad, TableRMSprop, TableFTRL and TableRowwiseAdagrad, TableAdam has its own."""
     table_step = True
-    _KERNEL = None               # "sgd" / "adagrad" / "rmsprop" / "ftrl" ("sgdm" is TableSGD's second kernel: `_kind`)
+    _KERNEL = None               # "sgd" / "adagrad" / "rmsprop" / "ftrl" ("sgdm" is TableSGD's second kernel, "rowwise" TableRowwiseAdagrad's: `_kind`)
     _ENV = "XDFM_OPT"            # the environment's <_ENV>_DEFERRED / <_ENV>_FLUSH_EVERY
     _PATHS = ("scan",)           # keys of `path_counts`
     _FLOOR = "OPT_DEFER_MIN_NUMEL"      # the module constant "auto" compares with (by name: read when the decision is taken)
@@ -387,6 +390,9 @@ class _TableStep(object):
 
     _DESC = _lib.OptTensor                      # the kernel's descriptor (TableFTRL: two state arrays, _lib.FtrlTensor)
 
+    def _desc_type(self, kind):                 # ... by the group's kernel (TableRowwiseAdagrad has two)
+        return self._DESC
+
     def _set_state(self, desc, st):             # st: what `_state_of` gave -> the state pointers written into `desc`
         desc.state = st[0].data_ptr() if st[0] is not None else None
         return (desc.state,)
@@ -441,10 +447,14 @@ class _TableStep(object):
                    tuple(s.data_ptr() for st in states for s in (st[0],) + tuple(st[2:]) if s is not None), l2)
             hit = self._desc.get(gi)
             if hit is None or hit[0] != key:
-                arr = (self._DESC * T)()
+                arr = (self._desc_type(kind) * T)()
                 aligned = []                           # the tensor's state may be read by float4: a condition of the marks
                 for k in range(T):
-                    arr[k].param, arr[k].numel = params[k].data_ptr(), params[k].numel()
+                    arr[k].param = params[k].data_ptr()
+                    if kind == "rowwise":              # K7w: [rows, dim], one accumulator per row
+                        arr[k].rows, arr[k].dim = params[k].shape
+                    else:
+                        arr[k].numel = params[k].numel()
                     aligned.append(all((q or 0) % 16 == 0 for q in self._set_state(arr[k], states[k])))
                     arr[k].l2 = l2[k] if l2 is not None else 0.0
                 hit = self._desc[gi] = (key, arr, aligned)
@@ -507,7 +517,8 @@ class _TableStep(object):
             nbytes = 0.0
             for k in range(T):
                 # the byte model of DESIGN.md (K7s / K7g / K7r / K7m; K7f: p, z and n)
-                per = 8.0 if kind == "sgd" else 24.0 if kind == "ftrl" else 16.0
+                # (K7w: p read and written, the row's accumulator once per row)
+                per = 8.0 if kind == "sgd" else 24.0 if kind == "ftrl" else 8.0 + 8.0 / arr[k].dim if kind == "rowwise" else 16.0
                 if arr[k].grad_marks:
                     # (RMSprop's accumulator decays in every step, the momentum buffer moves its weight in every step: no shortcut
                     # for a tensor without an L2 term)
@@ -549,6 +560,9 @@ class _TableStep(object):
             elif kind == "adagrad":
                 launch = lambda: lib.xdfm_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                        float(group["eps"]), ws_ptr, val_ptr, stream)
+            elif kind == "rowwise":
+                launch = lambda: lib.xdfm_rowwise_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
+                                                               float(group["eps"]), ws_ptr, val_ptr, stream)
             elif kind == "ftrl":
                 launch = lambda: lib.xdfm_ftrl_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
                                                     float(group["l1"]), float(group["l2"]), float(group["beta"]), ws_ptr, val_ptr,
@@ -1040,4 +1054,125 @@ class TableFTRL(_TableStep, torch.optim.Optimizer):
                 p.copy_(torch.where(live, w1, w))
                 z.copy_(torch.where(live, z1, z0))
                 n.copy_(torch.where(live, n1, n0))
+        return loss
+
+
+class TableRowwiseAdagrad(_TableStep, torch.optim.Optimizer):
+    """Row-wise Adagrad -- the rule large CTR embedding tables are usually trained with (the DLRM / TorchRec default, FBGEMM's
+    "exact row-wise Adagrad") -- whose step is K7w (`xdfm_rowwise_adagrad_step`) for the param groups with `rowwise=True` and K7g
+    (`xdfm_adagrad_step`, plain Adagrad) for the others.  A row-wise group takes 2-D parameters only and keeps ONE accumulator
+    per row, the running sum of the row's mean squared gradient; with the model's armed L2 strength l2m for the tensor:
+
+        g' = g + 2 l2m p;   s' = s + mean_d(g'_d^2);   p' = p - lr g' / (sqrt(s') + eps)
+
+    (the mean is taken in float64 and rounded to fp32; a row whose g' is all zeros keeps the bits of s and p).  State per
+    parameter: `sum`, fp32, of shape [rows] for a row-wise parameter -- 1 / D of Adagrad's state -- and of the parameter's shape
+    otherwise, filled with `initial_accumulator_value`; created by the first eager step, never inside a capture.
+    `for_model(model)` builds the two groups: the `nn.Embedding` weights of `model.embedding_dict` and
+    `model.linear_model.embedding_dict` are row-wise, everything else is element-wise.  With an L2 term on the tables every row is
+    a real update in every step (the sweep moves 8 + 8 / D bytes per parameter, K7g 16); with `l2_reg_embedding = l2_reg_linear =
+    0` -- the recommended configuration -- a row without a gradient does not move, exactly, and the step reads the gradient marks
+    and the batch's rows only.  What the kernels do not take -- CPU parameters, closures, non-fp32 / non-contiguous / sparse
+    tensors, tensor learning rates -- runs the same formulas in torch ops (`_stock_step`), with the armed L2 term applied by hand.
+    There is no deferred form (`deferred` is False; `flush` and `take_backlog` are no-ops), no lr_decay, no weight decay, none
+    of FBGEMM's weighted / counter variants.  Row-parallel runs need no code of their own but are untested on more than one
+    process."""
+    _KERNEL = "adagrad"          # the element-wise groups; "rowwise" for the others (`_kind`)
+
+    def __init__(self, params, lr=0.01, eps=1e-10, initial_accumulator_value=0.0):
+        if not isinstance(lr, torch.Tensor) and not lr >= 0.0:
+            raise ValueError("xdfm TableRowwiseAdagrad: lr %r is negative" % (lr,))
+        if not eps > 0.0:
+            raise ValueError("xdfm TableRowwiseAdagrad: eps %r is not above 0" % (eps,))
+        if not initial_accumulator_value >= 0.0:
+            raise ValueError("xdfm TableRowwiseAdagrad: initial_accumulator_value %r is negative" % (initial_accumulator_value,))
+        super().__init__(params, dict(lr=lr, eps=eps, initial_accumulator_value=initial_accumulator_value, rowwise=False))
+        self._table_init(deferred=False)
+
+    @classmethod
+    def for_model(cls, model, **kw):
+        """The optimizer over `model.parameters()` in two groups: row-wise for the embedding tables (VarLenSparseFeat tables
+        included) and the 1-wide linear tables, element-wise for everything else.  An empty group is left out."""
+        tables = []
+        for holder in (model, getattr(model, "linear_model", None)):
+            ed = getattr(holder, "embedding_dict", None)
+            if ed is not None:
+                tables += [m.weight for m in ed.values() if isinstance(m, torch.nn.Embedding)]
+        row_ids = {id(p) for p in tables}
+        rest = [p for p in model.parameters() if id(p) not in row_ids]
+        rows = [p for p in model.parameters() if id(p) in row_ids]
+        groups = [dict(params=ps, rowwise=rw) for ps, rw in ((rows, True), (rest, False)) if ps]
+        return cls(groups, **kw)
+
+    def add_param_group(self, param_group):
+        if param_group.get("rowwise", False):
+            ps = param_group["params"]
+            ps = param_group["params"] = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+            for p in ps:
+                if p.dim() != 2:
+                    raise ValueError("xdfm TableRowwiseAdagrad: a row-wise group takes 2-D parameters only (got shape %s)"
+                                     % (tuple(p.shape),))
+        return super().add_param_group(param_group)
+
+    def _plain(self, group):
+        return isinstance(group["eps"], float) and group["eps"] > 0
+
+    def _kind(self, group):
+        return "rowwise" if group.get("rowwise") else "adagrad"
+
+    def _desc_type(self, kind):
+        return _lib.RowwiseTensor if kind == "rowwise" else _lib.OptTensor
+
+    def _sum(self, group, p):
+        st = self.state[p]
+        if "sum" not in st:
+            if p.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("xdfm TableRowwiseAdagrad: the state is created by an eager step, not inside a HIP-graph capture")
+            shape = (p.shape[0],) if group.get("rowwise") else tuple(p.shape)
+            st["sum"] = torch.full(shape, float(group["initial_accumulator_value"]), dtype=torch.float32, device=p.device)
+        return st["sum"]
+
+    def _state_of(self, group, p):
+        acc = self._sum(group, p)
+        want = (p.shape[0],) if group.get("rowwise") else tuple(p.shape)
+        if not (acc.is_cuda and acc.dtype == torch.float32 and acc.is_contiguous() and tuple(acc.shape) == want):
+            raise RuntimeError("xdfm TableRowwiseAdagrad: the accumulator of a CUDA parameter must be a contiguous fp32 CUDA tensor "
+                               "of shape %s" % (want,))
+        return acc, None
+
+    def _set_state(self, desc, st):
+        desc.state = st[0].data_ptr()
+        # K7w reads the row's accumulator as one float: no 16-byte condition on it for the marks
+        return () if isinstance(desc, _lib.RowwiseTensor) else (desc.state,)
+
+    def _hyper(self, group):
+        return float(group["eps"])
+
+    @torch.no_grad()
+    def _stock_step(self, closure):
+        """The formulas of the class docstring in torch ops (fp32; the row sum in float64; float64 throughout for a float64
+        parameter).  The armed L2 term is in the gradients already (`_l2_by_hand`)."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for group in self.param_groups:
+            lr, eps = group["lr"], group["eps"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                acc = self._sum(group, p)
+                ct = torch.float64 if p.dtype == torch.float64 else torch.float32
+                g = (p.grad.to_dense() if p.grad.is_sparse else p.grad).to(ct)
+                w, s0 = p.to(ct), acc.to(ct)
+                if group.get("rowwise"):
+                    ms = g.double().square().sum(dim=1).div(g.shape[1]).to(ct)
+                    s1 = torch.where(ms > 0, s0 + ms, s0)
+                    den = (s1.sqrt() + eps).unsqueeze(1)
+                else:
+                    s1 = s0 + g * g
+                    den = s1.sqrt() + eps
+                w1 = torch.where(g != 0, w - lr * (g / den), w)
+                p.copy_(w1)
+                acc.copy_(s1)
         return loss

@@ -61,6 +61,7 @@ def _class_weight(args):
 
 
 FTRL_DEFAULTS = {"ftrl_l1": 0.0, "ftrl_l2": 0.0, "ftrl_beta": 1.0, "ftrl_init_acc": 0.1}       # TableFTRL's own
+ROWWISE_DEFAULTS = {"rowwise_eps": 1e-10, "rowwise_init_acc": 0.0}                               # TableRowwiseAdagrad's own
 
 
 def parse_args(argv=None, model=None, script=None):
@@ -106,6 +107,12 @@ def parse_args(argv=None, model=None, script=None):
                    help="with --ftrl: the proximal L2 strength, >= 0 (default 0; twice TensorFlow's l2_regularization_strength)")
     p.add_argument("--ftrl_beta", type=float, default=None, help="with --ftrl: beta of the per-coordinate rate, >= 0 (default 1)")
     p.add_argument("--ftrl_init_acc", type=float, default=None, help="with --ftrl: initial accumulator value, >= 0 (default 0.1)")
+    p.add_argument("--rowwise_adagrad", action="store_true",
+                   help="row-wise Adagrad (xdfm_amd.optim.TableRowwiseAdagrad: one accumulator per table row, plain Adagrad for "
+                        "everything else) in place of --optimizer; --learning_rate applies")
+    p.add_argument("--rowwise_eps", type=float, default=None, help="with --rowwise_adagrad: eps, > 0 (default 1e-10)")
+    p.add_argument("--rowwise_init_acc", type=float, default=None,
+                   help="with --rowwise_adagrad: initial accumulator value, >= 0 (default 0)")
     p.add_argument("--class_weight", type=float, nargs=2, default=None, metavar=("W0", "W1"),
                    help="weights of the negative and the positive examples in the training loss, e.g. 1 4 for a log whose "
                         "negatives were down-sampled (fit(class_weight={0: W0, 1: W1})); default: none")
@@ -143,6 +150,22 @@ def parse_args(argv=None, model=None, script=None):
             setattr(args, k, v)
         elif not getattr(args, k) >= 0.0:
             p.error("--%s %g is negative" % (k, getattr(args, k)))
+    given = [k for k in ROWWISE_DEFAULTS if getattr(args, k) is not None]
+    if args.rowwise_adagrad and args.ftrl:
+        p.error("--rowwise_adagrad does not go with --ftrl")
+    if args.rowwise_adagrad and (args.momentum != 0.0 or args.nesterov):
+        p.error("--rowwise_adagrad does not go with --momentum / --nesterov")
+    if given and not args.rowwise_adagrad:
+        p.error("%s need(s) --rowwise_adagrad" % ", ".join("--" + k for k in given))
+    for k, v in ROWWISE_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+    if not args.rowwise_eps > 0.0:
+        p.error("--rowwise_eps %g is not above 0" % args.rowwise_eps)
+    if not args.rowwise_init_acc >= 0.0:
+        p.error("--rowwise_init_acc %g is negative" % args.rowwise_init_acc)
+    if args.rowwise_adagrad and not args.learning_rate >= 0.0:
+        p.error("--rowwise_adagrad needs --learning_rate >= 0 (got %g)" % args.learning_rate)
     if args.ftrl and not args.learning_rate > 0.0:
         p.error("--ftrl needs --learning_rate > 0 (got %g): the step divides by it" % args.learning_rate)
     if (args.momentum != 0.0 or args.nesterov) and args.optimizer != "sgd":
@@ -286,12 +309,17 @@ def build_model(args, cols):
 
 def make_optimizer(args, model):
     """What compile() gets: the optimizer's name, or -- SGD with a momentum, which no name of compile() stands for -- the object:
-    xdfm_amd.optim.TableSGD (K7m) for a model on a GPU, torch.optim.SGD on the CPU; with --ftrl a xdfm_amd.optim.TableFTRL (K7f).
+    xdfm_amd.optim.TableSGD (K7m) for a model on a GPU, torch.optim.SGD on the CPU; with --ftrl a xdfm_amd.optim.TableFTRL (K7f),
+    with --rowwise_adagrad a xdfm_amd.optim.TableRowwiseAdagrad (K7w / K7g).
     The rate is set after compile()."""
     if args.ftrl:                                       # on the CPU too: the class brings its own torch-op step
         from xdfm_amd.optim import TableFTRL
         return TableFTRL(list(model.parameters()), lr=args.learning_rate, l1=args.ftrl_l1, l2=args.ftrl_l2, beta=args.ftrl_beta,
                          initial_accumulator_value=args.ftrl_init_acc)
+    if args.rowwise_adagrad:                            # on the CPU too; the groups come from the model
+        from xdfm_amd.optim import TableRowwiseAdagrad
+        return TableRowwiseAdagrad.for_model(model, lr=args.learning_rate, eps=args.rowwise_eps,
+                                             initial_accumulator_value=args.rowwise_init_acc)
     if args.optimizer != "sgd" or args.momentum == 0.0:
         return args.optimizer
     if args.optimizer != "sgd" or args.momentum == 0.0:
