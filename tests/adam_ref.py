@@ -1,4 +1,5 @@
-"""Reference, cases and C-ABI drivers of the Adam kernel tests (K7 / K7d: csrc/adam.hip, csrc/adam_math.h).
+"""Reference, cases and C-ABI drivers of the Adam kernel tests (K7 / K7d: csrc/adam.hip; the chunk update:
+csrc/adam_math.h, adam_four; the mark scan, the block's L2 partial and the launch loop: csrc/table_step.h).
 
 adam_f64 is one Adam step in numpy float64 with the fp32-rounded coefficients the kernels use; the case builders make the
 fixed-seed states and gradients of tests/test_gpu_adam.py; `Bank` and the drivers below it put a state on the device and

@@ -1,5 +1,6 @@
-"""Reference, cases and C-ABI drivers of the FTRL-Proximal tests (K7f: csrc/ftrl.hip; the element update: csrc/opt_math.h,
-ftrl_one) -- opt_ref.py's counterpart for the optimizer with two state arrays.  It imports opt_ref / adam_ref and changes neither.
+"""Reference, cases and C-ABI drivers of the FTRL-Proximal tests (K7f: csrc/ftrl.hip; the sweep's loops: csrc/table_step.h,
+tbl_sweep, shared with K7s / K7g / K7r / K7m; the element update: csrc/opt_math.h, ftrl_one) -- opt_ref.py's counterpart for the
+optimizer with two state arrays.  It imports opt_ref / adam_ref and changes neither.
 
 ftrl_f64 is one step in numpy float64 with the fp32-rounded coefficients the kernel uses, ftrl_f32 the same step in numpy fp32 in
 ftrl_one's order of operations; the builders make the states and gradients of tests/test_gpu_ftrl_abi.py (adam_ref's SIZES,

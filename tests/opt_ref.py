@@ -1,5 +1,6 @@
 """Reference, cases and C-ABI drivers of the SGD / Adagrad / RMSprop kernel tests (K7s / K7g / K7r: csrc/sgd_adagrad.hip;
-K7sd / K7gd / K7rd: csrc/sgd_adagrad_deferred.hip; the element update: csrc/opt_math.h) -- the counterpart of adam_ref.py.
+K7sd / K7gd / K7rd: csrc/sgd_adagrad_deferred.hip; the sweep's loops: csrc/table_step.h, tbl_sweep; the element update:
+csrc/opt_math.h) -- the counterpart of adam_ref.py.
 
 opt_f64 is one step in numpy float64 with the fp32-rounded coefficients the kernels use, opt_f32 the same step in numpy fp32
 in the kernels' order of operations (test_opt_reference.py: the bars are reachable in fp32); the case builders make the

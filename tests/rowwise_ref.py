@@ -1,6 +1,7 @@
-"""Reference, cases and C-ABI drivers of the row-wise Adagrad tests (K7w: csrc/rowwise.hip; the arithmetic: csrc/opt_math.h,
-rw_*) -- ftrl_ref.py's counterpart for the optimizer with one accumulator per table row.  It imports opt_ref and changes nothing
-there.  The reference has no such rule: float64 arithmetic written out here is the reference.
+"""Reference, cases and C-ABI drivers of the row-wise Adagrad tests (K7w: csrc/rowwise.hip; the block's L2 partial and the launch
+loop: csrc/table_step.h; the arithmetic: csrc/opt_math.h, rw_*) -- ftrl_ref.py's counterpart for the optimizer with one
+accumulator per table row.  It imports opt_ref and changes nothing there.  The reference has no such rule: float64 arithmetic
+written out here is the reference.
 
 rw_f64 is one step in numpy float64 with the fp32-rounded coefficients the kernel uses; rw_f32 the same step in numpy fp32 in
 the kernel's order of operations (the fma emulation of opt_ref / ftrl_ref, the summation order documented in include/xdfm.h);

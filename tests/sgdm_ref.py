@@ -1,6 +1,6 @@
 """Reference, cases and C-ABI drivers of the tests of SGD with momentum (K7m: csrc/sgd_adagrad.hip; K7md:
-csrc/sgd_adagrad_deferred.hip; the element update: csrc/opt_math.h, OPT_SGDM) -- opt_ref.py's counterpart for the fourth kind.
-It imports opt_ref / adam_ref and changes neither.
+csrc/sgd_adagrad_deferred.hip; the sweep's loops: csrc/table_step.h, tbl_sweep; the element update: csrc/opt_math.h, OPT_SGDM) --
+opt_ref.py's counterpart for the fourth kind.  It imports opt_ref / adam_ref and changes neither.
 
 sgdm_f64 is one step in numpy float64 with the fp32-rounded coefficients the kernels use, sgdm_f32 the same step in numpy fp32 in
 opt_one's order of operations (test_sgdm_reference.py ties the first to torch.optim.SGD and bounds the second by the bars);

@@ -1,6 +1,6 @@
-// Host-side check of csrc/table_step.h, a stand-alone program (its own main, no device work): the launch order and the grid
-// composer that K7 / K7d / K7s / K7g / K7r and their deferred forms share, against the loops those launchers spelled out
-// before the header existed (kept here as the reference), for T = 1, 63, 64, 65 and 130 tensors of 0, 1, 8191, 8192, 8193
+// Host-side check of csrc/table_step.h, a stand-alone program (its own main, no device work): the launch order, the grid
+// composer and the launch loop (tbl_launches) that K7 / K7d / K7s / K7g / K7r / K7f / K7w and their deferred forms share, against
+// the loops those launchers spelled out before the header held them (kept here as the reference), for T = 1, 63, 64, 65 and 130 tensors of 0, 1, 8191, 8192, 8193
 // and 10^9 elements.  Meant to be built with the host sanitizers and run on a CPU:
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=all
 //         tests/table_step_host.hip -o table_step_host && ./table_step_host
@@ -66,35 +66,48 @@ static void check_step(const std::vector<Tensor>& ts, int cap) {
         if (k) CHECK(ts[order[k - 1]].numel > ts[order[k]].numel || (ts[order[k - 1]].numel == ts[order[k]].numel && order[k - 1] < order[k]),
                      "step T=%d: order is not by falling size, stable", T);
     }
+    // the launches as tbl_step_launches composes them: descriptors, grid, first L2 slot and launch number
     const int nlaunch = ceil_div(T, N);
-    int taken = 0;
-    for (int l = 0; l < nlaunch; ++l) {
-        Batch<N> got, ref;
-        int cnt = 0;
-        for (int k = l; k < T; k += nlaunch) { got.t[cnt] = Dev{ts[order[k]].numel, ts[order[k]].id}; ref.t[cnt] = got.t[cnt]; ++cnt; }
-        CHECK(cnt >= 1 && cnt <= N, "step T=%d: launch %d holds %d tensors", T, l, cnt);
-        for (int k = cnt; k < N; ++k) ref.t[k] = ref.t[0];
-        ref_first(ref, cnt, cap);
-        tbl_grid(got, cnt, BLOCK, cap);
-        same(got, ref, cnt, cap, "step", T);
-        taken += cnt;
-    }
-    CHECK(taken == T, "step T=%d: the launches hold %d tensors", T, taken);
+    int taken = 0, slots = 0, launches = 0;
+    const int total = tbl_step_launches<Batch<N>>(
+        ts.data(), T, [](const Tensor& x) { return Dev{x.numel, x.id}; }, BLOCK, cap, [&](const Batch<N>& got, int got_cnt, int slot0, int l) {
+            CHECK(l == launches && l < nlaunch && slot0 == slots, "step T=%d: launch %d (expected %d) starts at slot %d (expected %d)", T, l,
+                  launches, slot0, slots);
+            Batch<N> ref;
+            int cnt = 0;
+            for (int k = l; k < T; k += nlaunch) ref.t[cnt++] = Dev{ts[want[k]].numel, ts[want[k]].id};
+            CHECK(cnt >= 1 && cnt <= N && cnt == got_cnt, "step T=%d: launch %d holds %d tensors, reference %d", T, l, got_cnt, cnt);
+            for (int k = cnt; k < N; ++k) ref.t[k] = ref.t[0];
+            ref_first(ref, cnt, cap);
+            same(got, ref, cnt, cap, "step", T);
+            taken += cnt;
+            slots += got.first[cnt];
+            ++launches;
+        });
+    CHECK(taken == T && launches == nlaunch && total == slots, "step T=%d: %d launches hold %d tensors in %d blocks (returned %d)", T, launches,
+          taken, slots, total);
 }
 
 // a flush / a deferred step: the tensors in their order, N per launch (xdfm_adam_flush with N = 64, opt_def_grid with N = 48)
 template <int N>
 static void check_chunks(const std::vector<Tensor>& ts, int cap) {
     const int n = (int)ts.size();
-    for (int l0 = 0; l0 < n; l0 += N) {
-        Batch<N> got, ref;
-        const int cnt = n - l0 < N ? n - l0 : N;
-        for (int k = 0; k < N; ++k) { const Tensor& x = ts[l0 + (k < cnt ? k : 0)]; ref.t[k] = Dev{x.numel, x.id}; }
-        ref_first(ref, cnt, cap);
-        for (int k = 0; k < cnt; ++k) got.t[k] = Dev{ts[l0 + k].numel, ts[l0 + k].id};
-        tbl_grid(got, cnt, BLOCK, cap);
-        same(got, ref, cnt, cap, "chunks", n);
-    }
+    int launches = 0, slots = 0;
+    const int total = tbl_launches<Batch<N>>(
+        tbl_in_order(n), false, [&](int t) { return Dev{ts[t].numel, ts[t].id}; }, BLOCK, cap, [&](const Batch<N>& got, int got_cnt, int slot0, int l) {
+            const int l0 = l * N;
+            CHECK(l == launches && l0 < n && slot0 == slots, "chunks T=%d: launch %d (expected %d) starts at slot %d (expected %d)", n, l, launches,
+                  slot0, slots);
+            Batch<N> ref;
+            const int cnt = n - l0 < N ? n - l0 : N;
+            CHECK(cnt == got_cnt, "chunks T=%d: launch %d holds %d tensors, reference %d", n, l, got_cnt, cnt);
+            for (int k = 0; k < N; ++k) { const Tensor& x = ts[l0 + (k < cnt ? k : 0)]; ref.t[k] = Dev{x.numel, x.id}; }
+            ref_first(ref, cnt, cap);
+            same(got, ref, cnt, cap, "chunks", n);
+            slots += got.first[cnt];
+            ++launches;
+        });
+    CHECK(launches == ceil_div(n, N) && total == slots, "chunks T=%d: %d launches, %d blocks (returned %d)", n, launches, slots, total);
 }
 
 int main() {

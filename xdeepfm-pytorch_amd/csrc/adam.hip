@@ -19,7 +19,7 @@
 #include "finish_batch.h"
 #include "adam_math.h"
 #include "cin_x3_pack.h"   // the catch-up carries the |W| maxima of the CIN weight packs as a rider
-#include "table_step.h"    // the streaming accesses, the chunk claim, the launch order and the grid composer
+#include "table_step.h"    // the streaming accesses, the chunk claim, the mark scan, the L2 partial, the launch loop
 
 #define ADAM_THREADS 256
 #define ADAM_BX 512             // most blocks one tensor gets (tools/adam_probe.py: 128 .. 4096 are within 5 % of each other, 512 best)
@@ -110,52 +110,14 @@ __device__ __forceinline__ void adam_step_body(
         float zf;
         asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
         const float4 zero4 = make_float4(zf, zf, zf, zf);
-        auto process = [&](long e) {
+        tbl_mark_scan(marks, n4, tid, stride, [&](long e) {        // the scan of K7s / K7f's sweep (table_step.h)
             float4 pa = p4[e], ma = m4[e], va = v4[e], ga = g4[e];
             g4[e] = zero4; marks[e] = 0;
             for (int s = (int)last[e] + 1; s < t; ++s) adam_replay4(pa, ma, va, adam_step_const(consts, s), g2, zf, c, sq2, eps_ok);
-            sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-            ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-            adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
-            adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+            adam_four(pa, ma, va, ga, g2, step_size, bc2_sqrt, c, sq);
             p4[e] = pa; m4[e] = ma; v4[e] = va;
             last[e] = (unsigned char)t;
-        };
-        // The scan reads the mark bytes 16 at a time (one uint4 per lane and load: the sweep over 144 M marks at Criteo-card
-        // vocabularies is what this step costs); the chunks in front of the first 16-byte boundary of the marks array and
-        // behind the last whole group go one by one.
-        const long head = ((16 - (long)((size_t)marks & 15)) & 15) < n4 ? ((16 - (long)((size_t)marks & 15)) & 15) : n4;
-        const long groups = (n4 - head) / 16;
-        const uint4* __restrict__ m16 = reinterpret_cast<const uint4*>(marks + head);
-        long g = tid;
-        for (; g + stride < groups; g += 2 * stride) {                       // two groups per thread in flight
-            const uint4 wa = m16[g], wb = m16[g + stride];
-            if (wa.x | wa.y | wa.z | wa.w) {
-                const unsigned w[4] = {wa.x, wa.y, wa.z, wa.w};
-#pragma unroll
-                for (int b = 0; b < 16; ++b)
-                    if ((w[b >> 2] >> ((b & 3) * 8)) & 255u) process(head + g * 16 + b);
-            }
-            if (wb.x | wb.y | wb.z | wb.w) {
-                const unsigned w[4] = {wb.x, wb.y, wb.z, wb.w};
-#pragma unroll
-                for (int b = 0; b < 16; ++b)
-                    if ((w[b >> 2] >> ((b & 3) * 8)) & 255u) process(head + (g + stride) * 16 + b);
-            }
-        }
-        if (g < groups) {                               // this thread's last, unpaired group
-            const uint4 wa = m16[g];
-            if (wa.x | wa.y | wa.z | wa.w) {
-                const unsigned w[4] = {wa.x, wa.y, wa.z, wa.w};
-#pragma unroll
-                for (int b = 0; b < 16; ++b)
-                    if ((w[b >> 2] >> ((b & 3) * 8)) & 255u) process(head + g * 16 + b);
-            }
-        }
-        for (long e = tid; e < head; e += stride)
-            if (marks[e]) process(e);
-        for (long e = head + groups * 16 + tid; e < n4; e += stride)
-            if (marks[e]) process(e);
+        });
         i = n4 + tid;                                   // nothing left for the dense loops below
     } else if (marks && (d.flags & XDFM_ADAM_LAZY)) {
         // opt-in row-sparse update: chunks the batch did not touch are skipped altogether (see xdfm.h)
@@ -172,10 +134,7 @@ __device__ __forceinline__ void adam_step_body(
                     const long e = i + q * stride;
                     float4 pa = p4[e], ma = m4[e], va = v4[e], ga = g4[e];
                     g4[e] = zero4; marks[e] = 0;
-                    sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-                    ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-                    adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
-                    adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+                    adam_four(pa, ma, va, ga, g2, step_size, bc2_sqrt, c, sq);
                     p4[e] = pa; m4[e] = ma; v4[e] = va;
                 }
             }
@@ -184,10 +143,7 @@ __device__ __forceinline__ void adam_step_body(
             if (marks[i]) {
                 float4 pa = p4[i], ma = m4[i], va = v4[i], ga = g4[i];
                 g4[i] = zero4; marks[i] = 0;
-                sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-                ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-                adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
-                adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+                adam_four(pa, ma, va, ga, g2, step_size, bc2_sqrt, c, sq);
                 p4[i] = pa; m4[i] = ma; v4[i] = va;
             }
         }
@@ -225,10 +181,7 @@ __device__ __forceinline__ void adam_step_body(
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float4 pa = P[q], ma = M[q], va = V[q], ga = G[q];
-                sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-                ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-                adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
-                adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+                adam_four(pa, ma, va, ga, g2, step_size, bc2_sqrt, c, sq);
                 tbl_st<NT>(at4(p4 + (iu + q * stride), tx16), pa); tbl_st<NT>(at4(m4 + (iu + q * stride), tx16), ma);
                 tbl_st<NT>(at4(v4 + (iu + q * stride), tx16), va);
                 __builtin_amdgcn_sched_barrier(0);       // one chunk's arithmetic at a time: its temporaries die before the next
@@ -240,10 +193,7 @@ __device__ __forceinline__ void adam_step_body(
             float4 pa = tbl_ld<NT>(p4 + i), ma = tbl_ld<NT>(m4 + i), va = tbl_ld<NT>(v4 + i);
             float4 ga = zero4;
             if (ka) { ga = g4[i]; g4[i] = zero4; marks[i] = 0; }
-            sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-            ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-            adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
-            adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+            adam_four(pa, ma, va, ga, g2, step_size, bc2_sqrt, c, sq);
             tbl_st<NT>(p4 + i, pa); tbl_st<NT>(m4 + i, ma); tbl_st<NT>(v4 + i, va);
         }
     }
@@ -259,10 +209,7 @@ __device__ __forceinline__ void adam_step_body(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             float4 pa = P[q], ma = M[q], va = V[q], ga = G[q];
-            sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-            ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-            adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
-            adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+            adam_four(pa, ma, va, ga, g2, step_size, bc2_sqrt, c, sq);
             tbl_st<NT>(at4(p4 + (iu + q * stride), tx16), pa); tbl_st<NT>(at4(m4 + (iu + q * stride), tx16), ma);
             tbl_st<NT>(at4(v4 + (iu + q * stride), tx16), va);
             __builtin_amdgcn_sched_barrier(0);
@@ -271,10 +218,7 @@ __device__ __forceinline__ void adam_step_body(
     i = iu + tx;
     for (; i < n4; i += stride) {
         float4 pa = tbl_ld<NT>(p4 + i), ga = tbl_ld<NT>(g4 + i), ma = tbl_ld<NT>(m4 + i), va = tbl_ld<NT>(v4 + i);
-        sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-        ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-        adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
-        adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+        adam_four(pa, ma, va, ga, g2, step_size, bc2_sqrt, c, sq);
         tbl_st<NT>(p4 + i, pa); tbl_st<NT>(m4 + i, ma); tbl_st<NT>(v4 + i, va);
     }
     for (long k = 4 * n4 + tid; k < n; k += stride) {
@@ -284,15 +228,7 @@ __device__ __forceinline__ void adam_step_body(
         p[k] = pa; m[k] = ma; v[k] = va;
         if (marks) { g[k] = 0.f; marks[k >> 2] = 0; }
     }
-    if (l2_part) {                                     // fixed-order block reduction of the squares
-        sq += sq2.x + sq2.y;
-        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-        __shared__ float wsum[ADAM_THREADS / 64];
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
-        __syncthreads();
-        // one slot per block of the step, in launch order: the finish kernel adds them in that fixed order
-        if (threadIdx.x == 0) l2_part[slot0 + bid] = l2c * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
-    }
+    tbl_l2_slot<ADAM_THREADS>(sq + (sq2.x + sq2.y), l2c, l2_part, slot0 + bid);
 }
 
 template <bool NT>
@@ -486,10 +422,7 @@ __device__ __forceinline__ void adam_apply_rows_body(
         adam_replay_span(pa, ma, va, act, k.old, t - 1, consts, g2, zf, c, sq2, eps_ok);     // the steps the chunk still misses
         if (act) {                                                                           // then this step, with its gradient
             float sq = sq2.x + sq2.y;
-            sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-            ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-            adam_one(pa.x, ga.x, ma.x, va.x, ss, bc, c); adam_one(pa.y, ga.y, ma.y, va.y, ss, bc, c);
-            adam_one(pa.z, ga.z, ma.z, va.z, ss, bc, c); adam_one(pa.w, ga.w, ma.w, va.w, ss, bc, c);
+            adam_four(pa, ma, va, ga, g2, ss, bc, c, sq);
             *p4 = pa; *m4 = ma; *v4 = va;
             sqv = l2c * sq;
         }
@@ -657,10 +590,7 @@ __device__ __forceinline__ void adam_apply_by_row_body(
                 adam_replay_span(pa, ma, va, act, old, t - 1, consts, g2, zf, c, sq2, eps_ok);   // the steps the chunk still misses
                 if (act) {                                                                       // then this step, with its gradient
                     float sq = sq2.x + sq2.y;
-                    sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
-                    ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
-                    adam_one(pa.x, ga.x, ma.x, va.x, ss, bc, c); adam_one(pa.y, ga.y, ma.y, va.y, ss, bc, c);
-                    adam_one(pa.z, ga.z, ma.z, va.z, ss, bc, c); adam_one(pa.w, ga.w, ma.w, va.w, ss, bc, c);
+                    adam_four(pa, ma, va, ga, g2, ss, bc, c, sq);
                     p4[q0 + j] = pa; m4[q0 + j] = ma; v4[q0 + j] = va;
                     fix += adam_backlog_fix(l2c * sq);
                 }
@@ -922,10 +852,9 @@ int xdfm_adam_step_deferred(const xdfm_adam_tensor* tensors, int T, const xdfm_a
 static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double lr, const double* lr_dev,
                           double beta1, double beta2, double eps, float* l2_ws, float* l2_value, void* stream,
                           const AdamRowsArgs* rows, bool rows_by_row, int rows_blocks) {
-    XDFM_REQUIRE(tensors, "adam_step: null pointer");
-    XDFM_REQUIRE(T > 0 && T <= 65535, "adam_step: bad tensor count %d", T);
+    if (int rc = tbl_check_call("adam_step", tensors, T)) return rc;
     XDFM_REQUIRE(lr >= 0 && beta1 >= 0 && beta1 < 1 && beta2 >= 0 && beta2 < 1 && eps >= 0, "adam_step: bad hyper-parameters");
-    XDFM_REQUIRE(!l2_value || l2_ws, "adam_step: l2_value needs l2_ws");
+    if (int rc = tbl_check_l2("adam_step", l2_ws, l2_value)) return rc;
     for (int t = 0; t < T; ++t)
         XDFM_REQUIRE(tensors[t].param && tensors[t].grad && tensors[t].exp_avg && tensors[t].exp_avg_sq && tensors[t].step &&
                          tensors[t].numel >= 0, "adam_step: tensor %d has a null pointer", t);
@@ -942,36 +871,29 @@ static int adam_step_impl(const xdfm_adam_tensor* tensors, int T, const xdfm_ada
     const int* clock = clk ? clk->clock : nullptr;
     const float* consts = clk ? clk->consts : nullptr;
     if (clk) hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, clk->clock, clk->consts, clk->cap, lr, lr_dev, beta1, beta2);
-    // Launch composition: tensors sorted by size and dealt round-robin to the launches (tbl_launch_order)
-    const int nlaunch = ceil_div(T, ADAM_CHUNK);
-    const std::vector<int> order = tbl_launch_order(tensors, T);
-    int slot0 = 0;
-    for (int l = 0; l < nlaunch; ++l) {
-        AdamBatch batch;
-        int cnt = 0;
-        for (int k = l; k < T; k += nlaunch) batch.t[cnt++] = adam_dev(tensors[order[k]]);
-        // blocks per tensor by size (option "adam_bx" caps them: a small footprint for experiments)
-        int cap = xdfm_opt(OPT_ADAM_BX);
-        if (cap <= 0 || cap > ADAM_BX) cap = ADAM_BX;
-        tbl_grid(batch, cnt, ADAM_BLOCK_ELEMS, cap);
+    // Launch composition (table_step.h): tensors sorted by size and dealt round-robin to the launches, blocks per tensor by size
+    // (option "adam_bx" caps them: a small footprint for experiments)
+    int cap = xdfm_opt(OPT_ADAM_BX);
+    if (cap <= 0 || cap > ADAM_BX) cap = ADAM_BX;
+    float* part = l2_value ? l2_ws : nullptr;
+    const int slots = tbl_step_launches<AdamBatch>(tensors, T, adam_dev, ADAM_BLOCK_ELEMS, cap, [&](const AdamBatch& batch, int cnt, int slot0, int l) {
         if (rows && l == 0) {                           // the step's workgroups, then the rows update's
             const dim3 grid((unsigned)(batch.first[cnt] + rows_blocks));
             if (rows_by_row)
                 hipLaunchKernelGGL(adam_step_rows_kernel<true>, grid, dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev, beta1,
-                                   beta2, eps, l2_value ? l2_ws : nullptr, clock, consts, *rows);
+                                   beta2, eps, part, clock, consts, *rows);
             else
                 hipLaunchKernelGGL(adam_step_rows_kernel<false>, grid, dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev, beta1,
-                                   beta2, eps, l2_value ? l2_ws : nullptr, clock, consts, *rows);
+                                   beta2, eps, part, clock, consts, *rows);
         } else if (xdfm_opt(OPT_DBG) & (1 << 17))       // experiment: ordinary (cached) loads and stores
             hipLaunchKernelGGL(adam_step_kernel<false>, dim3(batch.first[cnt]), dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr,
-                               lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts);
+                               lr_dev, beta1, beta2, eps, part, clock, consts);
         else
             hipLaunchKernelGGL(adam_step_kernel<true>, dim3(batch.first[cnt]), dim3(ADAM_THREADS), 0, st, batch, cnt, slot0, lr,
-                               lr_dev, beta1, beta2, eps, l2_value ? l2_ws : nullptr, clock, consts);
-        slot0 += batch.first[cnt];
-    }
+                               lr_dev, beta1, beta2, eps, part, clock, consts);
+    });
     if (l2_value)
-        if (int rc = xdfm_adam_l2_finish(l2_ws, slot0, l2_value, st)) return rc;
+        if (int rc = xdfm_adam_l2_finish(l2_ws, slots, l2_value, st)) return rc;
     return xdfm_check_launch("adam_step");
 }
 
@@ -1067,7 +989,7 @@ int xdfm_colaunch_adam_step(const xdfm_adam_tensor* tensors, int T, const xdfm_a
 
 int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_clock* clk, double beta1, double beta2,
                     double eps, float* backlog, void* stream) {
-    XDFM_REQUIRE(tensors && clk && backlog, "adam_flush: null pointer");
+    XDFM_REQUIRE(tensors && clk && backlog, "adam_flush: null pointer");     // (the clock is checked in front of the count here)
     if (int rc = adam_clock_ok("adam_flush", clk)) return rc;
     XDFM_REQUIRE(T > 0 && T <= 65535, "adam_flush: bad tensor count %d", T);
     XDFM_REQUIRE((((size_t)backlog) & 7) == 0, "adam_flush: backlog must be 8-byte aligned");
@@ -1079,15 +1001,11 @@ int xdfm_adam_flush(const xdfm_adam_tensor* tensors, int T, const xdfm_adam_cloc
                          "adam_flush: tensor %d has a null pointer", t);
             order.push_back(t);
         }
-    const int n = (int)order.size();
-    for (int l0 = 0; l0 < n; l0 += ADAM_CHUNK) {
-        AdamBatch batch;
-        const int cnt = n - l0 < ADAM_CHUNK ? n - l0 : ADAM_CHUNK;
-        for (int k = 0; k < cnt; ++k) batch.t[k] = adam_dev(tensors[order[l0 + k]]);
-        tbl_grid(batch, cnt, ADAM_BLOCK_ELEMS, ADAM_FLUSH_BX);
+    auto launch = [&](const AdamBatch& batch, int cnt, int, int) {
         hipLaunchKernelGGL(adam_flush_kernel, dim3(batch.first[cnt]), dim3(ADAM_THREADS), 0, st, batch, cnt, clk->clock, clk->consts,
                            beta1, beta2, eps, reinterpret_cast<unsigned long long*>(backlog));
-    }
+    };
+    tbl_launches<AdamBatch>(order, false, [&](int t) { return adam_dev(tensors[t]); }, ADAM_BLOCK_ELEMS, ADAM_FLUSH_BX, launch);
     hipLaunchKernelGGL(adam_clock_reset_kernel, dim3(1), dim3(64), 0, st, clk->clock);
     return xdfm_check_launch("adam_flush");
 }

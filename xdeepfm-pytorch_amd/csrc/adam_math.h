@@ -38,6 +38,17 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     p -= step_size * m / denom;
 }
 
+// One 16-byte chunk of a step with its gradient: the step's every loop, and the rows kernels, call this.  `sq` collects the
+// squares of the weights BEFORE the update as (x^2 + y^2) + (z^2 + w^2) -- that association is part of the L2 value's bits --
+// and g' = fma(2 l2, p, g) enters adam_one.
+__device__ __forceinline__ void adam_four(float4& pa, float4& ma, float4& va, float4 ga, float g2, float step_size, float bc2_sqrt,
+                                          const AdamCoef& c, float& sq) {
+    sq += (pa.x * pa.x + pa.y * pa.y) + (pa.z * pa.z + pa.w * pa.w);
+    ga.x = fmaf(g2, pa.x, ga.x); ga.y = fmaf(g2, pa.y, ga.y); ga.z = fmaf(g2, pa.z, ga.z); ga.w = fmaf(g2, pa.w, ga.w);
+    adam_one(pa.x, ga.x, ma.x, va.x, step_size, bc2_sqrt, c); adam_one(pa.y, ga.y, ma.y, va.y, step_size, bc2_sqrt, c);
+    adam_one(pa.z, ga.z, ma.z, va.z, step_size, bc2_sqrt, c); adam_one(pa.w, ga.w, ma.w, va.w, step_size, bc2_sqrt, c);
+}
+
 // Constants of one replayed step (wave-uniform; written by adam_tick_kernel into the clock's table, 4 floats per step):
 //   ss   = lr / (1 - beta1^t)            bc  = sqrt(1 - beta2^t)
 //   c2   = bc * 2^32                     rc2 = RN(1 / bc) * 2^-32, or 0 when the step must take the reference spelling

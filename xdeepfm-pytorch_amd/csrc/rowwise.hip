@@ -2,8 +2,9 @@
 // 2-D tensors [rows, D]: ONE accumulator per row, the running sum over the steps of the mean over the row of g'^2.  The state is
 // 1/D of Adagrad's and the sweep moves 8 + 8/D bytes per parameter (p read and written, s read and written once per row)
 // instead of K7g's 16.  Unlike every other K7 kernel, which updates a 16-byte chunk on its own, this one must see a whole row,
-// gradient and L2 term, before it may write any element of it.  Everything around the loops is shared: the streaming accesses,
-// the launch order and the grid composer (table_step.h), the block cap (option "opt_bx"), the workspace size
+// gradient and L2 term, before it may write any element of it.  So its loops are its own; everything around them is shared: the
+// streaming accesses, the block's L2 partial (tbl_l2_slot), the call's checks and the launch composition (table_step.h:
+// tbl_check_call, tbl_check_l2, tbl_launches), the block cap (option "opt_bx"), the workspace size
 // (xdfm_opt_step_ws_elems) and the L2 finish (xdfm_adam_l2_finish).  The arithmetic is opt_math.h's (rw_*); D == 1 IS Adagrad
 // and calls opt_one<OPT_ADAGRAD>.
 //
@@ -229,14 +230,7 @@ __global__ __launch_bounds__(ROW_THREADS) void rowwise_adagrad_kernel(const RowB
     else if (vec && D == 32) rw_hot<8>(d, c, lb, nb, sq);
     else if (vec && D == 64) rw_hot<16>(d, c, lb, nb, sq);
     else rw_units(d, c, hyp, lb * ROW_THREADS + threadIdx.x, nb * ROW_THREADS, sq);
-    if (l2_part) {                                     // fixed-order block reduction of the squares
-        for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-        __shared__ float wsum[ROW_THREADS / 64];
-        if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sq;
-        __syncthreads();
-        // one slot per block of the step, in launch order: the finish adds them in that fixed order
-        if (threadIdx.x == 0) l2_part[slot0 + blockIdx.x] = d.l2 * ((wsum[0] + wsum[1]) + (wsum[2] + wsum[3]));
-    }
+    tbl_l2_slot<ROW_THREADS>(sq, d.l2, l2_part, slot0 + (int)blockIdx.x);
 }
 
 extern "C" {
@@ -244,12 +238,11 @@ extern "C" {
 int xdfm_rowwise_adagrad_step(const xdfm_rowwise_tensor* tensors, int T, double lr, const double* lr_dev, double eps,
                               float* l2_ws, float* l2_value, void* stream) {
     const char* what = "rowwise_adagrad_step";
-    XDFM_REQUIRE(tensors, "%s: null pointer", what);
-    XDFM_REQUIRE(T > 0 && T <= 65535, "%s: bad tensor count %d", what, T);
+    if (int rc = tbl_check_call(what, tensors, T)) return rc;
     // (negated comparisons: a NaN is refused too)
     XDFM_REQUIRE(lr >= 0, "%s: bad hyper-parameters (lr %g is negative)", what, lr);
     XDFM_REQUIRE(eps > 0, "%s: bad hyper-parameters (eps %g is not above 0)", what, eps);
-    XDFM_REQUIRE(!l2_value || l2_ws, "%s: l2_value needs l2_ws", what);
+    if (int rc = tbl_check_l2(what, l2_ws, l2_value)) return rc;
     for (int t = 0; t < T; ++t) {
         const xdfm_rowwise_tensor& x = tensors[t];
         XDFM_REQUIRE(x.param && x.grad && x.state, "%s: tensor %d has a null pointer (%s)", what, t,
@@ -265,26 +258,20 @@ int xdfm_rowwise_adagrad_step(const xdfm_rowwise_tensor* tensors, int T, double 
                      (void*)x.param, (void*)x.grad);
     }
     hipStream_t st = (hipStream_t)stream;
+    // Launch composition as K7 (table_step.h), by the tensors' element counts; option "opt_bx" caps the blocks per tensor (tests)
     std::vector<RowDev> devs(T);
     for (int t = 0; t < T; ++t) {
         const xdfm_rowwise_tensor& x = tensors[t];
         devs[t] = RowDev{x.param, x.grad, x.state, x.grad_marks, x.rows * (long)x.dim, x.dim, x.l2};
     }
-    // Launch composition as K7: tensors sorted by size and dealt round-robin to the launches (tbl_launch_order)
-    const int nlaunch = ceil_div(T, ROW_CHUNK);
-    const std::vector<int> order = tbl_launch_order(devs.data(), T);
-    int slot0 = 0;
-    for (int l = 0; l < nlaunch; ++l) {
-        RowBatch batch;
-        int cnt = 0;
-        for (int k = l; k < T; k += nlaunch) batch.t[cnt++] = devs[order[k]];
-        tbl_grid(batch, cnt, ROW_BLOCK_ELEMS, opt_bx_cap(ROW_BX));      // option "opt_bx" caps the blocks per tensor (tests)
-        hipLaunchKernelGGL(rowwise_adagrad_kernel, dim3(batch.first[cnt]), dim3(ROW_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev,
-                           opt_hyper(OPT_ADAGRAD, eps, 0.0), l2_value ? l2_ws : nullptr);
-        slot0 += batch.first[cnt];
-    }
+    const int slots = tbl_step_launches<RowBatch>(
+        devs.data(), T, [](const RowDev& d) { return d; }, ROW_BLOCK_ELEMS, opt_bx_cap(ROW_BX),
+        [&](const RowBatch& batch, int cnt, int slot0, int) {
+            hipLaunchKernelGGL(rowwise_adagrad_kernel, dim3(batch.first[cnt]), dim3(ROW_THREADS), 0, st, batch, cnt, slot0, lr, lr_dev,
+                               opt_hyper(OPT_ADAGRAD, eps, 0.0), l2_value ? l2_ws : nullptr);
+        });
     if (l2_value)
-        if (int rc = xdfm_adam_l2_finish(l2_ws, slot0, l2_value, st)) return rc;
+        if (int rc = xdfm_adam_l2_finish(l2_ws, slots, l2_value, st)) return rc;
     return xdfm_check_launch(what);
 }
 

@@ -342,13 +342,12 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
                                   const xdfm_opt_clock* clk, double lr, const double* lr_dev, double eps, double alpha, OptMom mom,
                                   float* l2_ws, float* l2_value, void* stream) {
     constexpr bool ADA = K != OPT_SGD;
-    XDFM_REQUIRE(tensors && last, "%s: null pointer", what);
-    XDFM_REQUIRE(T > 0 && T <= 65535, "%s: bad tensor count %d", what, T);
+    if (int rc = tbl_check_call(what, tensors && last, T)) return rc;
     if (int rc = opt_clock_ok(what, clk)) return rc;
     XDFM_REQUIRE(lr >= 0 && (!ADA || K == OPT_SGDM || eps > 0), "%s: bad hyper-parameters", what);
     XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "%s: bad hyper-parameters (alpha %g is outside [0, 1))", what, alpha);
     XDFM_REQUIRE(K != OPT_SGDM || (mom.mu > 0 && mom.mu < 1), "%s: bad hyper-parameters (momentum %g is outside (0, 1))", what, mom.mu);
-    XDFM_REQUIRE(!l2_value || l2_ws, "%s: l2_value needs l2_ws", what);
+    if (int rc = tbl_check_l2(what, l2_ws, l2_value)) return rc;
     for (int t = 0; t < T; ++t)
         XDFM_REQUIRE(tensors[t].param && tensors[t].grad && tensors[t].numel >= 0 && tensors[t].l2 >= 0,
                      "%s: tensor %d has a null pointer, a negative size or a negative l2", what, t);
@@ -375,15 +374,12 @@ static int opt_step_deferred_impl(const char* what, const xdfm_opt_tensor* tenso
     if (!dense.empty()) {                               // stepped exactly as xdfm_sgd_step / xdfm_adagrad_step step them
         if (int rc = xdfm_opt_step_dense(K, what, dense.data(), (int)dense.size(), lr, lr_dev, eps, alpha, mom.mu, mom.nesterov, l2_ws, l2_value, stream)) return rc;
     }
-    const int n = (int)def.size();
-    for (int l0 = 0; l0 < n; l0 += OPTD_CHUNK) {
-        OptDefBatch batch;
-        const int cnt = n - l0 < OPTD_CHUNK ? n - l0 : OPTD_CHUNK;
-        for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[def[l0 + k]], last[def[l0 + k]]);
-        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, opt_bx_cap(OPTD_BX));
+    auto launch = [&](const OptDefBatch& batch, int cnt, int, int) {
         hipLaunchKernelGGL(opt_step_deferred_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock,
                            clk->rates, opt_hyper(K, eps, alpha, mom), clk->backlog, clk->cell);
-    }
+    };
+    tbl_launches<OptDefBatch>(def, false, [&](int t) { return opt_def_dev(tensors[t], last[t]); }, OPTD_BLOCK_ELEMS, opt_bx_cap(OPTD_BX),
+                              launch);
     hipLaunchKernelGGL(opt_l2_cell_finish_kernel, dim3(1), dim3(64), 0, st, clk->cell, l2_value, dense.empty() ? 0 : 1);
     return xdfm_check_launch(what);
 }
@@ -392,8 +388,7 @@ template <int K>
 static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* last, int T, const xdfm_opt_clock* clk, double eps,
                           double alpha, OptMom mom, void* stream) {
     constexpr bool ADA = K != OPT_SGD;
-    XDFM_REQUIRE(tensors && last, "opt_flush: null pointer");
-    XDFM_REQUIRE(T > 0 && T <= 65535, "opt_flush: bad tensor count %d", T);
+    if (int rc = tbl_check_call("opt_flush", tensors && last, T)) return rc;
     if (int rc = opt_clock_ok("opt_flush", clk)) return rc;
     XDFM_REQUIRE(!ADA || K == OPT_SGDM || eps > 0, "opt_flush: bad hyper-parameters");
     XDFM_REQUIRE(K != OPT_RMSPROP || (alpha >= 0 && alpha < 1), "opt_flush: bad hyper-parameters (alpha %g is outside [0, 1))", alpha);
@@ -407,14 +402,12 @@ static int opt_flush_impl(const xdfm_opt_tensor* tensors, unsigned char* const* 
                      "opt_flush: tensor %d has a pointer that is not 16-byte aligned", t);
     }
     hipStream_t st = (hipStream_t)stream;
-    for (int l0 = 0; l0 < T; l0 += OPTD_CHUNK) {
-        OptDefBatch batch;
-        const int cnt = T - l0 < OPTD_CHUNK ? T - l0 : OPTD_CHUNK;
-        for (int k = 0; k < cnt; ++k) batch.t[k] = opt_def_dev(tensors[l0 + k], last[l0 + k]);
-        tbl_grid(batch, cnt, OPTD_BLOCK_ELEMS, opt_bx_cap(OPTD_FLUSH_BX));
+    auto launch = [&](const OptDefBatch& batch, int cnt, int, int) {
         hipLaunchKernelGGL(opt_flush_kernel<K>, dim3(batch.first[cnt]), dim3(OPTD_THREADS), 0, st, batch, cnt, clk->clock, clk->rates,
                            opt_hyper(K, eps, alpha, mom), clk->backlog);
-    }
+    };
+    tbl_launches<OptDefBatch>(tbl_in_order(T), false, [&](int t) { return opt_def_dev(tensors[t], last[t]); }, OPTD_BLOCK_ELEMS,
+                              opt_bx_cap(OPTD_FLUSH_BX), launch);
     hipLaunchKernelGGL(opt_clock_reset_kernel, dim3(1), dim3(64), 0, st, clk->clock);
     return xdfm_check_launch("opt_flush");
 }

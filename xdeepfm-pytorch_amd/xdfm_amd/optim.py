@@ -27,9 +27,10 @@ arrays, `z` and `n`; its fallback is the class's own step in torch ops, and it h
 `TableRowwiseAdagrad` (K7w, `xdfm_rowwise_adagrad_step`) is row-wise Adagrad, the usual rule for large CTR embedding tables: one
 accumulator per table row for the groups marked `rowwise`, K7g for everything else; torch-op fallback, no deferred form.
 
-All six classes are the mixin `_TableStep` in front of the stock class (TableFTRL, TableRowwiseAdagrad: of torch.optim.Optimizer): the host scaffold (fields, learning rate on the
-device, invalidation, flush, backlog, pickling, the armed L2 term) exists once; a class brings its clock, its C calls and
-what its kernel implements."""
+All six classes are the mixin `_TableStep` in front of the stock class (torch.optim.Optimizer for the two rules torch does not
+have): the host scaffold (fields, learning rate on the device, invalidation, flush, backlog, pickling, the armed L2 term) exists
+once; a class brings its clock and what its kernel implements, and `KINDS` says which C functions a kernel kind calls and with
+which hyper-parameters.  TableAdam keeps a step of its own."""
 import ctypes
 import os
 
@@ -48,6 +49,41 @@ ROWS_MIN_NUMEL = 1 << 20  # tables at least this large get the step's update by 
 # 0 gives the stock torch.optim.SGD.step back for it.  Read once, at import; tools/optim_probe.py and the tests flip this
 # attribute to run both routes in one process (a captured graph keeps the route it was captured with).
 SGD_MOMENTUM_NATIVE = os.environ.get("XDFM_SGD_MOMENTUM_NATIVE", "1") != "0"
+
+
+class _Kind(object):
+    """A kernel kind of `_TableStep.step`.  step / deferred / catchup / flush: the names of its C functions (None: the kind has no
+    such form).  hyper: param group -> the arguments of a step between the rate and the L2 workspace.  lead, replay: the
+    arguments of a catch-up and of a flush in front of the common ones (xdfm_opt_*'s `adagrad` flag), and d["eps"] -> those
+    behind them.  per_param: descriptor -> bytes the sweep moves per parameter beside the gradient (the byte model of
+    DESIGN.md).  skip: an unmarked chunk of a tensor without an L2 term is an exact no-op that the sweep does not read (the
+    rule's SKIP in csrc/; not RMSprop, whose accumulator decays, nor SGDM, whose buffer moves its weight, in every step)."""
+
+    def __init__(self, step, hyper, per_param, skip=True, deferred=None, catchup=None, flush=None, lead=(), replay=None):
+        self.step, self.hyper, self.per_param, self.skip = step, hyper, per_param, skip
+        self.deferred, self.catchup, self.flush, self.lead, self.replay = deferred, catchup, flush, lead, replay
+
+
+_eps = lambda g: (float(g["eps"]),)
+_eps_replay = lambda e: (float(e or 0.0),)
+KINDS = {
+    "sgd": _Kind(step="xdfm_sgd_step", hyper=lambda g: (), per_param=lambda a: 8.0,
+                 deferred="xdfm_sgd_step_deferred", catchup="xdfm_opt_catchup_rows", flush="xdfm_opt_flush", lead=(0,),
+                 replay=_eps_replay),
+    "adagrad": _Kind(step="xdfm_adagrad_step", hyper=_eps, per_param=lambda a: 16.0,
+                     deferred="xdfm_adagrad_step_deferred", catchup="xdfm_opt_catchup_rows", flush="xdfm_opt_flush", lead=(1,),
+                     replay=_eps_replay),
+    "rmsprop": _Kind(step="xdfm_rmsprop_step", hyper=lambda g: (float(g["alpha"]), float(g["eps"])), per_param=lambda a: 16.0,
+                     skip=False, deferred="xdfm_rmsprop_step_deferred", catchup="xdfm_rmsprop_catchup_rows",
+                     flush="xdfm_rmsprop_flush", replay=lambda e: (float(e[0]), float(e[1]))),       # d["eps"]: (alpha, eps)
+    "sgdm": _Kind(step="xdfm_sgdm_step", hyper=lambda g: (float(g["momentum"]), int(bool(g["nesterov"]))),
+                  per_param=lambda a: 16.0, skip=False, deferred="xdfm_sgdm_step_deferred", catchup="xdfm_sgdm_catchup_rows",
+                  flush="xdfm_sgdm_flush", replay=lambda e: (float(e[0]), int(e[1]))),                # d["eps"]: (mu, nesterov)
+    "ftrl": _Kind(step="xdfm_ftrl_step", hyper=lambda g: (float(g["l1"]), float(g["l2"]), float(g["beta"])),
+                  per_param=lambda a: 24.0),                                                         # p, z and n
+    # K7w: p read and written, the row's accumulator once per row
+    "rowwise": _Kind(step="xdfm_rowwise_adagrad_step", hyper=_eps, per_param=lambda a: 8.0 + 8.0 / a.dim),
+}
 
 
 def _ptr_tables(struct, ts, ent, cols, tolerate, pad=0):
@@ -225,13 +261,8 @@ class _TableStep(object):
         head = (X.data_ptr(), X.stride(0), X.shape[0], cols.data_ptr(), vocab.data_ptr(), plan.m, plan.D, ctypes.byref(e_struct),
                 ctypes.byref(l_struct) if l_struct is not None else None, ctypes.byref(d["clk"]))
         stream = torch.cuda.current_stream(X.device).cuda_stream
-        kind = d["kind"]                                # the kernel of the steps the replays stand for, and its d["eps"]:
-        if kind == "rmsprop":                           # (alpha, eps)
-            rc = _lib.load().xdfm_rmsprop_catchup_rows(*(head + (float(d["eps"][0]), float(d["eps"][1]), stream)))
-        elif kind == "sgdm":                            # (mu, nesterov)
-            rc = _lib.load().xdfm_sgdm_catchup_rows(*(head + (float(d["eps"][0]), int(d["eps"][1]), stream)))
-        else:
-            rc = _lib.load().xdfm_opt_catchup_rows(1 if kind == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
+        k = KINDS[d["kind"]]                            # the kernel of the steps the replays stand for, and its d["eps"]
+        rc = getattr(_lib.load(), k.catchup)(*(k.lead + head + k.replay(d["eps"]) + (stream,)))
         _lib.check(rc, "opt_catchup_rows")
 
     @torch.no_grad()
@@ -256,13 +287,8 @@ class _TableStep(object):
             arr[k].state = state.data_ptr() if state is not None else None
             last[k] = lb.data_ptr()
         head = (ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(last, ctypes.c_void_p), len(ent), ctypes.byref(d["clk"]))
-        kind = d["kind"]
-        if kind == "rmsprop":
-            rc = _lib.load().xdfm_rmsprop_flush(*(head + (float(d["eps"][0]), float(d["eps"][1]), stream)))
-        elif kind == "sgdm":
-            rc = _lib.load().xdfm_sgdm_flush(*(head + (float(d["eps"][0]), int(d["eps"][1]), stream)))
-        else:
-            rc = _lib.load().xdfm_opt_flush(1 if kind == "adagrad" else 0, *(head + (float(d["eps"] or 0.0), stream)))
+        k = KINDS[d["kind"]]
+        rc = getattr(_lib.load(), k.flush)(*(k.lead + head + k.replay(d["eps"]) + (stream,)))
         _lib.check(rc, "opt_flush")
 
     def take_backlog(self):
@@ -516,13 +542,9 @@ class _TableStep(object):
                         last_arr[k] = d["tensors"][params[k].data_ptr()][1].data_ptr()
             nbytes = 0.0
             for k in range(T):
-                # the byte model of DESIGN.md (K7s / K7g / K7r / K7m; K7f: p, z and n)
-                # (K7w: p read and written, the row's accumulator once per row)
-                per = 8.0 if kind == "sgd" else 24.0 if kind == "ftrl" else 8.0 + 8.0 / arr[k].dim if kind == "rowwise" else 16.0
+                per = KINDS[kind].per_param(arr[k])
                 if arr[k].grad_marks:
-                    # (RMSprop's accumulator decays in every step, the momentum buffer moves its weight in every step: no shortcut
-                    # for a tensor without an L2 term)
-                    skip = (arr[k].l2 == 0.0 and kind not in ("rmsprop", "sgdm")) or (last_arr is not None and last_arr[k])
+                    skip = (arr[k].l2 == 0.0 and KINDS[kind].skip) or (last_arr is not None and last_arr[k])
                     nbytes += params[k].numel() * (0.0625 if skip else per + 0.0625)
                 else:
                     nbytes += params[k].numel() * (per + 4.0)
@@ -531,45 +553,16 @@ class _TableStep(object):
             lr_dev = self._lr_dev.get(gi)
             lr_ptr = lr_dev[1].data_ptr() if lr_dev is not None else None
             ws_ptr, val_ptr = (ws.data_ptr(), val.data_ptr()) if val is not None else (None, None)
+            entry = KINDS[kind]
+            tail = (float(group["lr"]), lr_ptr) + entry.hyper(group) + (ws_ptr, val_ptr, stream)
             if last_arr is not None:
-                lasts, clk = ctypes.cast(last_arr, ctypes.c_void_p), ctypes.byref(d["clk"])
-                if kind == "rmsprop":
-                    launch = lambda: lib.xdfm_rmsprop_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
-                                                                    float(group["lr"]), lr_ptr, float(group["alpha"]),
-                                                                    float(group["eps"]), ws_ptr, val_ptr, stream)
-                elif kind == "sgdm":
-                    launch = lambda: lib.xdfm_sgdm_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
-                                                                 float(group["lr"]), lr_ptr, float(group["momentum"]),
-                                                                 int(bool(group["nesterov"])), ws_ptr, val_ptr, stream)
-                elif kind == "adagrad":
-                    launch = lambda: lib.xdfm_adagrad_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
-                                                                    float(group["lr"]), lr_ptr, float(group["eps"]), ws_ptr,
-                                                                    val_ptr, stream)
-                else:
-                    launch = lambda: lib.xdfm_sgd_step_deferred(ctypes.cast(arr, ctypes.c_void_p), lasts, T, clk,
-                                                                float(group["lr"]), lr_ptr, ws_ptr, val_ptr, stream)
+                head = (ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(last_arr, ctypes.c_void_p), T, ctypes.byref(d["clk"]))
+                launch = lambda: getattr(lib, entry.deferred)(*(head + tail))
                 self.path_counts["scan"] += 1
                 if not capturing:
                     self._since += 1
-            elif kind == "rmsprop":
-                launch = lambda: lib.xdfm_rmsprop_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
-                                                       float(group["alpha"]), float(group["eps"]), ws_ptr, val_ptr, stream)
-            elif kind == "sgdm":
-                launch = lambda: lib.xdfm_sgdm_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
-                                                    float(group["momentum"]), int(bool(group["nesterov"])), ws_ptr, val_ptr, stream)
-            elif kind == "adagrad":
-                launch = lambda: lib.xdfm_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
-                                                       float(group["eps"]), ws_ptr, val_ptr, stream)
-            elif kind == "rowwise":
-                launch = lambda: lib.xdfm_rowwise_adagrad_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
-                                                               float(group["eps"]), ws_ptr, val_ptr, stream)
-            elif kind == "ftrl":
-                launch = lambda: lib.xdfm_ftrl_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
-                                                    float(group["l1"]), float(group["l2"]), float(group["beta"]), ws_ptr, val_ptr,
-                                                    stream)
             else:
-                launch = lambda: lib.xdfm_sgd_step(ctypes.cast(arr, ctypes.c_void_p), T, float(group["lr"]), lr_ptr,
-                                                   ws_ptr, val_ptr, stream)
+                launch = lambda: getattr(lib, entry.step)(ctypes.cast(arr, ctypes.c_void_p), T, *tail)
             _lib.check(ops._run("%s_step[bytes]" % kind, nbytes, launch), "%s_step" % kind)
             self._add_l2(val)
         if host_steps:
