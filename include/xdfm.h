@@ -78,6 +78,8 @@
  * version stays 9.
  * XDFM_ROWWISE_MAX_DIM, xdfm_rowwise_tensor, xdfm_rowwise_adagrad_step (K7w: row-wise Adagrad, one accumulator per table row) --
  * additions, the version stays 9.
+ * xdfm_eval_metrics_ws_bytes, xdfm_eval_metrics (K14s: the four metrics of evaluate() for up to 2^27 rows, the AUC by a radix
+ * sort) -- additions, the version stays 9.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -1270,6 +1272,35 @@ int xdfm_autodis_bwd(const float* x, long ldx, long B, int F, int K, int D, cons
 enum { XDFM_METRIC_LOGLOSS = 1, XDFM_METRIC_AUC = 2, XDFM_METRIC_MSE = 4, XDFM_METRIC_ACC = 8 };
 size_t xdfm_batch_metrics_ws_bytes(int B, int which);
 int xdfm_batch_metrics(const float* y, const float* p, int B, int which, void* ws, double* out4, void* stream);
+
+/* ------------------------------------------------------------------ K14s: evaluation metrics, any row count (csrc/eval_metrics.hip)
+ * replaces: the host tail of the reference's evaluate (deepctr/models/basemodel.py:311-352): all predictions copied to the
+ *           host and widened to float64, then sklearn's log_loss / roc_auc_score / mean_squared_error / accuracy_score on one
+ *           CPU thread -- by 2 launches without the AUC and 15 with it, for any subset of the four.  No float atomics, no
+ *           memset, no allocation, no synchronisation, no host read; the launches and their shapes depend on (N, which) alone;
+ *           a repeated call gives the same bits in all four slots.
+ *   y, p, which, out4   as for xdfm_batch_metrics above, with the same four definitions (positives y > 0.5, the clamp of the
+ *           logloss, a slot `which` does not name keeps its bits, one class or any NaN in p: auc = NaN)
+ *   ws      xdfm_eval_metrics_ws_bytes(N, which) bytes, 8-byte aligned, the caller's; it may hold anything (every cell read
+ *           is written first by an earlier launch of the call).  About 8 N + N / 4 bytes with the AUC, N / 100 without.
+ *           0 for an N or a `which` outside the supported range.
+ *   auc       exact, sort-based, in integers: scores become order-preserving u32 keys (-0.0 as +0.0), positives the key
+ *             0xFFFFFFFF; an LSD radix sort of the keys alone (4 passes of 8 bits: histogram, scan, stable scatter); every
+ *             positive takes a lower and an upper bound among the sorted non-positives; C = sum (lower + upper)
+ *             = sum (2 #less + #equal) in unsigned 64-bit integers and auc = (C * 0.5) / (double(n_pos) * double(n_neg)):
+ *             K14's formula, the bits of roc_auc_score.
+ *   logloss, mse   K14's arithmetic per row.  Order of both sums: a thread adds its 16 rows t, t + 256, ... of a 4096-row tile
+ *             in index order; the tile's 256 threads are added by a fixed tree (xor tree over a wave's 64 lanes, the 4 waves
+ *             in order); the finish gives thread t the tiles t, t + 256, ... in index order and adds its 256 threads by the
+ *             same tree; one division by N.  With T = ceil(N / 4096) tiles a term passes through at most
+ *             d = 25 + ceil(T / 256) + 9 additions, so against numpy's pairwise float64 sum of the same terms
+ *             (at most 27 + ceil(log2(max(N, 128) / 128)) additions deep):
+ *             |got - ref| <= ((d + d_numpy) * 2^-53 + 6 * 2^-52) * ref  (tests/eval_metrics_ref.py derives it).
+ *   accuracy, n_pos, NaN scores   64-bit integer counts per tile, added by the finish
+ * 1 <= N <= 2^27: n_pos * n_neg <= 2^52 keeps C / 2 exact in a double.  XDFM_ERR_INVALID, before any device call: a NULL
+ * operand, N outside the range, which == 0 or with bits above 15, a ws or out4 off 8-byte alignment. */
+size_t xdfm_eval_metrics_ws_bytes(long N, int which);
+int xdfm_eval_metrics(const float* y, const float* p, long N, int which, void* ws, double* out4, void* stream);
 
 #ifdef __cplusplus
 }

@@ -796,8 +796,13 @@ class BaseModel(nn.Module):
         entry still the function `_get_metrics` wires in (a callable the user put there keeps the path it had)."""
         if not (ops.METRICS_NATIVE and max_rows <= ops.METRICS_MAX_ROWS and ops.batch_metrics_supported(y_true, y_pred)):
             return {}
-        table = {M.log_loss: 0, M.roc_auc_score: 1, M.mean_squared_error: 2, BaseModel._accuracy_score: 3}
+        table = self._wired_slots()
         return {name: table[fn] for name, fn in self.metrics.items() if fn in table}
+
+    @staticmethod
+    def _wired_slots():
+        """{function `_get_metrics` wires in: its slot of out4} -- the table of K14 (`fit`) and K14s (`evaluate`)."""
+        return {M.log_loss: 0, M.roc_auc_score: 1, M.mean_squared_error: 2, BaseModel._accuracy_score: 3}
 
     def _in_multi_worker_mode(self):
         return None
@@ -1035,23 +1040,67 @@ class BaseModel(nn.Module):
         cbs.on_train_end()
         return self.history
 
-    def evaluate(self, x, y, batch_size=256):
-        pred = self.predict(x, batch_size)
-        return {name: fn(y, pred) for name, fn in self.metrics.items()}
+    def _eval_native_plan(self, y):
+        """(float32 labels [N], {metrics key: slot of xdfm_eval_metrics' out4}) when `evaluate` may take K14s for these labels,
+        else None: the switch ops.EVAL_NATIVE on, the model on a GPU, numeric labels that survive the round trip through
+        float32 unchanged, and at least one entry of `self.metrics` still the function `_get_metrics` wired in."""
+        if not (ops.EVAL_NATIVE and torch.device(self.device).type == "cuda"):
+            return None
+        table = self._wired_slots()
+        slots = {name: table[fn] for name, fn in self.metrics.items() if fn in table}
+        ya = np.asarray(y)
+        if not slots or ya.dtype.kind not in "buif" or not 1 <= ya.size <= ops.EVAL_MAX_ROWS:
+            return None
+        y32 = np.ascontiguousarray(ya.reshape(-1), dtype=np.float32)
+        if not np.array_equal(y32.astype(ya.dtype), ya.reshape(-1)):          # soft float64 labels, a NaN: the host's arithmetic
+            return None
+        return y32, slots
 
-    def predict(self, x, batch_size=256):
-        """float64 [N, 1] predictions (basemodel.py:325-352)."""
+    def evaluate(self, x, y, batch_size=256):
+        """{metrics key: value} of the predictions for x against y.  With a plan from `_eval_native_plan` the predictions stay
+        on the device, the labels go there once and ONE ops.eval_metrics call (K14s) with one host read serves every wired
+        entry; a callable the user put into `self.metrics` still gets host arrays, the predictions copied once for them.
+        Otherwise: the numpy functions on `predict`'s output."""
+        plan = self._eval_native_plan(y)
+        if plan is None:
+            pred = self.predict(x, batch_size)
+            return {name: fn(y, pred) for name, fn in self.metrics.items()}
+        y32, slots = plan
+        dev = self._predict_device(x, batch_size)
+        if dev is None or dev.numel() != y32.size or dev.dtype != torch.float32:       # not one label per row
+            pred = self._predictions_to_host(dev)
+            return {name: fn(y, pred) for name, fn in self.metrics.items()}
+        vals = ops.eval_metrics(torch.from_numpy(y32).to(dev.device), dev.reshape(-1),
+                                sum(1 << s for s in set(slots.values()))).tolist()      # the one host read
+        self._raise_on_bad_ids()
+        n_pos = int((y32 > 0.5).sum())
+        if 1 in slots.values() and vals[1] != vals[1] and n_pos in (0, y32.size):
+            raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+        pred = self._predictions_to_host(dev) if len(slots) < len(self.metrics) else None
+        return {name: vals[slots[name]] if name in slots else fn(y, pred) for name, fn in self.metrics.items()}
+
+    def _predict_device(self, x, batch_size):
+        """The batch loop of `predict`: the fp32 predictions for every row of x on the model's device, one per row in the
+        model's output shape ([N, 1]); None without rows."""
         self.eval()
         X_all, _ = self._resident(x)
         chunks = []
         with torch.no_grad():
             for start in range(0, X_all.shape[0], batch_size):
                 chunks.append(self(X_all[start:start + batch_size].to(self.device)))
-        if not chunks:
+        return torch.cat(chunks) if chunks else None
+
+    def _predictions_to_host(self, dev):
+        """What `predict` returns for the loop's output: float64 on the host, after the deferred id check."""
+        if dev is None:
             return np.zeros((0, 1), dtype="float64")
-        out = torch.cat(chunks).cpu().data.numpy().astype("float64")      # one device-to-host copy
+        out = dev.cpu().data.numpy().astype("float64")      # one device-to-host copy
         self._raise_on_bad_ids()
         return out
+
+    def predict(self, x, batch_size=256):
+        """float64 [N, 1] predictions (basemodel.py:325-352)."""
+        return self._predictions_to_host(self._predict_device(x, batch_size))
 
 
 # ------------------------------------------------------------------------------------------------- #

@@ -2244,3 +2244,54 @@ def batch_metrics(y, p, which, out):
     _lib.check(_run("batch_metrics", 0.0, lambda: lib.xdfm_batch_metrics(_ptr(y), _ptr(p), B, int(which), _ptr(ws), _ptr(out), _stream())),
                "batch_metrics")
     return out
+
+
+# --------------------------------------------------------------------------------------------- #
+# evaluation metrics for any row count (K14s, csrc/eval_metrics.hip)                             #
+# --------------------------------------------------------------------------------------------- #
+# XDFM_EVAL_NATIVE: `evaluate` (and with it the validation of `fit`) keeps the predictions on the device and takes logloss /
+# AUC / mse / accuracy from one `eval_metrics` call (a radix sort for the AUC) instead of copying the predictions to the host
+# and running the numpy functions of metrics.py there.  Read once, at import; a module attribute the tests and
+# tools/eval_probe.py flip.  The default follows profiles/eval_probe.md.
+EVAL_NATIVE = _env_switch(os.environ, "XDFM_EVAL_NATIVE", default=True)
+EVAL_MAX_ROWS = 1 << 27
+_EVAL_WS = {}
+
+
+def eval_metrics_supported(y, p):
+    """Can `eval_metrics` take this (labels, predictions) pair?  fp32, contiguous, 1-D device tensors of one length within the
+    kernel's cap."""
+    return bool(isinstance(y, torch.Tensor) and isinstance(p, torch.Tensor) and y.is_cuda and p.is_cuda and y.device == p.device
+                and y.dtype == torch.float32 and p.dtype == torch.float32 and y.dim() == 1 and p.dim() == 1
+                and y.is_contiguous() and p.is_contiguous() and y.numel() == p.numel() and 1 <= y.numel() <= EVAL_MAX_ROWS)
+
+
+def eval_metrics(y, p, which):
+    """A float64 [4] device tensor whose slot k holds metric k of (y, p) for every bit k of `which` (logloss | auc | mse |
+    accuracy; xdfm_eval_metrics) and NaN elsewhere: launches on the current stream, nothing reaches the host.  y, p: what
+    `eval_metrics_supported` accepts.  One workspace per device is kept and grown on demand: calls on one stream follow each
+    other."""
+    _need_cuda(y, "y")
+    _need_cuda(p, "p")
+    if not eval_metrics_supported(y, p):
+        raise ValueError("xdfm eval_metrics: y %s on %s and p %s on %s must be contiguous 1-D tensors of one length in [1, %d]"
+                         % (tuple(y.shape), y.device, tuple(p.shape), p.device, EVAL_MAX_ROWS))
+    lib = _lib.load()
+    y, p = y.detach(), p.detach()
+    N = y.numel()
+    need = lib.xdfm_eval_metrics_ws_bytes(N, int(which))
+    if need == 0:
+        raise ValueError("xdfm eval_metrics: N=%d, which=%d outside the supported range (1 <= N <= %d, 1 <= which <= 15)"
+                         % (N, int(which), EVAL_MAX_ROWS))
+    idx = y.device.index if y.device.index is not None else torch.cuda.current_device()
+    ws = _EVAL_WS.get(idx)
+    if ws is None or ws.numel() * 8 < need:
+        ws = None
+        _EVAL_WS.pop(idx, None)                                   # both references go: the smaller one is freed before the larger one comes
+        ws = torch.empty(need // 8, dtype=torch.float64, device=y.device)
+        if not torch.cuda.is_current_stream_capturing():          # a tensor born inside a capture belongs to that graph's pool
+            _EVAL_WS[idx] = ws
+    out = torch.full((4,), float("nan"), dtype=torch.float64, device=y.device)
+    _lib.check(_run("eval_metrics", 0.0, lambda: lib.xdfm_eval_metrics(_ptr(y), _ptr(p), N, int(which), _ptr(ws), _ptr(out), _stream())),
+               "eval_metrics")
+    return out
