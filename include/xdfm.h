@@ -80,6 +80,8 @@
  * additions, the version stays 9.
  * xdfm_eval_metrics_ws_bytes, xdfm_eval_metrics (K14s: the four metrics of evaluate() for up to 2^27 rows, the AUC by a radix
  * sort) -- additions, the version stays 9.
+ * xdfm_eval_metrics_w_ws_bytes, xdfm_eval_metrics_w (K14w: K14s with one weight per row, the weighted_metrics of evaluate() and
+ * fit()) -- additions, the version stays 9.
  */
 #ifndef XDFM_H
 #define XDFM_H
@@ -1301,6 +1303,44 @@ int xdfm_batch_metrics(const float* y, const float* p, int B, int which, void* w
  * operand, N outside the range, which == 0 or with bits above 15, a ws or out4 off 8-byte alignment. */
 size_t xdfm_eval_metrics_ws_bytes(long N, int which);
 int xdfm_eval_metrics(const float* y, const float* p, long N, int which, void* ws, double* out4, void* stream);
+
+/* ------------------------------------------------------------------ K14w: sample-weighted evaluation metrics (csrc/eval_metrics_w.hip)
+ * replaces: the host path of the weighted metrics (compile(weighted_metrics=...)): all predictions copied to the host, widened
+ *           to float64, then xdfm_amd/metrics.py's weighted_log_loss / weighted_roc_auc_score / weighted_mean_squared_error /
+ *           weighted_accuracy_score on one CPU thread -- by 2 launches without the AUC and 18 with it.  As K14s: no float
+ *           atomics, no memset, no allocation, no synchronisation, no host read; the launches and their shapes depend on
+ *           (N, which) alone; a repeated call gives the same bits in all four slots.
+ *   y, p, which, out4   as for xdfm_eval_metrics
+ *   w       [N] fp32 weights (contiguous), finite and >= 0 by the caller's contract (the host validates them).  A row with
+ *           w == 0 is selected away, not multiplied: a NaN score on it is harmless.  Any other bit pattern (negative, NaN)
+ *           counts as 0 too; weights never form an address, so the kernels write inside their arrays whatever w holds.
+ *   ws      xdfm_eval_metrics_w_ws_bytes(N, which) bytes, 8-byte aligned, the caller's; it may hold anything.  In 8-byte cells,
+ *           T = ceil(N / 4096): 7 T without the AUC (the documented prefix: nothing beyond it is touched then); with the AUC
+ *           9 T + (N + 1) [cum, doubles] + 4 ceil(N / 2) [keys and weights, two buffers each] + 128 T + 128: about 24 N bytes.
+ *           0 for an N or a `which` outside the supported range.
+ * With wd = double(w) on the rows with w > 0, W = sum wd, Wpos / Wneg the same over the positives (y > 0.5) / the others (each
+ * its own sum; Wneg is never W - Wpos):
+ *   logloss   -(sum wd (y log(pc) + (1 - y) log(1 - pc))) / W, pc as in K14
+ *   mse       (sum wd (y - p)^2) / W;      accuracy  (sum wd [(p > 0.5 ? 1 : 0) == y]) / W
+ *   auc       (C * 0.5) / (Wpos * Wneg), C = sum over the positives i of wd_i (cum[lb_i] + cum[ub_i]): the keys of K14s and the
+ *             weight as a payload go through K14s's stable radix sort (its histogram and scan kernels; the scatter stores key
+ *             and weight at the rank the ballots give), cum[k] is the float64 exclusive prefix sum of the sorted non-positives'
+ *             weights and lb / ub are K14s's bounds.  Stability fixes the order in which equal scores enter cum.  Order of cum:
+ *             a tile's total in the tiled order; one workgroup scans the tiles' totals, a thread taking ceil(T / 256) consecutive
+ *             tiles in order and the 256 runs by a Hillis-Steele scan; inside a tile 16 rows of 256 consecutive cells, each
+ *             scanned over the lanes of its 4 waves, the waves and then the rows carried in order: at most
+ *             d_cum = 37 + 2 ceil(T / 256) additions to a cell.
+ *             NaN: a NaN score on a row with w > 0, Wpos * Wneg == 0.  W == 0: NaN in every slot asked for.
+ *   sums      logloss, mse, accuracy, W, Wpos, Wneg and C in K14s's order (16 rows per thread, the fixed tree over the tile, the
+ *             finish over the tiles: d = 25 + ceil(T / 256) + 9 additions), each term one product with wd (an fma into the
+ *             sum).  tests/eval_metrics_w_ref.py derives the bounds against the float64 reference from these depths.
+ * UNIT WEIGHTS (w == 1.0f everywhere) give the bits of xdfm_eval_metrics in all four slots: the terms, their order and the
+ * divisions are K14s's, and W = N, Wpos, Wneg, cum[k] = k and C are then exact integers.  Weights that are multiples of 2^-k
+ * with every sum below 2^53 * 2^-k make the accuracy and the AUC exact likewise.
+ * 1 <= N <= 2^27.  XDFM_ERR_INVALID, before any device call: a NULL operand (w included), N outside the range, which == 0 or
+ * with bits above 15, a ws or out4 off 8-byte alignment. */
+size_t xdfm_eval_metrics_w_ws_bytes(long N, int which);
+int xdfm_eval_metrics_w(const float* y, const float* p, const float* w, long N, int which, void* ws, double* out4, void* stream);
 
 #ifdef __cplusplus
 }

@@ -175,6 +175,8 @@ SIGNATURES = {
     "xdfm_batch_metrics": (c_int, [P, P, c_int, c_int, P, P, P]),
     "xdfm_eval_metrics_ws_bytes": (c_size_t, [c_long, c_int]),
     "xdfm_eval_metrics": (c_int, [P, P, c_long, c_int, P, P, P]),
+    "xdfm_eval_metrics_w_ws_bytes": (c_size_t, [c_long, c_int]),
+    "xdfm_eval_metrics_w": (c_int, [P, P, P, c_long, c_int, P, P, P]),
 }
 
 class PackJob(ctypes.Structure):

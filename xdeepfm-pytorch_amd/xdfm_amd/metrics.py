@@ -44,6 +44,73 @@ def accuracy_score(y_true, y_pred):
 
 
 # ------------------------------------------------------------------------------------------------------------------
+# Sample-weighted versions (compile(weighted_metrics=...)), float64 throughout.  A row with w == 0 contributes nothing: it is
+# selected away before any arithmetic, not multiplied, so a NaN score on it is harmless.  Positives are y > 0.5.
+# W = sum w, Wpos = sum over the positives, Wneg = sum over the others: each its own sum, Wneg is never W - Wpos.
+# W == 0 gives NaN (for the AUC: the one-class error, as there is no weighted pair).  With unit weights each function returns
+# the bits of its unweighted namesake.
+# ------------------------------------------------------------------------------------------------------------------
+def _live(y_true, y_pred, w):
+    y = np.asarray(y_true, dtype=np.float64).ravel()
+    p = np.asarray(y_pred, dtype=np.float64).ravel()
+    w = np.asarray(w, dtype=np.float64).ravel()
+    if not (y.size == p.size == w.size):
+        raise ValueError("weighted metric: %d labels, %d predictions, %d weights" % (y.size, p.size, w.size))
+    keep = w > 0
+    return y[keep], p[keep], w[keep]
+
+
+def _ratio(num, den):
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return float(np.float64(num) / np.float64(den))
+
+
+def weighted_log_loss(y_true, y_pred, w):
+    """-sum w (y log pc + (1 - y) log(1 - pc)) / sum w, pc the clamp of `log_loss` for float64 predictions."""
+    y, p, w = _live(y_true, y_pred, w)
+    eps = np.finfo(np.float64).eps
+    p = np.clip(p, eps, 1 - eps)
+    return -_ratio(np.sum(w * (y * np.log(p) + (1 - y) * np.log(1 - p))), np.sum(w))
+
+
+def weighted_mean_squared_error(y_true, y_pred, w):
+    y, p, w = _live(y_true, y_pred, w)
+    d = y - p
+    return _ratio(np.sum(w * (d * d)), np.sum(w))
+
+
+def weighted_accuracy_score(y_true, y_pred, w):
+    """sum w [(p > 0.5 ? 1 : 0) == y] / sum w: y_pred are scores, thresholded as `compile`'s accuracy does."""
+    y, p, w = _live(y_true, y_pred, w)
+    return _ratio(np.sum(np.where(np.where(p > 0.5, 1.0, 0.0) == y, w, 0.0)), np.sum(w))
+
+
+def weighted_roc_auc_score(y_true, y_score, w):
+    """Weighted Mann-Whitney statistic with mid-rank ties: (C * 0.5) / (Wpos * Wneg), C = sum over the positives i of
+    w_i (cum[lb_i] + cum[ub_i]), where cum is the exclusive prefix sum of the non-positives' weights in ascending (stable)
+    score order and lb / ub are the lower / upper bound of the positive's score among those scores (-0.0 == +0.0).
+    NaN for a NaN score on a row with w > 0; ValueError when Wpos * Wneg == 0."""
+    y, s, w = _live(y_true, y_score, w)
+    pos = y > 0.5
+    w_pos, w_neg = w[pos], w[~pos]
+    Wpos, Wneg = np.sum(w_pos), np.sum(w_neg)
+    if Wpos * Wneg == 0:
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    if np.isnan(s).any():
+        return float("nan")
+    order = np.argsort(s[~pos], kind="mergesort")
+    neg = s[~pos][order]
+    cum = np.concatenate(([0.0], np.cumsum(w_neg[order])))
+    lb = np.searchsorted(neg, s[pos], side="left")
+    ub = np.searchsorted(neg, s[pos], side="right")
+    C = np.sum(w_pos * (cum[lb] + cum[ub]))
+    return _ratio(C * 0.5, Wpos * Wneg)
+
+
+WEIGHTED = {log_loss: weighted_log_loss, roc_auc_score: weighted_roc_auc_score, mean_squared_error: weighted_mean_squared_error}
+
+
+# ------------------------------------------------------------------------------------------------------------------
 # The same metrics on device tensors, each returning a 0-d float64 tensor without any host synchronisation: `fit`
 # logs them per step (basemodel.py:264-269 calls the sklearn functions on host copies of every batch -- a device
 # to host copy, a sync and a CPU sort per step) and reads the epoch's values back once.

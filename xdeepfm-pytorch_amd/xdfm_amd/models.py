@@ -707,7 +707,9 @@ class BaseModel(nn.Module):
         self._aux_unset = False
 
     # ------------------------------------------------------------------ compile
-    def compile(self, optimizer, loss=None, metrics=None):
+    def compile(self, optimizer, loss=None, metrics=None, weighted_metrics=None):
+        """`weighted_metrics` (Keras's name): the same names as `metrics`; each gives a `weighted_<name>` entry computed with
+        the example weights of `fit` / `evaluate` (xdfm_amd.metrics.weighted_*).  None or []: nothing about the model changes."""
         self.metrics_names = ["loss"]
         self._optim_capturable = False
         self._flush_optim()                # a previous optimizer may still owe table rows their latest steps
@@ -718,6 +720,26 @@ class BaseModel(nn.Module):
             self._optim_capturable = all(p.is_cuda for g in self.optim.param_groups for p in g["params"])
         self.loss_func = self._get_loss_func(loss)
         self.metrics = self._get_metrics(metrics)
+        self.weighted_metrics = self._get_weighted_metrics(weighted_metrics)
+
+    def _get_weighted_metrics(self, names):
+        """{"weighted_" + name: weighted function} for the names `_get_metrics` knows, in the order given; as there, a name it
+        does not know gets a History name and no function."""
+        table = {"binary_crossentropy": M.weighted_log_loss, "logloss": M.weighted_log_loss, "auc": M.weighted_roc_auc_score,
+                 "mse": M.weighted_mean_squared_error, "accuracy": M.weighted_accuracy_score, "acc": M.weighted_accuracy_score}
+        out = {}
+        for name in (names or []):
+            if name in table:
+                out["weighted_" + name] = table[name]
+            self.metrics_names.append("weighted_" + name)
+        return out
+
+    @staticmethod
+    def _weighted_slots():
+        """{weighted function `compile` wires in: (its slot of out4, the unweighted function it equals under unit weights)}"""
+        return {M.weighted_log_loss: (0, M.log_loss), M.weighted_roc_auc_score: (1, M.roc_auc_score),
+                M.weighted_mean_squared_error: (2, M.mean_squared_error),
+                M.weighted_accuracy_score: (3, BaseModel._accuracy_score)}
 
     def _get_optim(self, optimizer):
         if not isinstance(optimizer, str):
@@ -839,24 +861,30 @@ class BaseModel(nn.Module):
         given torch seed (the stock DataLoader draws it), BCE(sum) + L2, History keys, callbacks.
         `sample_weight` / `class_weight` (see `example_weights`): the data loss of a step is sum_b w_b loss_b.  The
         History `loss` stays (sum of weighted data loss + L2) / sample_num -- the reference's normaliser, not sum(w).
-        Training metrics, `evaluate`, `predict` and a third item of `validation_data` take no weights."""
+        The unweighted metrics and `predict` take no weights.  A model compiled with `weighted_metrics` also logs
+        `weighted_<name>` per step from the step's weights (unit weights without any) and `val_weighted_<name>` from the
+        validation weights: the tail of the weight vector under `validation_split`, else the third item of `validation_data`
+        times `class_weight`; on any other model that third item is accepted and ignored, as in the reference."""
         if isinstance(x, dict):
             x = [x[name] for name in self.feature_index]
-        w_all = example_weights(y, sample_weight, class_weight, getattr(self.out, "task", None))
+        task = getattr(self.out, "task", None)
+        w_all = example_weights(y, sample_weight, class_weight, task)
+        wm = getattr(self, "weighted_metrics", None) or {}
         do_validation = False
-        val_x, val_y = [], []
+        val_x, val_y, val_w = [], [], None
         if validation_data:
             do_validation = True
             if len(validation_data) == 2:
                 val_x, val_y = validation_data
             elif len(validation_data) == 3:
-                val_x, val_y, _ = validation_data
+                val_x, val_y, val_w = validation_data
             else:
                 raise ValueError('When passing a `validation_data` argument, it must contain either 2 items '
                                  '(x_val, y_val), or 3 items (x_val, y_val, val_sample_weights). '
                                  'However we received `validation_data=%s`' % (validation_data,))
             if isinstance(val_x, dict):
                 val_x = [val_x[name] for name in self.feature_index]
+            val_w = example_weights(val_y, val_w, class_weight, task) if wm else None
         elif validation_split and 0. < validation_split < 1.:
             do_validation = True
             n0 = x[0].shape[0] if hasattr(x[0], 'shape') else len(x[0])
@@ -864,7 +892,8 @@ class BaseModel(nn.Module):
             x, val_x = _slice(x, 0, split_at), _slice(x, split_at)
             y, val_y = _slice(y, 0, split_at), _slice(y, split_at)
             if w_all is not None:
-                w_all = w_all[:split_at]       # the validation part's weights are dropped: validation is unweighted
+                # the validation part's weights serve the weighted metrics alone: the unweighted validation takes none
+                w_all, val_w = w_all[:split_at], (w_all[split_at:] if wm else None)
 
         X_all, Y_all = self._resident(x, y)
         W_all = None if w_all is None else torch.from_numpy(w_all).to(X_all.device)    # resident with X / Y
@@ -887,7 +916,7 @@ class BaseModel(nn.Module):
         self.stop_training = False
         print("Train on {0} samples, validate on {1} samples, {2} steps per epoch".format(
             sample_num, len(val_y), steps_per_epoch))
-        loss_log = metric_log = native_log = None
+        loss_log = metric_log = native_log = wnative_log = None
         for epoch in range(initial_epoch, epochs):
             cbs.on_epoch_begin(epoch)
             epoch_logs, train_result = {}, {}
@@ -896,6 +925,7 @@ class BaseModel(nn.Module):
             step_no = 0
             logged = {}
             native_logged = {}
+            wlogged, wresult = {}, {}
             has_extra = False
             order = epoch_order(sample_num, shuffle)
             if order is not None:
@@ -914,10 +944,11 @@ class BaseModel(nn.Module):
                         self.__dict__["_row_weight"] = dp.row_weight()
                     xd = xb.to(self.device)
                     yd = yb.to(self.device)
-                    if wb is None:
+                    wd = None if wb is None else wb.to(self.device)
+                    if wd is None:
                         y_pred, loss, total_loss = self.train_on_batch(xd, yd)
                     else:
-                        y_pred, loss, total_loss = self.train_on_batch(xd, yd, wb.to(self.device))
+                        y_pred, loss, total_loss = self.train_on_batch(xd, yd, wd)
                     if dp is not None and dp.row_weight() == 0.0:
                         # stand-in row of a rank without rows in this (tail) batch: contributes nothing
                         total_loss = total_loss - loss
@@ -963,6 +994,10 @@ class BaseModel(nn.Module):
                                                          dtype=torch.float64, device=yt.device)
                             metric_log[step_no - 1, k:k + 1].copy_(dev_fn(yt, yp.detach()).reshape(1))
                             logged[name] = k
+                        if wm:
+                            wt = wd if wd is None or dp is None else dp.gather_rows(wd.reshape(-1))
+                            wnative_log = self._log_weighted_step(yt, yp.detach(), wt, global_bs, steps_per_epoch, step_no - 1,
+                                                                  wnative_log, wlogged, wresult)
             except KeyboardInterrupt:
                 if bar is not None:
                     bar.close()
@@ -1012,20 +1047,34 @@ class BaseModel(nn.Module):
                 if slot == 1 and any(v != v for v in vals):
                     raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
                 train_result[name] = vals
+            for name, (log, slot) in wlogged.items():             # K14w's rows, or K14's for a batch without weights
+                vals = log[:step_no, slot].tolist()
+                if slot == 1 and any(v != v for v in vals):
+                    raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+                wresult[name] = vals
             for name in self.metrics:                             # History keys in the order `compile` was given
                 if name in train_result:
                     epoch_logs[name] = np.sum(train_result[name]) / steps_per_epoch
+            for name, fn in wm.items():
+                if name not in wresult and w_all is None and fn in self._weighted_slots():
+                    # unit weights, and the unweighted function is one of `self.metrics`: its values
+                    twin = [k for k, f in self.metrics.items() if f is self._weighted_slots()[fn][1] and k in train_result]
+                    if twin:
+                        wresult[name] = train_result[twin[0]]
+                if name in wresult:
+                    epoch_logs[name] = np.sum(wresult[name]) / steps_per_epoch
             if do_validation:
-                for name, val in self.evaluate(val_x, val_y, batch_size).items():
+                val_logs = self.evaluate(val_x, val_y, batch_size, sample_weight=val_w) if wm else self.evaluate(val_x, val_y, batch_size)
+                for name, val in val_logs.items():
                     epoch_logs["val_" + name] = val
             if verbose > 0 and (dp is None or dp.rank == 0):
                 msg = "{0}s - loss: {1: .4f}".format(int(time.time() - t_epoch), epoch_logs["loss"])
                 if "sfg_loss" in epoch_logs:
                     msg += " - sfg_loss: {0: .4f}".format(epoch_logs["sfg_loss"])
-                for name in self.metrics:
+                for name in list(self.metrics) + list(wm):
                     msg += " - " + name + ": {0: .4f}".format(epoch_logs[name])
                 if do_validation:
-                    for name in self.metrics:
+                    for name in list(self.metrics) + list(wm):
                         msg += " - val_" + name + ": {0: .4f}".format(epoch_logs["val_" + name])
                 print('Epoch {0}/{1}'.format(epoch + 1, epochs))
                 print(msg)
@@ -1040,27 +1089,79 @@ class BaseModel(nn.Module):
         cbs.on_train_end()
         return self.history
 
+    def _log_weighted_step(self, yt, yp, wt, max_rows, steps_per_epoch, row, log, wlogged, wresult):
+        """One step's `weighted_*` values of `fit` (labels yt, predictions yp, weights wt of the global batch; wt None: unit
+        weights).  On a GPU with fp32 tensors every wired entry comes from ONE ops.eval_metrics_w call (K14w) into row `row`
+        of the float64 log, read once per epoch -- for a batch without weights from ops.batch_metrics (K14), whose values are
+        the unweighted ones, unless the unweighted function is logged anyway (`fit` takes those values at the epoch's end).
+        Everything else: the numpy functions on host copies, appended to wresult[name].  Returns the log; wlogged[name] =
+        (log, slot) for what it holds."""
+        wtable = self._weighted_slots()
+        y1, p1 = yt.reshape(-1), yp.reshape(-1)
+        native = {}
+        if wt is not None:
+            w1 = wt.reshape(-1)
+            if ops.EVAL_W_NATIVE and ops.eval_metrics_w_supported(y1, p1, w1):
+                native = {name: wtable[fn][0] for name, fn in self.weighted_metrics.items() if fn in wtable}
+        elif ops.METRICS_NATIVE and max_rows <= ops.METRICS_MAX_ROWS and ops.batch_metrics_supported(yt, yp):
+            native = {name: wtable[fn][0] for name, fn in self.weighted_metrics.items()
+                      if fn in wtable and wtable[fn][1] not in self.metrics.values()}
+        if native:
+            if log is None or log.device != yt.device:
+                log = torch.empty((steps_per_epoch + 1, 4), dtype=torch.float64, device=yt.device)
+            which = sum({1 << s for s in native.values()})
+            if wt is not None:
+                ops.eval_metrics_w(y1, p1, w1, which, log[row])
+            else:
+                ops.batch_metrics(yt, yp, which, log[row])
+            wlogged.update({name: (log, slot) for name, slot in native.items()})
+        host = None
+        for name, fn in self.weighted_metrics.items():
+            if name in native or (wt is None and fn in wtable and wtable[fn][1] in self.metrics.values()):
+                continue
+            if host is None:
+                host = (yt.cpu().data.numpy(), yp.cpu().data.numpy().astype("float64"),
+                        None if wt is None else wt.cpu().data.numpy())
+            if wt is None and fn in wtable:
+                wresult.setdefault(name, []).append(wtable[fn][1](host[0], host[1]))
+            else:
+                wresult.setdefault(name, []).append(fn(host[0], host[1], np.ones(host[0].size, np.float32) if wt is None else host[2]))
+        return log
+
     def _eval_native_plan(self, y):
         """(float32 labels [N], {metrics key: slot of xdfm_eval_metrics' out4}) when `evaluate` may take K14s for these labels,
         else None: the switch ops.EVAL_NATIVE on, the model on a GPU, numeric labels that survive the round trip through
         float32 unchanged, and at least one entry of `self.metrics` still the function `_get_metrics` wired in."""
-        if not (ops.EVAL_NATIVE and torch.device(self.device).type == "cuda"):
-            return None
         table = self._wired_slots()
         slots = {name: table[fn] for name, fn in self.metrics.items() if fn in table}
+        y32 = self._eval_native_labels(y) if ops.EVAL_NATIVE and slots else None
+        return None if y32 is None else (y32, slots)
+
+    def _eval_native_labels(self, y):
+        """The labels as float32 [N] when K14s / K14w may take them (the model on a GPU, numeric labels that survive the round
+        trip through float32 unchanged, a row count within the kernels' cap), else None."""
+        if torch.device(self.device).type != "cuda":
+            return None
         ya = np.asarray(y)
-        if not slots or ya.dtype.kind not in "buif" or not 1 <= ya.size <= ops.EVAL_MAX_ROWS:
+        if ya.dtype.kind not in "buif" or not 1 <= ya.size <= ops.EVAL_MAX_ROWS:
             return None
         y32 = np.ascontiguousarray(ya.reshape(-1), dtype=np.float32)
         if not np.array_equal(y32.astype(ya.dtype), ya.reshape(-1)):          # soft float64 labels, a NaN: the host's arithmetic
             return None
-        return y32, slots
+        return y32
 
-    def evaluate(self, x, y, batch_size=256):
+    def evaluate(self, x, y, batch_size=256, sample_weight=None):
         """{metrics key: value} of the predictions for x against y.  With a plan from `_eval_native_plan` the predictions stay
         on the device, the labels go there once and ONE ops.eval_metrics call (K14s) with one host read serves every wired
         entry; a callable the user put into `self.metrics` still gets host arrays, the predictions copied once for them.
-        Otherwise: the numpy functions on `predict`'s output."""
+        Otherwise: the numpy functions on `predict`'s output.
+        A model compiled with `weighted_metrics` returns those entries after the unweighted ones (`_evaluate_weighted`);
+        `sample_weight` (one finite weight >= 0 per row; None: unit weights) is refused on any other model."""
+        if getattr(self, "weighted_metrics", None):
+            return self._evaluate_weighted(x, y, batch_size, sample_weight)
+        if sample_weight is not None:
+            raise ValueError("evaluate(sample_weight=...) needs a model compiled with weighted_metrics: no entry of this "
+                             "model would use the weights")
         plan = self._eval_native_plan(y)
         if plan is None:
             pred = self.predict(x, batch_size)
@@ -1078,6 +1179,59 @@ class BaseModel(nn.Module):
             raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
         pred = self._predictions_to_host(dev) if len(slots) < len(self.metrics) else None
         return {name: vals[slots[name]] if name in slots else fn(y, pred) for name, fn in self.metrics.items()}
+
+    def _evaluate_weighted(self, x, y, batch_size, sample_weight):
+        """`evaluate` of a model compiled with `weighted_metrics`: the unweighted entries as `evaluate` computes them (K14s when
+        its conditions hold, else the host), then the `weighted_*` entries.  With weights and ops.EVAL_W_NATIVE, on the
+        conditions of the native route, the weights go to the device once and ONE ops.eval_metrics_w call (K14w) serves every
+        wired weighted entry; both calls' values come back in one host read.  Without weights (unit weights) a wired weighted
+        entry is the value of its unweighted function, taken from the same computation.  Otherwise: metrics.py's weighted
+        numpy functions on the host copy of the predictions."""
+        w = example_weights(y, sample_weight, None, getattr(self.out, "task", None))
+        table, wtable = self._wired_slots(), self._weighted_slots()
+        unit = {name: wtable[fn][1] for name, fn in self.weighted_metrics.items() if w is None and fn in wtable}
+        y32 = self._eval_native_labels(y)
+        dev = self._predict_device(x, batch_size)
+        on_dev = y32 is not None and dev is not None and dev.numel() == y32.size and dev.dtype == torch.float32
+        u_slots, a_slots, w_slots = {}, {}, {}
+        if on_dev and ops.EVAL_NATIVE:
+            u_slots = {name: table[fn] for name, fn in self.metrics.items() if fn in table}
+            a_slots = {name: table[fn] for name, fn in unit.items()}
+        if on_dev and ops.EVAL_W_NATIVE and w is not None:
+            w_slots = {name: wtable[fn][0] for name, fn in self.weighted_metrics.items() if fn in wtable}
+        uvals = wvals = None
+        if u_slots or a_slots or w_slots:
+            yd, pd, parts = torch.from_numpy(y32).to(dev.device), dev.reshape(-1), []
+            if u_slots or a_slots:
+                parts.append(ops.eval_metrics(yd, pd, sum(1 << s for s in set(u_slots.values()) | set(a_slots.values()))))
+            if w_slots:
+                parts.append(ops.eval_metrics_w(yd, pd, torch.from_numpy(w).to(dev.device), sum(1 << s for s in set(w_slots.values()))))
+            vals = torch.cat(parts).tolist()                                            # the one host read
+            uvals, wvals = (vals[:4] if u_slots or a_slots else None), (vals[-4:] if w_slots else None)
+            self._raise_on_bad_ids()
+            one_class = ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+            pos = y32 > 0.5
+            if uvals is not None and 1 in set(u_slots.values()) | set(a_slots.values()) and uvals[1] != uvals[1] \
+                    and int(pos.sum()) in (0, y32.size):
+                raise one_class
+            if wvals is not None and 1 in w_slots.values() and wvals[1] != wvals[1] \
+                    and float(w[pos].sum(dtype=np.float64)) * float(w[~pos].sum(dtype=np.float64)) == 0:
+                raise one_class
+        served = set(u_slots) | set(a_slots) | set(w_slots)
+        pred = self._predictions_to_host(dev) if len(served) < len(self.metrics) + len(self.weighted_metrics) else None
+        out, by_fn = {}, {}
+        for name, fn in self.metrics.items():
+            out[name] = by_fn[fn] = uvals[u_slots[name]] if name in u_slots else fn(y, pred)
+        for name, fn in self.weighted_metrics.items():
+            if name in w_slots:
+                out[name] = wvals[w_slots[name]]
+            elif name in a_slots:
+                out[name] = uvals[a_slots[name]]
+            elif name in unit:
+                out[name] = by_fn[unit[name]] if unit[name] in by_fn else unit[name](y, pred)
+            else:
+                out[name] = fn(y, pred, np.ones(len(pred), np.float32) if w is None else w)
+        return out
 
     def _predict_device(self, x, batch_size):
         """The batch loop of `predict`: the fp32 predictions for every row of x on the model's device, one per row in the

@@ -2295,3 +2295,59 @@ def eval_metrics(y, p, which):
     _lib.check(_run("eval_metrics", 0.0, lambda: lib.xdfm_eval_metrics(_ptr(y), _ptr(p), N, int(which), _ptr(ws), _ptr(out), _stream())),
                "eval_metrics")
     return out
+
+
+# --------------------------------------------------------------------------------------------- #
+# sample-weighted evaluation metrics (K14w, csrc/eval_metrics_w.hip)                             #
+# --------------------------------------------------------------------------------------------- #
+# XDFM_EVAL_W_NATIVE: the `weighted_*` entries of `evaluate` and of the per-batch log of `fit` (compile(weighted_metrics=...))
+# come from one `eval_metrics_w` call on the device instead of metrics.py's weighted numpy functions on host copies.  Read once,
+# at import; a module attribute the tests and tools/weighted_eval_probe.py flip.  The default follows
+# profiles/weighted_eval_probe.md.
+EVAL_W_NATIVE = _env_switch(os.environ, "XDFM_EVAL_W_NATIVE", default=True)
+_EVAL_W_WS = {}
+
+
+def eval_metrics_w_supported(y, p, w):
+    """Can `eval_metrics_w` take this (labels, predictions, weights) triple?  What `eval_metrics_supported` asks of (y, p), and
+    the same of w."""
+    return bool(eval_metrics_supported(y, p) and isinstance(w, torch.Tensor) and w.is_cuda and w.device == y.device
+                and w.dtype == torch.float32 and w.dim() == 1 and w.is_contiguous() and w.numel() == y.numel())
+
+
+def eval_metrics_w(y, p, w, which, out=None):
+    """`eval_metrics` with one weight per row (xdfm_eval_metrics_w): a float64 [4] device tensor, slot k the weighted metric k
+    for every bit k of `which` and NaN elsewhere; launches on the current stream, nothing reaches the host.  w: finite and
+    >= 0 -- the caller's contract (`models.example_weights` checks it on the host).  Its own workspace per device, grown on
+    demand.  out: a contiguous float64 [4] device tensor (a row of `fit`'s log) to write the named slots into instead; its
+    other slots keep what they hold."""
+    _need_cuda(y, "y")
+    _need_cuda(p, "p")
+    _need_cuda(w, "w")
+    if not eval_metrics_w_supported(y, p, w):
+        raise ValueError("xdfm eval_metrics_w: y %s on %s, p %s on %s and w %s on %s must be contiguous 1-D float32 tensors of one "
+                         "length in [1, %d]" % (tuple(y.shape), y.device, tuple(p.shape), p.device, tuple(w.shape), w.device,
+                                                EVAL_MAX_ROWS))
+    lib = _lib.load()
+    y, p, w = y.detach(), p.detach(), w.detach()
+    N = y.numel()
+    need = lib.xdfm_eval_metrics_w_ws_bytes(N, int(which))
+    if need == 0:
+        raise ValueError("xdfm eval_metrics_w: N=%d, which=%d outside the supported range (1 <= N <= %d, 1 <= which <= 15)"
+                         % (N, int(which), EVAL_MAX_ROWS))
+    idx = y.device.index if y.device.index is not None else torch.cuda.current_device()
+    ws = _EVAL_W_WS.get(idx)
+    if ws is None or ws.numel() * 8 < need:
+        ws = None
+        _EVAL_W_WS.pop(idx, None)                                 # both references go: the smaller one is freed before the larger one comes
+        ws = torch.empty(need // 8, dtype=torch.float64, device=y.device)
+        if not torch.cuda.is_current_stream_capturing():          # a tensor born inside a capture belongs to that graph's pool
+            _EVAL_W_WS[idx] = ws
+    if out is None:
+        out = torch.full((4,), float("nan"), dtype=torch.float64, device=y.device)
+    elif not (out.is_cuda and out.device == y.device and out.dtype == torch.float64 and out.shape == (4,) and out.is_contiguous()):
+        raise ValueError("xdfm eval_metrics_w: out must be a contiguous float64 [4] tensor on %s" % (y.device,))
+    _lib.check(_run("eval_metrics_w", 0.0,
+                    lambda: lib.xdfm_eval_metrics_w(_ptr(y), _ptr(p), _ptr(w), N, int(which), _ptr(ws), _ptr(out), _stream())),
+               "eval_metrics_w")
+    return out

@@ -331,7 +331,11 @@ class BaseModelSFG(BaseModel):
             self.sfg_loss_fn = None
         self.to(device)
 
-    def compile(self, optimizer, loss=None, metrics=None):
+    def compile(self, optimizer, loss=None, metrics=None, weighted_metrics=None):
+        if weighted_metrics:
+            # the weights such metrics would follow are refused by train_on_batch below, for the reason given there
+            raise NotImplementedError("weighted_metrics are not supported by %s: its SFG term is normalised on its own; "
+                                      "train it without example weights" % type(self).__name__)
         super().compile(optimizer, loss, metrics)
         if self.use_sfg:                                   # basemodel_sfg.py:588-590
             self.metrics_names.insert(1, "sfg_loss")

@@ -116,6 +116,9 @@ def parse_args(argv=None, model=None, script=None):
     p.add_argument("--class_weight", type=float, nargs=2, default=None, metavar=("W0", "W1"),
                    help="weights of the negative and the positive examples in the training loss, e.g. 1 4 for a log whose "
                         "negatives were down-sampled (fit(class_weight={0: W0, 1: W1})); default: none")
+    p.add_argument("--weighted_metrics", action="store_true",
+                   help="also report the metrics weighted by --class_weight (compile(weighted_metrics=...)): weighted_* and "
+                        "val_weighted_* in the history; unit weights without --class_weight")
     p.add_argument("--epochs", type=int, default=None)
     p.add_argument("--batch_size", type=int, default=None)
     p.add_argument("--pred_batch_size", type=int, default=None)
@@ -378,12 +381,14 @@ def main(argv=None, model=None, script=None):
     model = build_model(args, cols)
     # final mode compiles without metrics: a single-class batch would make AUC undefined (xdftrain.py:607-621)
     model.compile(optimizer=make_optimizer(args, model), loss="binary_crossentropy",
-                  metrics=[] if final else ["binary_crossentropy", "auc"])
+                  metrics=[] if final else ["binary_crossentropy", "auc"],
+                  **({"weighted_metrics": ["binary_crossentropy", "auc"]} if args.weighted_metrics and not final else {}))
     for pg in model.optim.param_groups:
         pg["lr"] = args.learning_rate
 
     stem = {"xdeepfm": "xdeepfm", "attn": "xdeepfm_attn", "pro": "xdeepfm_pro"}[args.model]
-    config = {k: (list(v) if isinstance(v, tuple) else v) for k, v in vars(args).items()}
+    config = {k: (list(v) if isinstance(v, tuple) else v) for k, v in vars(args).items()
+              if k != "weighted_metrics" or v}           # without the flag the written files are what they were
     if final:
         hist = model.fit({k: xtr[k] for k in names}, train_t["label"].reshape(-1, 1), batch_size=args.batch_size,
                          epochs=args.epochs, verbose=args.verbose, validation_split=0.0, shuffle=True,
