@@ -353,7 +353,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_rows_kernel(
     const int QE = (D + 3) / 4 + ((D & 3) ? 1 : 0);     // chunks a row of D floats can straddle
     const int QT = QE + (has_lin ? 1 : 0);
     const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
-    const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+    const AdamCoef c = adam_uniform(AdamCoef{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps});
     const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
     float zf;
     asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
@@ -393,7 +393,7 @@ __device__ __forceinline__ void adam_apply_rows_body(
     const long idx = bid * ADAM_THREADS + threadIdx.x;
     const long nrow = (long)B * m * QT;
     const float ss = consts[ADAM_CONSTS_PER_STEP * t], bc = consts[ADAM_CONSTS_PER_STEP * t + 1];
-    const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+    const AdamCoef c = adam_uniform(AdamCoef{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps});
     const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
     float zf;
     asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
@@ -506,7 +506,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_catchup_by_row_kernel(
     const int t = clock[0];
     const int Q = D / 4;
     const long idx = (long)blockIdx.x * ADAM_THREADS + threadIdx.x;
-    const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+    const AdamCoef c = adam_uniform(AdamCoef{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps});
     const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
     float zf;
     asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
@@ -552,7 +552,7 @@ __device__ __forceinline__ void adam_apply_by_row_body(
     const long idx = bid * ADAM_THREADS + threadIdx.x;
     const long nrow = (long)B * m * (has_lin ? 2 : 1);
     const float ss = consts[ADAM_CONSTS_PER_STEP * t], bc = consts[ADAM_CONSTS_PER_STEP * t + 1];
-    const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+    const AdamCoef c = adam_uniform(AdamCoef{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps});
     const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
     float zf;
     asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
@@ -686,12 +686,13 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_flush_kernel(const AdamBatc
     unsigned char* __restrict__ last = d.last;
     const long n4 = d.numel / 4;
     const float l2c = d.l2;
-    const float g2 = 2.f * l2c;
+    const float g2 = adam_uniform(2.f * l2c);
     float zf;
     asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
-    const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+    const AdamCoef c = adam_uniform(AdamCoef{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps});
     adam_f2 sq2 = {0.f, 0.f};
     const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
+    const unsigned tx16 = threadIdx.x * 16u;
     // whole-wave iterations (the replay lines the lanes up on the step number): the tail lanes are masked, not absent
     for (long base = (long)lb * ADAM_THREADS; base < n4; base += (long)nb * ADAM_THREADS) {
         const long i = base + threadIdx.x;
@@ -699,9 +700,11 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_flush_kernel(const AdamBatc
         const int old = in ? (int)last[i] : 0;
         const bool act = in && old < t;
         float4 pa = make_float4(0.f, 0.f, 0.f, 0.f), ma = pa, va = pa;
-        if (act) { pa = tbl_ld<true>(p4 + i); ma = tbl_ld<true>(m4 + i); va = tbl_ld<true>(v4 + i); }
-        adam_replay_span(pa, ma, va, act, old, t, consts, g2, zf, c, sq2, eps_ok);
-        if (act) { tbl_st<true>(p4 + i, pa); tbl_st<true>(m4 + i, ma); tbl_st<true>(v4 + i, va); }
+        // (addresses: the iteration's wave-uniform base plus one 32-bit lane offset, as in the step's loops -- three 64-bit
+        // per-lane pointers would sit in registers through the whole replay)
+        if (act) { pa = tbl_ld<true>(at4(p4 + base, tx16)); ma = tbl_ld<true>(at4(m4 + base, tx16)); va = tbl_ld<true>(at4(v4 + base, tx16)); }
+        adam_replay_span<true>(pa, ma, va, act, old, t, consts, g2, zf, c, sq2, eps_ok);
+        if (act) { tbl_st<true>(at4(p4 + base, tx16), pa); tbl_st<true>(at4(m4 + base, tx16), ma); tbl_st<true>(at4(v4 + base, tx16), va); }
         if (in && old) last[i] = 0;
     }
     adam_backlog_add(l2c * (sq2.x + sq2.y), backlog);
@@ -764,7 +767,7 @@ __global__ __launch_bounds__(256) void adam_selftest_kernel(int mode, unsigned l
             done = 1; bad = __float_as_uint(fast) != __float_as_uint(ref) && !(fast == 0.f && ref == 0.f);
             what = ((unsigned long long)__float_as_uint(nn) << 32) | __float_as_uint(d);
         } else {                            // whole replayed steps against adam_one, states incl. zeros / denormals / huge values
-            const AdamCoef c = {(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps};
+            const AdamCoef c = adam_uniform(AdamCoef{(float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), 0.f, (float)eps});
             const bool eps_ok = c.eps >= ADAM_EPS_MIN && c.eps <= 1.f;
             float zf;
             asm volatile("v_mov_b32 %0, 0" : "=v"(zf));
